@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s of the MI355X wavefront path tracer on BASELINE.json's configs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1|c5] [--spp-per-step S] [--inproc]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1|c5] [--spp-per-step S] [--inproc] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch: S samples per pixel of the whole frame (raygen ->
 {closest-hit, shade/BSDF/NEE, shadow} x bounces -> accumulate).  Default workload: C3 (BASELINE.json configs[2]: the
@@ -17,8 +17,12 @@ sharding, no exchange while rendering — then ONE RCCL all-reduce (sum) of the 
 timed region.  Weak scaling: per-GPU work is fixed.  `--inproc` instead drives all N devices from ONE process through the
 library's own multi-device entry (pt_create with a device list; host thread + stream per device; ncclAllReduce inside).
 
-The timed region runs with per-kernel timing OFF; kernel times come from a second, separately timed pass of the same
-steps with HIP events around every launch (on the renderer's stream).  Rank 0 prints ONE JSON line with
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the K timed steps, the outputs (--dump-outputs DIR:
+the float accumulator the timed steps left, as DIR/accumulator.npy; a fixed, seeded sample of its pixels when it exceeds 64 MB), and
+ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed step, config, extra).
+
+--full adds what is measured beside it.  The timed region runs with per-kernel timing OFF; kernel times come from a second, separately
+timed pass of the same steps with HIP events around every launch (on the renderer's stream).  With --full rank 0's JSON line also holds
   roofline          the kernel with the largest device time, against every ceiling that could bind it
   roofline_kernels  the same block for each hot kernel (k_shade, k_trace_closest, k_trace_shadow)
   cpu_baseline      (N = 1) the product's own stage functions compiled for the host (tests/emu) on all host cores, bounded sample of the
@@ -134,6 +138,12 @@ def parse_args(argv=None):
                          "by the watchdog); 0 = off")
     ap.add_argument("--test-stall-after-start", action="store_true", help=argparse.SUPPRESS)   # tests/test_multi_gpu_gloo.py only: a rank that never comes back
     ap.add_argument("--spp", type=int, default=0, help="--strong: total samples per pixel of the render (default: the workload's full spp, 1024 for c3 = C4)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beside the headline figure: the instrumented traversal sample, the event-timed kernel pass "
+                         "(extra.kernel_ms), the roofline blocks and the CPU baseline (N = 1); a plain run only warms up and times the steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the accumulator they computed to DIR/accumulator.npy (float32, H x W x 4; above 64 MB a "
+                         "fixed, seeded sample of its pixels: accumulator_sample.npy + accumulator_sample_pixel.npy)")
     return ap.parse_args(argv)
 
 
@@ -330,6 +340,27 @@ def kernel_block(name, items, item_name, ms, launches, alg_bytes_per_item, pmc, 
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 20   # 16 MB of float32 RGBA
+DUMP_SAMPLE_SEED = 1729
+
+
+def dump_outputs(out_dir, acc):
+    """The accumulator the timed steps left (H x W x 4 float32) as <out_dir>/accumulator.npy; one larger than DUMP_LIMIT_BYTES (C5 at 3840x2160)
+    as a fixed, seeded sample of DUMP_SAMPLE_PIXELS pixels (accumulator_sample.npy) with their row-major pixel indices
+    (accumulator_sample_pixel.npy, float64: exact below 2^53)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    acc = np.ascontiguousarray(acc, dtype=np.float32)
+    if acc.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "accumulator.npy"), acc)
+        return
+    flat = acc.reshape(-1, acc.shape[-1])
+    pix = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.shape[0], size=min(DUMP_SAMPLE_PIXELS, flat.shape[0]), replace=False))
+    np.save(os.path.join(out_dir, "accumulator_sample.npy"), flat[pix])
+    np.save(os.path.join(out_dir, "accumulator_sample_pixel.npy"), pix.astype(np.float64))
+
+
 def main():
     args = parse_args()
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: what RCCL / cross-process tensor sharing need on this pool
@@ -513,7 +544,7 @@ def main():
     pass_allowance = args.rank_timeout + 4.0 * step_s * K
     # ---- instrumented sample (outside the timed region): BVH nodes / triangles fetched per ray ----
     nodes_c = tris_c = nodes_s = tris_s = 0.0
-    if not args.pmc_pass:
+    if args.full and not args.pmc_pass:
         start(total_spp, first)
         r.measureTraversal(first)
         st0 = r.stats()
@@ -535,10 +566,12 @@ def main():
     spp_all = total_spp * (1 if inproc else world)   # samples per pixel the whole job accumulated in the timed region
     value = W * H * spp_all * B / elapsed / 1e6
     mean_radiance = float(acc[..., :3].mean().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, acc.cpu().numpy())   # before the kernel pass below starts the render again
 
-    # ---- kernel pass: the same K steps again with HIP events around every launch (not part of `value`) ----
+    # ---- kernel pass (--full): the same K steps again with HIP events around every launch (not part of `value`) ----
     ks, elapsed_k = st, None
-    if not args.pmc_pass and not args.no_kernel_pass:
+    if args.full and not args.pmc_pass and not args.no_kernel_pass:
         start(total_spp, first)
         r.setProfiling(True)
         elapsed_k = timed_pass()
@@ -562,13 +595,13 @@ def main():
         del src, dst
 
     lib_sha = library_sha16()
-    pmc, pmc_src = load_pmc_profile(args.workload)
+    pmc, pmc_src = load_pmc_profile(args.workload) if args.full else (None, None)
     if rank == 0 and pmc is not None:
         stale = bool(lib_sha and pmc.get("library_sha16") and pmc["library_sha16"] != lib_sha)
         print("bench.py: counter figures from %s (taken on library %s; this library %s%s)" % (pmc_src, pmc.get("library_sha16"), lib_sha,
               " - STALE: the roofline's counter bytes are NOT of this build, re-run tools/profile_round.sh" if stale else ""), file=sys.stderr)
     blocks = {}
-    if ks.ms_closest > 0:
+    if args.full and ks.ms_closest > 0:
         blocks["k_trace_closest"] = kernel_block(
             "k_trace_closest", ks.closest_rays, "rays", ks.ms_closest, ks.launches_closest, algorithmic_bytes_closest(nodes_c, tris_c), pmc, pmc_src,
             lib_sha, {"nodes_per_ray": round(nodes_c, 2), "tris_per_ray": round(tris_c, 2)})
@@ -635,12 +668,12 @@ def main():
     if calib_copy:
         out["calibration_copy"] = calib_copy
 
-    # ---- CPU baseline (rank 0, N = 1 only), bounded sample of the same workload ----
+    # ---- CPU baseline (--full; rank 0, N = 1 only), bounded sample of the same workload ----
     # "the same __host__ __device__ kernels built for the host, all host cores" - tests/emu compiles the product's own
     # stage functions (platinum_amd/csrc/pt_*.h: sampler, camera, 6-wide traversal, BSDF, NEE / MIS, accumulate) with g++ -ffp-contract=off and
     # runs them on std::thread workers over 16x16 pixel tiles (kind "same-kernels-host").  The scalar oracle (oracle/pt_oracle.cpp, its own
     # median-split BVH) is timed beside it on a shorter sample (`oracle`, kind "port").  Neither is the target; the roofline is.
-    if members_all == 1 and not args.no_cpu_baseline and not args.pmc_pass:
+    if args.full and members_all == 1 and not args.no_cpu_baseline and not args.pmc_pass:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import numpy as _np
         import emu_lib

@@ -682,36 +682,49 @@ def test_radiance_hdr_environment_reader(tmp_path, rle):
 
 
 EXRWRITE_PATH = os.path.join(sf.ROOT, "oracle", "_ref", "exrwrite")
+EXR_TINYEXR_WRITTEN_CASES = [("piz", "half", 3, (70, 51)), ("piz", "float", 4, (33, 64)), ("piz", "half", 1, (40, 40)),
+                             ("piz", "half", 4, (5, 3)), ("zip", "half", 3, (70, 51)), ("rle", "float", 3, (20, 31))]
 
 
-@pytest.mark.skipif(not (os.path.exists(EXRWRITE_PATH) and os.path.exists(sf.EXR2RAW_PATH)), reason="oracle/_ref (reference tinyexr) not built")
-@pytest.mark.parametrize("comp,ptype,chans,shape", [("piz", "half", 3, (70, 51)), ("piz", "float", 4, (33, 64)), ("piz", "half", 1, (40, 40)),
-                                                     ("piz", "half", 4, (5, 3)), ("zip", "half", 3, (70, 51)), ("rle", "float", 3, (20, 31))])
-def test_exr_files_written_by_the_reference_tinyexr(tmp_path, comp, ptype, chans, shape):
-    """Files ENCODED by the reference's own tinyexr (oracle/_ref/exrwrite) — the only PIZ encoder here — read by the product and by
-    the reference's LoadEXR to the same bits.  Smooth + noisy + constant content: both wavelet modes (14 / 16 bit), Huffman
-    run-length codes and long codes get exercised."""
-    import subprocess
+def exr_tinyexr_written_image(ptype, chans, shape):
+    """Smooth + noisy + constant content (float32, H x W x chans) for the files the reference's tinyexr encodes."""
     h, w = shape
     rng = np.random.default_rng(h * 131 + w)
     yy, xx = np.mgrid[0:h, 0:w]
     img = np.stack([np.sin(xx * 0.2) * 3 + 4, (yy * xx) % 7 * 0.5, rng.random((h, w)) * (60000.0 if ptype == "half" else 1e6), np.full((h, w), 0.75)], -1)[..., :chans]
     img[: h // 3, : w // 2] = 1.5   # a constant region -> run-length codes
-    img = np.ascontiguousarray(img, dtype=f32)
-    raw = str(tmp_path / "in.f32"); path = str(tmp_path / "t.exr")
-    img.tofile(raw)
-    subprocess.check_call([EXRWRITE_PATH, raw, str(w), str(h), str(chans), ptype, comp, path])
-    sc = scene_io.SceneFile.empty()
-    sc.load_environment(path)
-    sc.add_camera((0, 0, 3), (0, 0, 0))
-    got = _env_pixels(sc)
-    ref = sf.tinyexr_reference_rgba(path, str(tmp_path))
-    assert got.shape == (h, w, 4) and got.tobytes() == ref.tobytes()
+    return np.ascontiguousarray(img, dtype=f32)
+
+
+@pytest.mark.parametrize("comp,ptype,chans,shape", EXR_TINYEXR_WRITTEN_CASES)
+def test_exr_files_written_by_the_reference_tinyexr(tmp_path, comp, ptype, chans, shape):
+    """Files ENCODED by the reference's own tinyexr (oracle/_ref/exrwrite) — the only PIZ encoder here — read by the product and by
+    the reference's LoadEXR to the same bits.  Smooth + noisy + constant content: both wavelet modes (14 / 16 bit), Huffman
+    run-length codes and long codes get exercised.  tests/golden/exr_tinyexr_written.npz holds each file and what LoadEXR reads from it
+    (tools/make_golden.py); where oracle/_ref was built, a file freshly encoded by exrwrite is checked the same way."""
+    import subprocess
+    h, w = shape
+    img = exr_tinyexr_written_image(ptype, chans, shape)
     want = img.astype(np.float16).astype(f32) if ptype == "half" else img
-    if chans >= 3:
-        assert np.array_equal(got[..., :3], want[..., :3])
-    else:
-        assert np.array_equal(got[..., 0], want[..., 0]) and np.array_equal(got[..., 3], want[..., 0])
+    k = EXR_TINYEXR_WRITTEN_CASES.index((comp, ptype, chans, shape))
+    g = np.load(os.path.join(G, "exr_tinyexr_written.npz"))
+    files = [(os.path.join(str(tmp_path), "stored.exr"), g[f"rgba_{k}"])]
+    g[f"exr_{k}"].tofile(files[0][0])
+    if os.path.exists(EXRWRITE_PATH) and os.path.exists(sf.EXR2RAW_PATH):
+        raw = str(tmp_path / "in.f32"); path = str(tmp_path / "t.exr")
+        img.tofile(raw)
+        subprocess.check_call([EXRWRITE_PATH, raw, str(w), str(h), str(chans), ptype, comp, path])
+        files.append((path, sf.tinyexr_reference_rgba(path, str(tmp_path))))
+    for path, ref in files:
+        sc = scene_io.SceneFile.empty()
+        sc.load_environment(path)
+        sc.add_camera((0, 0, 3), (0, 0, 0))
+        got = _env_pixels(sc)
+        assert got.shape == (h, w, 4) and got.tobytes() == ref.tobytes(), path
+        if chans >= 3:
+            assert np.array_equal(got[..., :3], want[..., :3])
+        else:
+            assert np.array_equal(got[..., 0], want[..., 0]) and np.array_equal(got[..., 3], want[..., 0])
 
 
 def test_committed_piz_fixture():
@@ -800,14 +813,9 @@ def test_jpeg_decoder_reproduces_the_reference_stb_image_on_the_committed_files(
         assert got.shape == g[f"rgba_{k}"].shape and np.array_equal(got, g[f"rgba_{k}"]), k
 
 
-def test_jpeg_decoder_vs_the_reference_stb_image_over_many_variants(tmp_path):
-    """Every sampling mode x baseline / progressive (libjpeg's scripts use successive approximation) / optimised tables /
-    restart intervals x odd sizes down to 1x1: byte-identical to stb_image v2.30 compiled from the reference tree."""
-    pytest.importorskip("PIL")
-    if not sf.stbi_available():
-        pytest.skip("oracle/_ref/stbi2raw not built (reference tree absent)")
-    import io
-    n = 0
+def jpeg_variant_cases():
+    """(w, h, mode, PIL save options): every sampling mode x baseline / progressive / optimised tables / restart intervals x odd sizes."""
+    out = []
     for (w, h) in [(1, 1), (7, 5), (16, 16), (33, 17), (129, 97), (250, 3)]:
         for mode in ("RGB", "L", "CMYK"):
             for kw in (dict(quality=90, subsampling=0), dict(quality=75, subsampling=1), dict(quality=60, subsampling=2),
@@ -815,12 +823,38 @@ def test_jpeg_decoder_vs_the_reference_stb_image_over_many_variants(tmp_path):
                        dict(quality=80, subsampling=2, restart_marker_blocks=3)):
                 if mode != "RGB":
                     kw = {k: v for k, v in kw.items() if k != "subsampling"}
-                buf = io.BytesIO()
-                jpeg_test_image(w, h, mode).save(buf, "JPEG", **kw)
-                path = tmp_path / "t.jpg"
-                path.write_bytes(buf.getvalue())
-                assert np.array_equal(scene_io.decode_image_rgba8(buf.getvalue()), sf.stbi_reference_rgba(path)), (w, h, mode, kw)
-                n += 1
+                out.append((w, h, mode, kw))
+    return out
+
+
+def test_jpeg_decoder_vs_the_reference_stb_image_over_many_variants(tmp_path):
+    """Every sampling mode x baseline / progressive (libjpeg's scripts use successive approximation) / optimised tables /
+    restart intervals x odd sizes down to 1x1: byte-identical to stb_image v2.30 compiled from the reference tree.
+    tests/golden/jpeg_stb_variants.npz holds the 108 files and a sha256 of the RGBA8 stb_image decodes from each (tools/make_golden.py);
+    where oracle/_ref was built, freshly encoded files are compared with its decode as well."""
+    import hashlib
+    cases = jpeg_variant_cases()
+    g = np.load(os.path.join(G, "jpeg_stb_variants.npz"))
+    assert len(cases) == 108 and len(g["rgba_sha256"]) == len(cases)
+    for k, case in enumerate(cases):
+        got = scene_io.decode_image_rgba8(g[f"jpg_{k}"].tobytes())
+        assert got.shape == tuple(g["rgba_shape"][k]), case
+        assert hashlib.sha256(np.ascontiguousarray(got).tobytes()).digest() == g["rgba_sha256"][k].tobytes(), case
+    try:
+        import PIL  # noqa: F401  (the live leg's encoder)
+    except ImportError:
+        return
+    if not sf.stbi_available():
+        return
+    import io
+    n = 0
+    for (w, h, mode, kw) in cases:
+        buf = io.BytesIO()
+        jpeg_test_image(w, h, mode).save(buf, "JPEG", **kw)
+        path = tmp_path / "t.jpg"
+        path.write_bytes(buf.getvalue())
+        assert np.array_equal(scene_io.decode_image_rgba8(buf.getvalue()), sf.stbi_reference_rgba(path)), (w, h, mode, kw)
+        n += 1
     assert n == 108
 
 

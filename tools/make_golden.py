@@ -18,6 +18,10 @@ as small fixtures under tests/golden/.  Re-running must reproduce the files bit-
   exr_piz_tiled_fixture.* the same for a 70x45 file in 32x16 PIZ tiles (oracle/_ref/exrwrite … 32 16)
   jpeg_stb_fixture.npz    nine small JPEG files (baseline / progressive, 4:4:4 / 4:2:2 / 4:2:0, grey, CMYK, restart markers) and the RGBA8
                           the reference's vendored stb_image (oracle/_ref/stbi2raw) decodes from each
+  exr_tinyexr_written.npz the six files of test_exr_files_written_by_the_reference_tinyexr, ENCODED by the reference's tinyexr
+                          (oracle/_ref/exrwrite), and the RGBA floats its LoadEXR decodes from each (oracle/_ref/exr2raw)
+  jpeg_stb_variants.npz   the 108 JPEG files of test_jpeg_decoder_vs_the_reference_stb_image_over_many_variants (PIL / libjpeg) and a
+                          sha256 + shape of the RGBA8 the reference's stb_image decodes from each
   n3_textured_golden.npz  scenes.textured_scene() (textures, normal map, cut-outs, environment), 96x54, 6 bounces: accumulator
                           at 2 spp, per-bounce hit ids of sample 0, the environment alias table
 """
@@ -100,8 +104,17 @@ if os.path.exists(exrwrite) and os.path.exists(exr2raw):
         env2.tofile(os.path.join(td, "in2.f32"))
         subprocess.check_call([exrwrite, os.path.join(td, "in2.f32"), "70", "45", "3", "half", "piz", os.path.join(G, "exr_piz_tiled_fixture.exr"), "32", "16"])
         np.savez_compressed(os.path.join(G, "exr_piz_tiled_fixture.npz"), rgba=sf.tinyexr_reference_rgba(os.path.join(G, "exr_piz_tiled_fixture.exr"), td))
+    fx = {}
+    for k, (comp, ptype, chans, (h, w)) in enumerate(tsi.EXR_TINYEXR_WRITTEN_CASES):
+        with tempfile.TemporaryDirectory() as td:
+            tsi.exr_tinyexr_written_image(ptype, chans, (h, w)).tofile(os.path.join(td, "in.f32"))
+            path = os.path.join(td, "t.exr")
+            subprocess.check_call([exrwrite, os.path.join(td, "in.f32"), str(w), str(h), str(chans), ptype, comp, path])
+            fx[f"exr_{k}"] = np.fromfile(path, np.uint8)
+            fx[f"rgba_{k}"] = sf.tinyexr_reference_rgba(path, td)
+    np.savez_compressed(os.path.join(G, "exr_tinyexr_written.npz"), **fx)
 else:
-    print("oracle/_ref/exrwrite not built: exr_piz_fixture left as is")
+    print("oracle/_ref/exrwrite not built: exr_piz_fixture and exr_tinyexr_written.npz left as is")
 # ---- N4: JPEG files (encoded by PIL / libjpeg: test infrastructure) and the RGBA8 the REFERENCE's stb_image decodes from them ----
 stbi2raw = os.path.join(ROOT, "oracle", "_ref", "stbi2raw")
 try:
@@ -121,7 +134,20 @@ if os.path.exists(stbi2raw) and Image is not None:
             fx[f"jpg_{k}"] = np.frombuffer(data, np.uint8)
             fx[f"rgba_{k}"] = sf.stbi_reference_rgba(path)
     np.savez_compressed(os.path.join(G, "jpeg_stb_fixture.npz"), **fx)
+    fx, digests, shapes = {}, [], []
+    for k, (w, h, mode, kw) in enumerate(tsi.jpeg_variant_cases()):
+        buf = io.BytesIO()
+        tsi.jpeg_test_image(w, h, mode).save(buf, "JPEG", **kw)
+        data = buf.getvalue()
+        with tempfile.TemporaryDirectory() as td:
+            path = os.path.join(td, "t.jpg")
+            open(path, "wb").write(data)
+            rgba = sf.stbi_reference_rgba(path)
+        fx[f"jpg_{k}"] = np.frombuffer(data, np.uint8)
+        digests.append(np.frombuffer(hashlib.sha256(np.ascontiguousarray(rgba).tobytes()).digest(), np.uint8))
+        shapes.append(rgba.shape)
+    np.savez_compressed(os.path.join(G, "jpeg_stb_variants.npz"), rgba_sha256=np.stack(digests), rgba_shape=np.array(shapes, np.int32), **fx)
 else:
-    print("oracle/_ref/stbi2raw or PIL missing: jpeg_stb_fixture.npz left as is")
+    print("oracle/_ref/stbi2raw or PIL missing: jpeg_stb_fixture.npz and jpeg_stb_variants.npz left as is")
 for f in sorted(os.listdir(G)):
     print(f, os.path.getsize(os.path.join(G, f)))

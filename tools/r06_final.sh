@@ -16,6 +16,7 @@ fi
 [ "$stage" = profiles ] && exit 0
 bench() { # name timeout args...
   n=$1; t=$2; shift 2
+  set -- --full "$@"   # the summary below reads the kernel times, the roofline and the CPU baseline
   timeout -k 10 $t python bench.py "$@" > gpurun_out/${tag}_$n.json 2> gpurun_out/${tag}_$n.err || { tail -8 gpurun_out/${tag}_$n.err; fail "bench $n failed"; }
   grep -q "STALE" gpurun_out/${tag}_$n.err && fail "bench $n used a STALE counter file (the profile passes above did not update profiles/)"
 }

@@ -160,7 +160,7 @@ GATHER_FACTOR = {"k_trace_closest": 1.0, "k_trace_shadow": 1.0, "k_trace_closest
 STREAM_IN_BYTES = {"k_shade": 68.0}
 
 lines = [f"# rocprofv3 summary — bench.py --workload {wl} (MI355X, {tag})", "",
-         "Durations: `rocprofv3 --kernel-trace --stats -- python3 bench.py --workload %s --no-cpu-baseline` (both of bench.py's passes)." % wl,
+         "Durations: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --workload %s --no-cpu-baseline` (both of bench.py's passes)." % wl,
          "Counters: separate `--pmc` passes of `bench.py --workload %s --pmc-pass --steps 2` (full batches of the library's own size only: 128 spp at 1080p)." % wl, "",
          "Calibration on known byte counts: " + json.dumps({k: (round(v, 4) if isinstance(v, float) and v < 100 else v) for k, v in calib.items()}), "",
          "| kernel | calls | total ms | avg ms | FETCH raw MiB/launch | FETCH corrected MiB/launch (x%.2f streams, x1 gathers, k_shade split: r02_calib_gather.md) | WRITE MiB/launch | HBM B/item (corr.) | VALU wave-insts/item | items |" % ff,
