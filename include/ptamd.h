@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 4u /* 4: pt_get_runtime_info, PT_ERR_RUNTIME_CONFLICT, pt_stats::leaf_slots */
+#define PT_ABI_VERSION 5u /* 4: pt_get_runtime_info, PT_ERR_RUNTIME_CONFLICT, pt_stats::leaf_slots; 5: AOVs + denoiser (pt_create accepts 4 and 5) */
 
 /* ---------------------------------------------------------------------------------------------------------- */
 /* Enums (same numeric values as the reference)                                                                 */
@@ -378,6 +378,35 @@ int pt_present_render_target(pt_renderer* r, void** device_rgba8_out, void** str
 int pt_read_accumulator(pt_renderer* r, float* rgba_out);
 /* Device address of the accumulator (for an RCCL reduce by the caller); NULL before pt_start_render. */
 void* pt_accumulator_device_ptr(pt_renderer* r);
+
+
+/* ---- first-hit AOVs and the denoiser (NEW, ABI 5; no reference counterpart) -----------------------------------------------
+ * A render started while `enabled` is set keeps three W*H RGBA32F images beside the accumulator, running means over its samples
+ * folded per pixel in sample order like the accumulator (the same bits however the samples are batched):
+ *   PT_AOV_ALBEDO   rgb: linear base colour at the camera ray's first hit (base texture included); a miss contributes (1,1,1).  a: 1
+ *   PT_AOV_NORMAL   rgb: world-space shading normal at the first hit (normal map included); a miss contributes 0.  a: hit fraction h
+ *   PT_AOV_MOMENTS  r: first-hit distance (a miss contributes 0; mean depth = r / h); g, b: means of lum(L) and lum(L)^2 of the
+ *                   sample radiance after the non-finite policy, lum = (0.2126, 0.7152, 0.0722).  a: 0
+ * The accumulator and every other result are the same bits with AOVs on or off.  AOVs cost 32 bytes per path slot: with
+ * samples_in_flight = 0 the renderer counts them when it sizes its batches (pt_plan_queues describes AOV-off renders).
+ * The denoiser is an edge-avoiding a-trous filter (SVGF's spatial filter: Dammertz et al. 2010, Schied et al. 2017, no temporal
+ * part) guided by the AOVs, run on demand over the current image (DESIGN.md section 3 states its arithmetic).
+ * A device group (device_count >= 2) refuses enabled = 1 with PT_ERR_UNSUPPORTED: merging the AOVs would take one more all-reduce. */
+typedef struct pt_denoise_options {
+  uint32_t enabled;          /* accumulate AOVs for renders started from now on (read at pt_start_render) */
+  uint32_t iterations;       /* 0..8, default 5; 0 = demodulate + remodulate only (the accumulator itself) */
+  float sigma_luminance, sigma_normal, sigma_depth;   /* 4, 128, 1: finite and > 0 */
+  uint32_t apply_to_target;  /* pt_read_render_target / pt_present_render_target post-process the denoised image (of a render
+                                started with AOVs; a render without them shows its accumulator as before) */
+} pt_denoise_options;
+enum { PT_AOV_ALBEDO = 0, PT_AOV_NORMAL = 1, PT_AOV_MOMENTS = 2 };
+void pt_default_denoise_options(pt_denoise_options* o);
+/* The filter fields take effect at the next read or present, `enabled` at the next pt_start_render. */
+int pt_set_denoise_options(pt_renderer* r, const pt_denoise_options* o);
+/* One AOV image (W*H*4 floats).  Blocks like pt_read_accumulator.  PT_ERR_BAD_STATE for a render started without AOVs. */
+int pt_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out);
+/* The denoised image (W*H*4 floats, alpha 1).  Blocks.  PT_ERR_BAD_STATE for a render started without AOVs. */
+int pt_read_denoised(pt_renderer* r, float* rgba_out);
 
 const char* pt_last_error(void);
 

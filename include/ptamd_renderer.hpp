@@ -28,6 +28,9 @@
  *   color::Colorspace& outputColorspace()               :73      pt_colorspace& (the four chromaticity pairs a color::Colorspace is built from)
  *        the caller edits them in place; they are flattened and handed to the library whenever an image is asked for (the reference's
  *        passes read theirs when they are encoded)
+ *   (no counterpart)                                             pt_denoise_options& denoiseOptions() / setDenoiseOptions(...), readbackAov(kind),
+ *                                                                readbackDenoised(): first-hit AOVs and the a-trous denoiser (ptamd.h, ABI 5);
+ *                                                                `enabled` is handed over at startRender, the rest whenever an image is asked for
  * Error behaviour as the reference's: nothing throws; a failing call prints "renderer_pt: <message>" to stderr (the
  * reference prints and asserts, renderer_pt.cpp:402, 1044) and leaves the object in Status_Blocked; lastError() keeps the text.
  * Threading as the reference's: one caller thread per Renderer.
@@ -100,6 +103,7 @@ public:
     p.samples_in_flight = m_samplesInFlight;
     p.nonfinite_policy = m_nonfinitePolicy;
     p.accel_structure = m_accelStructure;
+    if (!check(pt_set_denoise_options(m_pt, &m_denoise))) return;   // (`enabled` is read here)
     if (!check(pt_start_render(m_pt, &scene, &p))) return;
     m_size = uint2{p.width, p.height};
     m_started = true;
@@ -168,6 +172,25 @@ public:
     if (!check(pt_read_accumulator(m_pt, out.data()))) out.clear();
     return out;
   }
+  // First-hit AOVs and the denoiser (ptamd.h, ABI 5).  Edited in place like gmonOptions().
+  [[nodiscard]] constexpr pt_denoise_options& denoiseOptions() { return m_denoise; }
+  void setDenoiseOptions(const pt_denoise_options& o) { m_denoise = o; }
+  // One AOV image (PT_AOV_*), W*H RGBA32F; empty for a render started without AOVs.  Blocks.
+  [[nodiscard]] std::vector<float> readbackAov(uint32_t kind) const {
+    std::vector<float> out;
+    if (!m_pt || !m_started || !check(pt_set_denoise_options(m_pt, &m_denoise))) return out;
+    out.resize((size_t)m_size.x * m_size.y * 4);
+    if (!check(pt_read_aov(m_pt, kind, out.data()))) out.clear();
+    return out;
+  }
+  // The denoised image, W*H RGBA32F; empty for a render started without AOVs.  Blocks.
+  [[nodiscard]] std::vector<float> readbackDenoised() const {
+    std::vector<float> out;
+    if (!m_pt || !m_started || !check(pt_set_gmon_options(m_pt, &m_gmonOptions)) || !check(pt_set_denoise_options(m_pt, &m_denoise))) return out;
+    out.resize((size_t)m_size.x * m_size.y * 4);
+    if (!check(pt_read_denoised(m_pt, out.data()))) out.clear();
+    return out;
+  }
   void wait() const { if (m_pt && m_started) check(pt_wait(m_pt)); }
   [[nodiscard]] bool ok() const { return m_pt != nullptr && m_lastError.empty(); }
   [[nodiscard]] const std::string& lastError() const { return m_lastError; }
@@ -178,6 +201,7 @@ private:
     pt_tonemap_options defaults;
     pt_default_tonemap_options(&defaults);
     m_outputSpace = defaults.output_space;   // Display P3 (renderer_pt.hpp:182)
+    pt_default_denoise_options(&m_denoise);
     std::vector<int32_t> ord(devices, devices + count);
     pt_create_info ci{};
     ci.abi_version = PT_ABI_VERSION;
@@ -199,7 +223,8 @@ private:
     pt_tonemap_options tonemap;
     postprocess::flatten(m_exposure, m_chromaticAberration, m_contrastSaturation, m_toneCurve, m_vignette, &post);
     postprocess::flatten(m_tonemap, m_outputSpace, &tonemap);
-    return check(pt_set_gmon_options(m_pt, &m_gmonOptions)) && check(pt_set_post_options(m_pt, &post)) && check(pt_set_tonemap_options(m_pt, &tonemap));
+    return check(pt_set_gmon_options(m_pt, &m_gmonOptions)) && check(pt_set_post_options(m_pt, &post)) && check(pt_set_tonemap_options(m_pt, &tonemap)) &&
+           check(pt_set_denoise_options(m_pt, &m_denoise));
   }
 
   pt_renderer* m_pt = nullptr;
@@ -216,6 +241,7 @@ private:
   postprocess::TonemapOptions m_tonemap;
   pt_colorspace m_outputSpace{};
   pt_gmon_options m_gmonOptions{1.0f};
+  pt_denoise_options m_denoise{};
   mutable void* m_presentStream = nullptr;
   mutable std::string m_lastError;
 };

@@ -7,7 +7,7 @@ library is missing or cannot find a device, loading / pt_create raises.
 import ctypes as C
 import os
 
-PT_ABI_VERSION = 4
+PT_ABI_VERSION = 5
 
 # renderer_pt.hpp:21-26
 STATUS_BLOCKED, STATUS_READY, STATUS_BUSY, STATUS_DONE = 0, 1, 4, 8
@@ -168,6 +168,14 @@ class TonemapOptions(C.Structure):
 TONEMAP_NONE, TONEMAP_AGX, TONEMAP_KHRONOS_PBR, TONEMAP_FLIM = 0, 1, 2, 3
 
 
+class DenoiseOptions(C.Structure):
+    _fields_ = [("enabled", C.c_uint32), ("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("apply_to_target", C.c_uint32)]
+
+
+AOV_ALBEDO, AOV_NORMAL, AOV_MOMENTS = 0, 1, 2
+
+
 class HitRecord(C.Structure):
     _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("instance", C.c_int32), ("primitive", C.c_int32)]
 
@@ -223,6 +231,10 @@ SYMBOLS = [
     ("pt_read_render_target", C.c_int, [C.c_void_p, C.c_void_p]),
     ("pt_present_render_target", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("pt_read_gmon_bucket", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("pt_default_denoise_options", None, [C.POINTER(DenoiseOptions)]),
+    ("pt_set_denoise_options", C.c_int, [C.c_void_p, C.POINTER(DenoiseOptions)]),
+    ("pt_read_aov", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("pt_read_denoised", C.c_int, [C.c_void_p, C.c_void_p]),
     ("pt_last_error", C.c_char_p, []),
     ("pt_get_constants", C.c_int, [C.c_void_p, C.POINTER(Constants)]),
     ("pt_get_lights", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),

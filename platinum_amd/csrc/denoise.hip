@@ -1,0 +1,181 @@
+// denoise.hip — first-hit AOVs and the a-trous denoiser on the device (pt_denoise.h holds the arithmetic; DESIGN.md §3 "Denoiser").
+//
+//   k_aov             after k_trace_closest(bounce 0), before k_shade(0): per camera ray, stage_aov -> Abuf[pid] (32 B)
+//   k_accumulate_aov  after k_accumulate / k_gmon: folds Abuf and Lbuf into the three AOV images, per pixel in sample order
+//   k_dn_prep         demodulation, variance, depth gradient
+//   k_atrous          one 5x5 step per launch (ping-pong); the last one remodulates
+// Only a render started with AOVs enabled launches any of them (renderer.hip enqueue_batch).
+//
+// Compiled with -ffp-contract=off (deterministic fp32 contract, pt_math.h).
+#include <hip/hip_runtime.h>
+
+#include "denoise.h"
+#include "pt_denoise.h"
+#include "queue_plan.h"
+
+namespace pt {
+
+// ---- queue / radiance-buffer indexing: the same functions as kernels.hip (seg_slot, segment_lbuf_base, lbuf_index) --------------
+#ifndef PT_SEG_GROUP
+#define PT_SEG_GROUP 16
+#endif
+#ifndef PT_PIXEL_MAJOR
+#define PT_PIXEL_MAJOR 1
+#endif
+static_assert(PT_SEG_GROUP == kSegGroupChunks, "queue_plan.h sizes the queue arrays for this interleaving");
+__device__ __forceinline__ uint32_t dn_wave_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+__device__ __forceinline__ uint32_t dn_seg_slot(uint32_t nseg, uint32_t s, uint32_t r) {
+  const uint32_t k = r >> 6;
+  return (((k / PT_SEG_GROUP) * nseg + s) * PT_SEG_GROUP + (k % PT_SEG_GROUP)) * 64u + (r & 63u);
+}
+__device__ __forceinline__ uint32_t dn_segment_lbuf_base(const Segments& seg, uint32_t sg) {
+  const uint32_t per_band = seg.nseg / seg.bands;
+  return ((sg % seg.bands) * per_band + sg / seg.bands) * seg.tiles_per_seg * seg.nsamples * 64u;
+}
+__device__ __forceinline__ uint32_t dn_lbuf_index(uint32_t tile, uint32_t s, uint32_t nsamples, uint32_t lane) {
+#if PT_PIXEL_MAJOR
+  return (tile * 64u + lane) * nsamples + s;
+#else
+  return (tile * nsamples + s) * 64u + lane;
+#endif
+}
+
+// ---- k_aov: the bounce-0 queue (state buffer 0) -> Abuf.  Reads the queue only. ----------------------------------------------------
+// Abuf[2 * pid] = {albedo, t}, Abuf[2 * pid + 1] = {normal, 1} for a hit; {1, 1, 1, 0}, {0, 0, 0, 0} for a miss.
+__global__ void __launch_bounds__(256) k_aov(const DeviceScene* __restrict__ Sp, PathState st, const vec4* __restrict__ hit, Segments seg,
+                                             vec4* __restrict__ Abuf) {
+  const DeviceScene& S = *Sp;
+  const uint32_t lane = dn_wave_lane();
+  const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = gridDim.x * (blockDim.x >> 6);
+  for (uint32_t sg = wave; sg < seg.nseg; sg += nwaves) {
+    const uint32_t n = seg.active[0][sg];
+    const uint32_t base = dn_segment_lbuf_base(seg, sg);
+    for (uint32_t k = lane; k < n; k += 64) {
+      const uint32_t i = dn_seg_slot(seg.nseg, sg, k);
+      const vec4 h4 = hit[i], d4 = st.rayD[i];
+      const uint32_t pid = base + (f2u(d4.w) >> kMetaPidShift);
+      AovSample a = aov_miss();
+      float hf = 0.0f;
+      if (f2u(h4.w) != kInvalidRef) {
+        const vec4 o4 = st.rayO[i];
+        ShadeIn in;
+        in.o = v3(o4.x, o4.y, o4.z);
+        in.d = v3(d4.x, d4.y, d4.z);
+        in.att = v3(1.0f);
+        in.rayO = &st.rayO[i];
+        in.rayD = &st.rayD[i];
+        in.lastSpecular = false;
+        in.offset = 0; in.dim = 0; in.bounce = 0;
+        in.t = h4.x; in.u = h4.y; in.v = h4.z;
+        in.tri = f2u(h4.w) & kHitTriMask;
+        a = stage_aov(S, in);
+        hf = 1.0f;
+      }
+      Abuf[2u * pid] = vec4{a.albedo.x, a.albedo.y, a.albedo.z, a.t};
+      Abuf[2u * pid + 1u] = vec4{a.normal.x, a.normal.y, a.normal.z, hf};
+    }
+  }
+}
+
+// ---- k_accumulate_aov: one wave per 8x8 tile, k_accumulate's layout ---------------------------------------------------------------
+// Eight samples of the tile's 64 pixels are staged through LDS per round for each of the three streams (Lbuf and the two halves of
+// Abuf), fully coalesced; every lane then folds the eight samples of its pixel in sample order.  One wave per block: the three
+// staging areas take 27 KB.
+__global__ void __launch_bounds__(64) k_accumulate_aov(vec4* __restrict__ albedo, vec4* __restrict__ normal, vec4* __restrict__ moments,
+                                                        const vec4* __restrict__ Abuf, const vec4* __restrict__ Lbuf, uint32_t width,
+                                                        uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy) {
+  constexpr uint32_t kRow = 9;
+  __shared__ vec4 stage[3][64 * kRow];
+  const uint32_t lane = dn_wave_lane();
+  const uint32_t tilesX = (width + 7u) / 8u, tiles = tilesX * ((height + 7u) / 8u);
+  const uint32_t tile = blockIdx.x;
+  const bool live = tile < tiles;
+  const uint32_t ty = live ? tile / tilesX : 0u, x = (tile - ty * tilesX) * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
+  const bool inside = live && x < width && y < height;
+  const size_t p = (size_t)y * width + x;
+  vec4 A = inside ? albedo[p] : vec4{0, 0, 0, 0}, N = inside ? normal[p] : vec4{0, 0, 0, 0}, M = inside ? moments[p] : vec4{0, 0, 0, 0};
+  for (uint32_t s0 = 0; s0 < nsamples; s0 += 8u) {
+    const uint32_t nb = nsamples - s0 < 8u ? nsamples - s0 : 8u;
+    __syncthreads();
+    if (live) {
+#pragma unroll
+      for (uint32_t i = 0; i < 8u; i++) {
+        const uint32_t px = i * 8u + (lane >> 3), j = lane & 7u;
+        if (j < nb) {
+          const uint32_t pid = dn_lbuf_index(tile, s0 + j, nsamples, px);
+          stage[0][px * kRow + j] = Lbuf[pid];
+          stage[1][px * kRow + j] = Abuf[2u * pid];
+          stage[2][px * kRow + j] = Abuf[2u * pid + 1u];
+        }
+      }
+    }
+    __syncthreads();
+    if (inside) {
+      for (uint32_t j = 0; j < nb; j++) {
+        const vec4 l4 = stage[0][lane * kRow + j], a4 = stage[1][lane * kRow + j], n4 = stage[2][lane * kRow + j];
+        vec3 L = v3(l4.x, l4.y, l4.z);
+        if (!(fabsf(L.x) <= 3.0e38f && fabsf(L.y) <= 3.0e38f && fabsf(L.z) <= 3.0e38f) && nonfinite_policy == PT_NONFINITE_ZERO) L = v3(0.0f);
+        const float lum = dn_lum(L);
+        const uint32_t n = n0 + s0 + j;
+        const vec3 a = aov_fold(v3(A.x, A.y, A.z), v3(a4.x, a4.y, a4.z), n);
+        const vec3 nn = aov_fold(v3(N.x, N.y, N.z), v3(n4.x, n4.y, n4.z), n);
+        const vec3 m = aov_fold(v3(M.x, M.y, M.z), v3(a4.w, lum, lum * lum), n);
+        A = vec4{a.x, a.y, a.z, 1.0f};
+        N = vec4{nn.x, nn.y, nn.z, aov_fold(N.w, n4.w, n)};
+        M = vec4{m.x, m.y, m.z, 0.0f};
+      }
+    }
+  }
+  if (inside) { albedo[p] = A; normal[p] = N; moments[p] = M; }
+}
+
+// ---- the filter: 16x16 pixel blocks -----------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_dn_prep(const vec4* __restrict__ acc, const vec4* __restrict__ albedo, const vec4* __restrict__ normal,
+                                                 const vec4* __restrict__ moments, uint32_t W, uint32_t H, float N, vec4* __restrict__ guide,
+                                                 vec4* __restrict__ col, vec4* __restrict__ aux) {
+  const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
+  if (x < W && y < H) dn_prep_pixel(acc, albedo, normal, moments, W, H, x, y, N, guide, col, aux);
+}
+
+__global__ void __launch_bounds__(256) k_atrous(const vec4* __restrict__ guide, const vec4* __restrict__ aux, const vec4* __restrict__ col_in,
+                                                vec4* __restrict__ col_out, const vec4* __restrict__ acc, vec4* __restrict__ out, DenoiseParams P,
+                                                uint32_t step, uint32_t last) {
+  const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
+  if (x < P.W && y < P.H) dn_iterate_pixel(guide, aux, col_in, col_out, acc, out, P, x, y, step, last != 0);
+}
+
+// iterations 0: demodulation and remodulation only, which is the identity: the accumulator itself (alpha 1)
+__global__ void __launch_bounds__(256) k_dn_copy(const vec4* __restrict__ acc, vec4* __restrict__ out, uint32_t npix) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p < npix) { const vec4 c = acc[p]; out[p] = vec4{c.x, c.y, c.z, 1.0f}; }
+}
+
+void launch_aov(hipStream_t s, uint32_t grid, const DeviceScene* S_device, PathState st, const vec4* hit, Segments seg, vec4* Abuf) {
+  hipLaunchKernelGGL(k_aov, dim3(grid), dim3(256), 0, s, S_device, st, hit, seg, Abuf);
+}
+
+void launch_accumulate_aov(hipStream_t s, vec4* albedo, vec4* normal, vec4* moments, const vec4* Abuf, const vec4* Lbuf, uint32_t width,
+                           uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy) {
+  static_assert(PT_PIXEL_MAJOR, "k_accumulate_aov stages the [pixel][sample] layout of a tile");
+  const uint32_t tiles = ((width + 7u) / 8u) * ((height + 7u) / 8u);
+  hipLaunchKernelGGL(k_accumulate_aov, dim3(tiles), dim3(64), 0, s, albedo, normal, moments, Abuf, Lbuf, width, height, nsamples, n0,
+                     nonfinite_policy);
+}
+
+void launch_denoise(hipStream_t s, const vec4* acc, const vec4* albedo, const vec4* normal, const vec4* moments, uint32_t W, uint32_t H,
+                    uint32_t nsamples, const DenoiseParams& P, uint32_t iterations, vec4* guide, vec4* aux, vec4* col0, vec4* col1, vec4* out) {
+  if (iterations == 0) {
+    hipLaunchKernelGGL(k_dn_copy, dim3((W * H + 255u) / 256u), dim3(256), 0, s, acc, out, W * H);
+    return;
+  }
+  const dim3 grid((W + 15u) / 16u, (H + 15u) / 16u), block(16, 16);
+  hipLaunchKernelGGL(k_dn_prep, grid, block, 0, s, acc, albedo, normal, moments, W, H, (float)nsamples, guide, col0, aux);
+  vec4* cin = col0;
+  vec4* cout = col1;
+  for (uint32_t i = 0; i < iterations; i++) {
+    hipLaunchKernelGGL(k_atrous, grid, block, 0, s, guide, aux, cin, cout, acc, out, P, 1u << i, i + 1 == iterations ? 1u : 0u);
+    vec4* t = cin; cin = cout; cout = t;
+  }
+}
+
+}  // namespace pt

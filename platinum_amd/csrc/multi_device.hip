@@ -543,7 +543,8 @@ int pt_rccl_selftest(int32_t device_ordinal) {
 int pt_create(const pt_create_info* info, pt_renderer** out) {
   if (!info || !out) return fail(PT_ERR_INVALID_ARGUMENT, "pt_create: null argument");
   *out = nullptr;
-  if (info->abi_version != PT_ABI_VERSION) return fail(PT_ERR_INVALID_ARGUMENT, "pt_create: ABI version mismatch");
+  // ABI 5 only added entry points: a version-4 caller gets exactly what it got before
+  if (info->abi_version != PT_ABI_VERSION && info->abi_version != 4u) return fail(PT_ERR_INVALID_ARGUMENT, "pt_create: ABI version mismatch");
   if (info->device_count == 0) return dev_create(info, info->device_ordinal, out);
   if (!info->device_ordinals) return fail(PT_ERR_INVALID_ARGUMENT, "pt_create: device_count without device_ordinals");
   if (info->device_count == 1) return dev_create(info, info->device_ordinals[0], out);
@@ -700,6 +701,25 @@ int pt_set_profiling(pt_renderer* r, int enabled) {
   if (!is_group(r)) return dev_set_profiling(r, enabled);
   for (auto* m : r->group->shards) { int rc = dev_set_profiling(m, enabled); if (rc != PT_OK) return rc; }
   return PT_OK;
+}
+
+// AOVs are per device; a group would have to merge them (one more all-reduce of 12 floats per pixel), which is not implemented
+int pt_set_denoise_options(pt_renderer* r, const pt_denoise_options* o) {
+  if (!is_group(r)) return dev_set_denoise_options(r, o);
+  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (o->enabled) return fail(PT_ERR_UNSUPPORTED, "pt_set_denoise_options: a device group does not keep AOVs");
+  for (auto* m : r->group->shards) { int rc = dev_set_denoise_options(m, o); if (rc != PT_OK) return rc; }
+  return PT_OK;
+}
+
+int pt_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out) {
+  if (!is_group(r)) return dev_read_aov(r, aov, rgba_out);
+  return fail(PT_ERR_BAD_STATE, "pt_read_aov: a device group does not keep AOVs");
+}
+
+int pt_read_denoised(pt_renderer* r, float* rgba_out) {
+  if (!is_group(r)) return dev_read_denoised(r, rgba_out);
+  return fail(PT_ERR_BAD_STATE, "pt_read_denoised: a device group does not keep AOVs");
 }
 
 int pt_get_stats(pt_renderer* r, pt_stats* out) {

@@ -87,6 +87,8 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
       ScopedTimer t(r, K_CLOSEST);
       launch_trace_closest(s, r->closest_grid, S, r->path_state(cur), r->hit.p, seg, (uint32_t)cur, ctr, b, r->spill.p, hitlog, S.width * S.height, count);
     }
+    // first-hit AOVs of a render that keeps them (denoise.hip): the camera rays' hits, read from the queue before k_shade consumes it
+    if (b == 0 && mode == BATCH_RENDER && r->aov) launch_aov(s, r->grid, r->scene_d.p, r->path_state(cur), r->hit.p, seg, r->Abuf.p);
     {
       ScopedTimer t(r, K_SHADE);
       launch_shade(s, r->shade_grid, r->scene_d.p, r->path_state(cur), r->path_state(cur ^ 1), r->hit.p, r->shadow_queue(), r->Lbuf.p, seg, (uint32_t)cur, ctr, b);
@@ -114,6 +116,9 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
     } else {
       launch_accumulate(s, r->acc, r->Lbuf.p, npix, S.width, ns, n0, r->params.nonfinite_policy, ctr);
     }
+    if (r->aov)
+      launch_accumulate_aov(s, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * (size_t)npix, r->Abuf.p, r->Lbuf.p, S.width, S.height, ns, n0,
+                            r->params.nonfinite_policy);
   }
   // BATCH_DEBUG still folds (to clear the per-wave statistics) but into a scratch Totals slot
   launch_fold_counters(s, ctr, mode == BATCH_DEBUG ? r->totals.p + 1 : r->totals.p, seg, count);
@@ -210,7 +215,7 @@ extern "C" int pt_get_runtime_info(pt_runtime_info* out) {
 int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out) {
   if (!info || !out) return fail(PT_ERR_INVALID_ARGUMENT, "pt_create: null argument");
   *out = nullptr;
-  if (info->abi_version != PT_ABI_VERSION) return fail(PT_ERR_INVALID_ARGUMENT, "pt_create: ABI version mismatch");
+  if (info->abi_version != PT_ABI_VERSION && info->abi_version != 4u) return fail(PT_ERR_INVALID_ARGUMENT, "pt_create: ABI version mismatch");
   {  // one HIP runtime over one HSA runtime per process, or whoever initialises second sees no GPU (runtime_identity.h)
     const std::string conflict = runtime_conflict();
     if (!conflict.empty()) return fail(PT_ERR_RUNTIME_CONFLICT, "pt_create: " + conflict);
@@ -223,6 +228,7 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   auto* r = new pt_renderer();
   pt_default_post_options(&r->post);
   pt_default_tonemap_options(&r->tonemap);
+  pt_default_denoise_options(&r->denoise);
   r->device = device_ordinal;
   if (const char* e = getenv("PTAMD_REFILL")) r->refill_threshold = (uint32_t)atoi(e);
   if (const char* e = getenv("PTAMD_TILES_PER_SEG")) r->tiles_per_seg_override = (uint32_t)std::max(0, atoi(e));  // tuning knobs
@@ -462,6 +468,8 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   // ---- wavefront buffers ----
   phase("shade / light records");
   const uint64_t npix = (uint64_t)p->width * p->height;
+  const bool aov = r->denoise.enabled != 0;
+  if (!aov) { r->Abuf.release(); r->aov_img.release(); }  // (an AOV-off render holds nothing more than before)
   // Queue segments (kernels.hip): one per 8x8 tile (a few tiles each once the image has more than 32640 of them), each with
   // room for its tiles under all samples in flight; queue_plan.h holds the sizing and every index-width limit.  The producers
   // (raygen, shade) are persistent grids whose waves take segments round-robin; the trace kernels claim chunks from a table,
@@ -470,6 +478,10 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
     else free_b += r->queue_bytes_held();  // what the previous render's queues occupy is reused, i.e. available
+    if (aov && free_b) {  // AOVs add 32 B per path slot to the ~200 B of queue state the automatic choice assumes
+      free_b += r->Abuf.bytes_held();
+      free_b = free_b / 232 * 200;
+    }
     pt_queue_plan plan{};
     const char* why = "";
     const int rc = plan_queues(p->width, p->height, p->spp, p->samples_in_flight, free_b, r->tiles_per_seg_override, r->seg_bands, &plan, &why);
@@ -516,6 +528,11 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
     PT_HIP(hipMemsetAsync(r->gmon_buckets_d.p, 0, sizeof(vec4) * npix * own, r->stream));
   }
   PT_HIP(hipMemsetAsync(r->acc, 0, sizeof(vec4) * npix, r->stream));
+  if (aov) {
+    PT_HIP(r->Abuf.alloc(2 * r->Lbuf.n));
+    PT_HIP(r->aov_img.alloc(3 * npix));
+    PT_HIP(hipMemsetAsync(r->aov_img.p, 0, sizeof(vec4) * 3 * npix, r->stream));
+  }
   PT_HIP(hipMemsetAsync(r->totals.p, 0, sizeof(Totals), r->stream));
   PT_HIP(hipStreamSynchronize(r->stream));
 
@@ -527,6 +544,7 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   r->last_batch_ns = 0;   // Lbuf holds nothing of THIS render yet
   r->batch_done_valid = false;
   r->total = p->spp;
+  r->aov = aov;
   r->started = true;
   r->render_start = std::chrono::steady_clock::now();
   r->timer_ms = 0;
@@ -712,6 +730,63 @@ int dev_set_tonemap_options(pt_renderer* r, const pt_tonemap_options* o) {
   return PT_OK;
 }
 
+extern "C" void pt_default_denoise_options(pt_denoise_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->iterations = 5;
+  o->sigma_luminance = 4.0f; o->sigma_normal = 128.0f; o->sigma_depth = 1.0f;
+}
+
+int dev_set_denoise_options(pt_renderer* r, const pt_denoise_options* o) {
+  if (!r || !o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (o->iterations > 8) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_denoise_options: iterations must be 0..8");
+  const float sg[3] = {o->sigma_luminance, o->sigma_normal, o->sigma_depth};
+  for (float v : sg)
+    if (!(v > 0.0f && v <= 3.4028234663852886e38f)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_denoise_options: every sigma must be finite and > 0");
+  r->denoise = *o;
+  return PT_OK;
+}
+
+// The filter over the current image into r->denoised, enqueued on the renderer's stream (denoise.hip).  Samples pending are enqueued first.
+int enqueue_denoise(pt_renderer* r) {
+  { const int rc = flush_pending(r, true); if (rc != PT_OK) return rc; }
+  const size_t npix = (size_t)r->S.width * r->S.height;
+  PT_HIP(r->denoised.alloc(npix));
+  if (r->denoise.iterations) {
+    PT_HIP(r->dn_guide.alloc(npix)); PT_HIP(r->dn_aux.alloc(npix));
+    PT_HIP(r->dn_col[0].alloc(npix)); PT_HIP(r->dn_col[1].alloc(npix));
+  }
+  DenoiseParams P;
+  P.W = r->S.width; P.H = r->S.height;
+  P.sigma_l = r->denoise.sigma_luminance; P.sigma_n = r->denoise.sigma_normal; P.sigma_z = r->denoise.sigma_depth;
+  launch_denoise(r->stream, r->acc, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * npix, P.W, P.H, (uint32_t)r->launched, P,
+                 r->denoise.iterations, r->dn_guide.p, r->dn_aux.p, r->dn_col[0].p, r->dn_col[1].p, r->denoised.p);
+  PT_HIP(hipGetLastError());
+  return PT_OK;
+}
+
+int dev_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out) {
+  if (!r || !rgba_out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (!r->started || !r->aov) return fail(PT_ERR_BAD_STATE, "pt_read_aov: the render was not started with AOVs enabled");
+  if (aov > PT_AOV_MOMENTS) return fail(PT_ERR_INVALID_ARGUMENT, "pt_read_aov: no such AOV");
+  int rc = dev_wait(r);
+  if (rc != PT_OK) return rc;
+  const size_t npix = (size_t)r->S.width * r->S.height;
+  PT_HIP(hipMemcpy(rgba_out, r->aov_img.p + aov * npix, sizeof(vec4) * npix, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+int dev_read_denoised(pt_renderer* r, float* rgba_out) {
+  if (!r || !rgba_out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (!r->started || !r->aov) return fail(PT_ERR_BAD_STATE, "pt_read_denoised: the render was not started with AOVs enabled");
+  int rc = dev_wait(r);
+  if (rc != PT_OK) return rc;
+  if ((rc = enqueue_denoise(r)) != PT_OK) return rc;
+  PT_HIP(hipStreamSynchronize(r->stream));
+  PT_HIP(hipMemcpy(rgba_out, r->denoised.p, sizeof(vec4) * (size_t)r->S.width * r->S.height, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
 int dev_postprocess_to_host(pt_renderer* r, const vec4* acc_device, uint8_t* rgba8_out) {
   PT_HIP(hipSetDevice(r->device));
   const size_t npix = (size_t)r->S.width * r->S.height;
@@ -741,7 +816,13 @@ int dev_present(pt_renderer* r, const vec4* acc_device, void** device_rgba8_out,
   pc.tm = r->tonemap;
   const Mat3 odt = compute_transform(r->params.working_space, r->tonemap.output_space);  // renderer_pt.cpp:190-191
   pc.odt = PPMat3{odt.c0, odt.c1, odt.c2};
-  launch_postprocess(r->stream, acc_device ? acc_device : r->acc, r->render_target.p, r->S.width, r->S.height, pc);
+  const vec4* src = acc_device ? acc_device : r->acc;
+  if (!acc_device && r->aov && r->denoise.apply_to_target) {  // the denoised image, enqueued on the same stream (no host round trip)
+    const int rc = enqueue_denoise(r);
+    if (rc != PT_OK) return rc;
+    src = r->denoised.p;
+  }
+  launch_postprocess(r->stream, src, r->render_target.p, r->S.width, r->S.height, pc);
   PT_HIP(hipGetLastError());
   *device_rgba8_out = r->render_target.p;
   if (stream_out) *stream_out = (void*)r->stream;
@@ -753,6 +834,10 @@ int dev_read_render_target(pt_renderer* r, uint8_t* rgba8_out) {
   if (!r->started) return fail(PT_ERR_BAD_STATE, "pt_read_render_target before pt_start_render");
   int rc = dev_wait(r);
   if (rc != PT_OK) return rc;
+  if (r->aov && r->denoise.apply_to_target) {
+    if ((rc = enqueue_denoise(r)) != PT_OK) return rc;
+    return dev_postprocess_to_host(r, r->denoised.p, rgba8_out);
+  }
   return dev_postprocess_to_host(r, r->acc, rgba8_out);
 }
 

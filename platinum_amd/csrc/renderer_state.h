@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "host_scene.h"
+#include "denoise.h"
 #include "kernels.h"
 #include "pt_bvh.h"
 
@@ -122,6 +123,12 @@ struct pt_renderer {
   pt_post_options post{};
   pt_tonemap_options tonemap{};
   DevBuf<uint32_t> render_target;  // RGBA8 (renderer_pt.cpp:832-835)
+  // first-hit AOVs + denoiser (denoise.hip): only a render started with denoise.enabled allocates or launches any of it
+  pt_denoise_options denoise{};
+  bool aov = false;                 // this render accumulates AOVs
+  DevBuf<vec4> Abuf;                // 2 vec4 per Lbuf entry: {albedo, t}, {normal, hit}
+  DevBuf<vec4> aov_img;             // [PT_AOV_*][pixel] running means
+  DevBuf<vec4> dn_guide, dn_aux, dn_col[2], denoised;  // the filter's per-pixel buffers and its output
   uint32_t closest_grid = 0, shadow_grid = 0, closest_blocks_per_cu = PT_CLOSEST_WAVES, shadow_blocks_per_cu = PT_SHADOW_WAVES;  // persistent trace grids, each sized for its kernel's occupancy
   uint32_t last_batch_ns = 0, last_batch_first = 0;  // the batch Lbuf holds ($PTAMD_DEBUG_PIXEL)
   uint32_t nseg = 0, tiles_per_seg = 1, seg_bands = 4, tiles_per_seg_override = 0, nstats = 0, seg_cap = 0, blocks_per_cu = 6, shade_grid = 0, refill_threshold = 48;
@@ -167,6 +174,7 @@ struct pt_renderer {
     bvh = LbvhResult{};
     acc = nullptr;
     started = false;
+    aov = false;
     last_batch_ns = 0;
   }
   // bytes of path-queue memory this renderer already holds (reused by the next render: they count as free when the batch is sized)
@@ -184,6 +192,7 @@ struct pt_renderer {
     for (int k = 0; k < 2; k++) { st_rayO[k].release(); st_rayD[k].release(); st_att[k].release(); }
     seg_active[0].release(); seg_active[1].release(); seg_shadow.release(); seg_poison.release(); wave_stats.release(); chunk_table[0].release(); chunk_table[1].release(); shade_order.release(); shade_cost.release(); gmon_buckets_d.release(); render_target.release();
     hit.release(); sq_o.release(); sq_d.release(); sq_c.release(); Lbuf.release(); acc_own.release(); spill.release();
+    Abuf.release(); aov_img.release(); dn_guide.release(); dn_aux.release(); dn_col[0].release(); dn_col[1].release(); denoised.release();
   }
   void drop_timed() {
     for (auto& t : timed) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
@@ -218,3 +227,6 @@ int dev_debug_sample(pt_renderer* r, uint32_t sample_idx, float* radiance_out, i
 int dev_measure_traversal(pt_renderer* r, uint32_t sample_idx);
 int dev_set_profiling(pt_renderer* r, int enabled);
 int dev_get_stats(pt_renderer* r, pt_stats* out);
+int dev_set_denoise_options(pt_renderer* r, const pt_denoise_options* o);
+int dev_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out);
+int dev_read_denoised(pt_renderer* r, float* rgba_out);

@@ -135,6 +135,39 @@ class Renderer:
         abi.check(self._lib, self._lib.pt_present_render_target(self._h, C.byref(ptr), C.byref(stream)))
         return ptr.value, stream.value
 
+    # first-hit AOVs + denoiser (include/ptamd.h, ABI 5): no reference counterpart
+    def denoiseOptions(self):
+        """The options in effect (pt_default_denoise_options until setDenoiseOptions is called)."""
+        if getattr(self, "_denoise", None) is None:
+            self._denoise = abi.DenoiseOptions()
+            self._lib.pt_default_denoise_options(C.byref(self._denoise))
+        o = abi.DenoiseOptions()
+        C.memmove(C.byref(o), C.byref(self._denoise), C.sizeof(o))
+        return o
+
+    def setDenoiseOptions(self, o=None, **fields):
+        """Sets `o` (default: the current options) with `fields` overriding it, e.g. setDenoiseOptions(enabled=1).
+        `enabled` takes effect at the next startRender, the filter fields at the next read or present."""
+        o = self.denoiseOptions() if o is None else o
+        for k, v in fields.items():
+            setattr(o, k, v)
+        abi.check(self._lib, self._lib.pt_set_denoise_options(self._h, C.byref(o)))
+        self._denoise = o
+
+    def readbackAov(self, kind):
+        """(H, W, 4) float32 running mean of AOV `kind` (abi.AOV_ALBEDO / AOV_NORMAL / AOV_MOMENTS)."""
+        w, h = self.size
+        out = np.empty((h, w, 4), dtype=np.float32)
+        abi.check(self._lib, self._lib.pt_read_aov(self._h, kind, out.ctypes.data))
+        return out
+
+    def readbackDenoised(self):
+        """(H, W, 4) float32: the accumulator through the a-trous denoiser with the current options."""
+        w, h = self.size
+        out = np.empty((h, w, 4), dtype=np.float32)
+        abi.check(self._lib, self._lib.pt_read_denoised(self._h, out.ctypes.data))
+        return out
+
     def setGmonOptions(self, cap=1.0):
         """gmonOptions().cap (renderer_pt.hpp:71)."""
         o = abi.GmonOptions(cap)

@@ -32,6 +32,7 @@ def main():
     ap.add_argument("--focal", type=float, default=28.0)
     ap.add_argument("--env", default="none", help="'sky' = procedural sky, or the path of an .exr / Radiance .hdr environment map")
     ap.add_argument("--exposure", type=float, default=0.0)
+    ap.add_argument("--denoise", action="store_true", help="keep first-hit AOVs and write the image through the a-trous denoiser")
     a = ap.parse_args()
     t0 = time.time()
     if a.scene.startswith("builtin:"):
@@ -48,6 +49,8 @@ def main():
         c = sc.counts()
         print(f"scene: {c.instances} instances, {c.triangles} triangles, {c.textures} textures, {c.materials} materials, cameras {sc.cameras()}")
     r = Renderer(device=0)
+    if a.denoise:
+        r.setDenoiseOptions(enabled=1, apply_to_target=1)
     flags = abi.FLAG_MULTISCATTER_GGX | (abi.FLAG_GMON if a.gmon > 1 else 0)
     r.startRender(sc, tuple(a.size), a.spp, gmonBuckets=max(1, a.gmon), flags=flags, max_bounces=a.bounces, nonfinite_policy=abi.NONFINITE_ZERO)
     t1 = time.time()
