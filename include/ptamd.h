@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 5u /* 4: pt_get_runtime_info, PT_ERR_RUNTIME_CONFLICT, pt_stats::leaf_slots; 5: AOVs + denoiser (pt_create accepts 4 and 5) */
+#define PT_ABI_VERSION 5u /* 4: pt_get_runtime_info, PT_ERR_RUNTIME_CONFLICT, pt_stats::leaf_slots; 5: AOVs + denoiser (pt_create accepts 4 and 5), then tile-adaptive sampling as an additive extension */
 
 /* ---------------------------------------------------------------------------------------------------------- */
 /* Enums (same numeric values as the reference)                                                                 */
@@ -407,6 +407,33 @@ int pt_set_denoise_options(pt_renderer* r, const pt_denoise_options* o);
 int pt_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out);
 /* The denoised image (W*H*4 floats, alpha 1).  Blocks.  PT_ERR_BAD_STATE for a render started without AOVs. */
 int pt_read_denoised(pt_renderer* r, float* rgba_out);
+
+/* ---- tile-adaptive sampling (NEW, an additive extension of ABI 5: new entry points and one new struct, no existing struct changed) ----
+ * A render started while `enabled` is set stops sampling an 8x8 tile of the accumulator once it has converged; pt_render_params.spp
+ * becomes the per-pixel maximum.  Checkpoints are at the sample counts c_k = min_spp + k * interval with c_k < spp.  At each, every
+ * still-active tile is tested with the luminance moments of its pixels after c_k samples (m1, m2: the running means of lum(L) and
+ * lum(L)^2 after the non-finite policy, the same bits as PT_AOV_MOMENTS .g / .b):
+ *     var = max(m2 - m1^2, 0) * n / (n - 1),   err = sqrt(var / n) / max(m1, 1e-3)
+ * The tile converges when err <= threshold for every one of its pixels inside the image (a NaN err keeps it active).  A converged tile
+ * receives no further samples: its accumulator and AOV pixels stay as they were at c_k.  Batches never straddle a checkpoint, so an
+ * adaptive render is the same bits for any samples_in_flight and any sequence of pt_render_step calls, and a tile that stopped after n
+ * samples equals a uniform render with spp = n on that tile.  A render with spp <= min_spp has no checkpoint.
+ * The render ends at spp, or once the host has observed that no tile is active: pt_progress then reports accumulated = total and
+ * pt_status Done.  pt_render_step never blocks to find out (the count arrives through pinned memory); pt_wait may synchronise at
+ * checkpoints.  pt_trace_primary, pt_debug_sample and pt_measure_traversal stay full-frame.
+ * Refused with PT_ERR_UNSUPPORTED: PT_FLAG_GMON together with enabled (at pt_start_render), and enabled = 1 on a device group. */
+typedef struct pt_adaptive_options {
+  uint32_t enabled;    /* read at pt_start_render; default 0 */
+  float threshold;     /* finite and > 0; default 0.02 */
+  uint32_t min_spp;    /* >= 2; default 32: the first checkpoint */
+  uint32_t interval;   /* >= 1; default 32: samples between checkpoints */
+} pt_adaptive_options;
+void pt_default_adaptive_options(pt_adaptive_options* o);
+/* PT_ERR_INVALID_ARGUMENT for threshold not finite or <= 0, min_spp < 2, interval < 1 */
+int pt_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o);
+/* The samples folded into each pixel (W*H values, its tile's count); on a non-adaptive render the uniform count.  Blocks like
+ * pt_read_accumulator. */
+int pt_read_sample_counts(pt_renderer* r, uint32_t* out);
 
 const char* pt_last_error(void);
 

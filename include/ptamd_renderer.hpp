@@ -31,6 +31,9 @@
  *   (no counterpart)                                             pt_denoise_options& denoiseOptions() / setDenoiseOptions(...), readbackAov(kind),
  *                                                                readbackDenoised(): first-hit AOVs and the a-trous denoiser (ptamd.h, ABI 5);
  *                                                                `enabled` is handed over at startRender, the rest whenever an image is asked for
+ *   (no counterpart)                                             pt_adaptive_options& adaptiveOptions() / setAdaptiveOptions(...),
+ *                                                                readbackSampleCounts(): tile-adaptive sampling (ptamd.h, ABI 5 extension);
+ *                                                                handed over at startRender
  * Error behaviour as the reference's: nothing throws; a failing call prints "renderer_pt: <message>" to stderr (the
  * reference prints and asserts, renderer_pt.cpp:402, 1044) and leaves the object in Status_Blocked; lastError() keeps the text.
  * Threading as the reference's: one caller thread per Renderer.
@@ -104,6 +107,7 @@ public:
     p.nonfinite_policy = m_nonfinitePolicy;
     p.accel_structure = m_accelStructure;
     if (!check(pt_set_denoise_options(m_pt, &m_denoise))) return;   // (`enabled` is read here)
+    if (!check(pt_set_adaptive_options(m_pt, &m_adaptive))) return;  // (read here)
     if (!check(pt_start_render(m_pt, &scene, &p))) return;
     m_size = uint2{p.width, p.height};
     m_started = true;
@@ -191,6 +195,17 @@ public:
     if (!check(pt_read_denoised(m_pt, out.data()))) out.clear();
     return out;
   }
+  // Tile-adaptive sampling (ptamd.h, an additive extension of ABI 5).  Edited in place like denoiseOptions(); read at startRender.
+  [[nodiscard]] constexpr pt_adaptive_options& adaptiveOptions() { return m_adaptive; }
+  void setAdaptiveOptions(const pt_adaptive_options& o) { m_adaptive = o; }
+  // The samples folded into each pixel, W*H (its 8x8 tile's count; uniform for a non-adaptive render).  Blocks.
+  [[nodiscard]] std::vector<uint32_t> readbackSampleCounts() const {
+    std::vector<uint32_t> out;
+    if (!m_pt || !m_started) return out;
+    out.resize((size_t)m_size.x * m_size.y);
+    if (!check(pt_read_sample_counts(m_pt, out.data()))) out.clear();
+    return out;
+  }
   void wait() const { if (m_pt && m_started) check(pt_wait(m_pt)); }
   [[nodiscard]] bool ok() const { return m_pt != nullptr && m_lastError.empty(); }
   [[nodiscard]] const std::string& lastError() const { return m_lastError; }
@@ -202,6 +217,7 @@ private:
     pt_default_tonemap_options(&defaults);
     m_outputSpace = defaults.output_space;   // Display P3 (renderer_pt.hpp:182)
     pt_default_denoise_options(&m_denoise);
+    pt_default_adaptive_options(&m_adaptive);
     std::vector<int32_t> ord(devices, devices + count);
     pt_create_info ci{};
     ci.abi_version = PT_ABI_VERSION;
@@ -242,6 +258,7 @@ private:
   pt_colorspace m_outputSpace{};
   pt_gmon_options m_gmonOptions{1.0f};
   pt_denoise_options m_denoise{};
+  pt_adaptive_options m_adaptive{};
   mutable void* m_presentStream = nullptr;
   mutable std::string m_lastError;
 };

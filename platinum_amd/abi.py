@@ -176,6 +176,10 @@ class DenoiseOptions(C.Structure):
 AOV_ALBEDO, AOV_NORMAL, AOV_MOMENTS = 0, 1, 2
 
 
+class AdaptiveOptions(C.Structure):
+    _fields_ = [("enabled", C.c_uint32), ("threshold", C.c_float), ("min_spp", C.c_uint32), ("interval", C.c_uint32)]
+
+
 class HitRecord(C.Structure):
     _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("instance", C.c_int32), ("primitive", C.c_int32)]
 
@@ -235,6 +239,9 @@ SYMBOLS = [
     ("pt_set_denoise_options", C.c_int, [C.c_void_p, C.POINTER(DenoiseOptions)]),
     ("pt_read_aov", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     ("pt_read_denoised", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("pt_default_adaptive_options", None, [C.POINTER(AdaptiveOptions)]),
+    ("pt_set_adaptive_options", C.c_int, [C.c_void_p, C.POINTER(AdaptiveOptions)]),
+    ("pt_read_sample_counts", C.c_int, [C.c_void_p, C.c_void_p]),
     ("pt_last_error", C.c_char_p, []),
     ("pt_get_constants", C.c_int, [C.c_void_p, C.POINTER(Constants)]),
     ("pt_get_lights", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),

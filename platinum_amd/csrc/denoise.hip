@@ -2,7 +2,8 @@
 //
 //   k_aov             after k_trace_closest(bounce 0), before k_shade(0): per camera ray, stage_aov -> Abuf[pid] (32 B)
 //   k_accumulate_aov  after k_accumulate / k_gmon: folds Abuf and Lbuf into the three AOV images, per pixel in sample order
-//   k_dn_prep         demodulation, variance, depth gradient
+//                     (k_accumulate_aov_adaptive: the same over the active tiles of an adaptive render)
+//   k_dn_prep         demodulation, variance, depth gradient (k_dn_prep_counts: with per-pixel sample counts, adaptive renders)
 //   k_atrous          one 5x5 step per launch (ping-pong); the last one remodulates
 // Only a render started with AOVs enabled launches any of them (renderer.hip enqueue_batch).
 //
@@ -81,16 +82,21 @@ __global__ void __launch_bounds__(256) k_aov(const DeviceScene* __restrict__ Sp,
 // Eight samples of the tile's 64 pixels are staged through LDS per round for each of the three streams (Lbuf and the two halves of
 // Abuf), fully coalesced; every lane then folds the eight samples of its pixel in sample order.  One wave per block: the three
 // staging areas take 27 KB.
-__global__ void __launch_bounds__(64) k_accumulate_aov(vec4* __restrict__ albedo, vec4* __restrict__ normal, vec4* __restrict__ moments,
-                                                        const vec4* __restrict__ Abuf, const vec4* __restrict__ Lbuf, uint32_t width,
-                                                        uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy) {
+// ADAPTIVE (k_accumulate_aov_adaptive, tile-adaptive sampling): block v folds virtual tile v < *active_count into image tile active[v]
+// (kernels.hip k_accumulate_adaptive); Abuf and Lbuf are dense over virtual tiles.
+template <bool ADAPTIVE>
+__device__ __forceinline__ void accumulate_aov_body(vec4* __restrict__ albedo, vec4* __restrict__ normal, vec4* __restrict__ moments,
+                                                    const vec4* __restrict__ Abuf, const vec4* __restrict__ Lbuf, uint32_t width,
+                                                    uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy,
+                                                    const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count) {
   constexpr uint32_t kRow = 9;
   __shared__ vec4 stage[3][64 * kRow];
   const uint32_t lane = dn_wave_lane();
-  const uint32_t tilesX = (width + 7u) / 8u, tiles = tilesX * ((height + 7u) / 8u);
+  const uint32_t tilesX = (width + 7u) / 8u, tiles = ADAPTIVE ? *active_count : tilesX * ((height + 7u) / 8u);
   const uint32_t tile = blockIdx.x;
   const bool live = tile < tiles;
-  const uint32_t ty = live ? tile / tilesX : 0u, x = (tile - ty * tilesX) * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
+  const uint32_t itile = ADAPTIVE ? (live ? active[tile] : 0u) : tile;   // the image tile
+  const uint32_t ty = live ? itile / tilesX : 0u, x = (itile - ty * tilesX) * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
   const bool inside = live && x < width && y < height;
   const size_t p = (size_t)y * width + x;
   vec4 A = inside ? albedo[p] : vec4{0, 0, 0, 0}, N = inside ? normal[p] : vec4{0, 0, 0, 0}, M = inside ? moments[p] : vec4{0, 0, 0, 0};
@@ -129,12 +135,33 @@ __global__ void __launch_bounds__(64) k_accumulate_aov(vec4* __restrict__ albedo
   if (inside) { albedo[p] = A; normal[p] = N; moments[p] = M; }
 }
 
+__global__ void __launch_bounds__(64) k_accumulate_aov(vec4* __restrict__ albedo, vec4* __restrict__ normal, vec4* __restrict__ moments,
+                                                        const vec4* __restrict__ Abuf, const vec4* __restrict__ Lbuf, uint32_t width,
+                                                        uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy) {
+  accumulate_aov_body<false>(albedo, normal, moments, Abuf, Lbuf, width, height, nsamples, n0, nonfinite_policy, nullptr, nullptr);
+}
+
+__global__ void __launch_bounds__(64) k_accumulate_aov_adaptive(vec4* __restrict__ albedo, vec4* __restrict__ normal, vec4* __restrict__ moments,
+                                                                 const vec4* __restrict__ Abuf, const vec4* __restrict__ Lbuf, uint32_t width,
+                                                                 uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy,
+                                                                 const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count) {
+  accumulate_aov_body<true>(albedo, normal, moments, Abuf, Lbuf, width, height, nsamples, n0, nonfinite_policy, active, active_count);
+}
+
 // ---- the filter: 16x16 pixel blocks -----------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_dn_prep(const vec4* __restrict__ acc, const vec4* __restrict__ albedo, const vec4* __restrict__ normal,
                                                  const vec4* __restrict__ moments, uint32_t W, uint32_t H, float N, vec4* __restrict__ guide,
                                                  vec4* __restrict__ col, vec4* __restrict__ aux) {
   const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
   if (x < W && y < H) dn_prep_pixel(acc, albedo, normal, moments, W, H, x, y, N, guide, col, aux);
+}
+
+// the prep of an adaptive render: N = the pixel's own sample count, its tile's (dn_prep_pixel_counts)
+__global__ void __launch_bounds__(256) k_dn_prep_counts(const vec4* __restrict__ acc, const vec4* __restrict__ albedo, const vec4* __restrict__ normal,
+                                                        const vec4* __restrict__ moments, uint32_t W, uint32_t H, const uint32_t* __restrict__ tile_n,
+                                                        vec4* __restrict__ guide, vec4* __restrict__ col, vec4* __restrict__ aux) {
+  const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
+  if (x < W && y < H) dn_prep_pixel_counts(acc, albedo, normal, moments, W, H, x, y, tile_n, guide, col, aux);
 }
 
 __global__ void __launch_bounds__(256) k_atrous(const vec4* __restrict__ guide, const vec4* __restrict__ aux, const vec4* __restrict__ col_in,
@@ -162,14 +189,24 @@ void launch_accumulate_aov(hipStream_t s, vec4* albedo, vec4* normal, vec4* mome
                      nonfinite_policy);
 }
 
+void launch_accumulate_aov_adaptive(hipStream_t s, vec4* albedo, vec4* normal, vec4* moments, const vec4* Abuf, const vec4* Lbuf, uint32_t width,
+                                    uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy, const uint32_t* active,
+                                    const uint32_t* active_count) {
+  const uint32_t tiles = ((width + 7u) / 8u) * ((height + 7u) / 8u);   // one block per tile that may still be active
+  hipLaunchKernelGGL(k_accumulate_aov_adaptive, dim3(tiles), dim3(64), 0, s, albedo, normal, moments, Abuf, Lbuf, width, height, nsamples, n0,
+                     nonfinite_policy, active, active_count);
+}
+
 void launch_denoise(hipStream_t s, const vec4* acc, const vec4* albedo, const vec4* normal, const vec4* moments, uint32_t W, uint32_t H,
-                    uint32_t nsamples, const DenoiseParams& P, uint32_t iterations, vec4* guide, vec4* aux, vec4* col0, vec4* col1, vec4* out) {
+                    uint32_t nsamples, const DenoiseParams& P, uint32_t iterations, vec4* guide, vec4* aux, vec4* col0, vec4* col1, vec4* out,
+                    const uint32_t* tile_n) {
   if (iterations == 0) {
     hipLaunchKernelGGL(k_dn_copy, dim3((W * H + 255u) / 256u), dim3(256), 0, s, acc, out, W * H);
     return;
   }
   const dim3 grid((W + 15u) / 16u, (H + 15u) / 16u), block(16, 16);
-  hipLaunchKernelGGL(k_dn_prep, grid, block, 0, s, acc, albedo, normal, moments, W, H, (float)nsamples, guide, col0, aux);
+  if (tile_n) hipLaunchKernelGGL(k_dn_prep_counts, grid, block, 0, s, acc, albedo, normal, moments, W, H, tile_n, guide, col0, aux);
+  else hipLaunchKernelGGL(k_dn_prep, grid, block, 0, s, acc, albedo, normal, moments, W, H, (float)nsamples, guide, col0, aux);
   vec4* cin = col0;
   vec4* cout = col1;
   for (uint32_t i = 0; i < iterations; i++) {

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "pt_denoise.h"
 #include "pt_post.h"
 #include "pt_shade.h"
 #include "queue_plan.h"
@@ -334,6 +335,56 @@ __global__ void __launch_bounds__(kBlock) k_raygen(DeviceScene S, PathState st, 
         const uint32_t j = seg_slot(seg.nseg, sg, n_out + wave_prefix(m));
         const uint32_t pid = lbuf_index(tile, s, nsamples, pl);
         const uint32_t rel = pid - first_tile * nsamples * 64u;  // relative to the segment's window (segment_lbuf_base)
+        st.rayO[j] = vec4{rg.o.x, rg.o.y, rg.o.z, 0.0f};
+        st.rayD[j] = vec4{rg.d.x, rg.d.y, rg.d.z, u2f((rg.dim & kMetaDimMask) | (rel << kMetaPidShift))};
+        st.att[j] = vec4{1.0f, 1.0f, 1.0f, u2f(rg.offset)};
+        Lbuf[pid] = vec4{0.0f, 0.0f, 0.0f, 1.0f};
+      }
+      n_out += (uint32_t)__popcll(m);
+    }
+    if (lane == 0) { seg.active[0][sg] = n_out; seg.poison[sg] = 0u; }
+    started += n_out;
+  }
+  if (lane == 0) {
+    WaveStats& ws = seg.stats[wave_index()];
+    ws.paths += started;
+    ws.closest += started;
+  }
+}
+
+// Tile-adaptive sampling: k_raygen over the VIRTUAL tiles 0 .. *active_count - 1, the still active tiles of the render; virtual tile v
+// is image tile active[v] (an ascending list).  Lbuf, the segments and the pids are dense over virtual tiles: only the pixel position
+// of a ray looks the list up, and segments past the active count emit nothing.  (A kernel of its own: k_raygen's code is left as it is.)
+__global__ void __launch_bounds__(kBlock) k_raygen_adaptive(DeviceScene S, PathState st, vec4* __restrict__ Lbuf, Segments seg,
+                                                             uint32_t first_sample, uint32_t nsamples, uint32_t tilesX,
+                                                             const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count) {
+  const uint32_t lane = wave_lane();
+  const uint32_t tiles = *active_count;   // virtual tiles
+  uint32_t started = 0;
+  for (uint32_t sg = wave_index(); sg < seg.nseg; sg += wave_count()) {
+    uint32_t n_out = 0;
+    const uint32_t first_tile = segment_first_tile(seg, sg);
+    for (uint32_t k = 0; k < seg.tiles_per_seg * nsamples; k++) {
+      const uint32_t tile = first_tile + k / nsamples;
+      if (tile >= tiles) break;  // wave-uniform
+#if PT_PIXEL_MAJOR
+      const uint32_t r = (k % nsamples) * 64u + lane;
+      const uint32_t pl = r / nsamples, s = r - pl * nsamples;
+#else
+      const uint32_t pl = lane, s = k % nsamples;
+#endif
+      const uint32_t itile = active[tile];   // the image tile
+      const uint32_t ty = itile / tilesX;
+      const uint32_t x = (itile - ty * tilesX) * 8 + (pl & 7);
+      const uint32_t y = ty * 8 + (pl >> 3);
+      const bool valid = x < S.width && y < S.height;
+      RayGenOut rg;
+      if (valid) rg = stage_raygen(S, x, y, first_sample + s);
+      const unsigned long long m = __ballot(valid);
+      if (valid) {
+        const uint32_t j = seg_slot(seg.nseg, sg, n_out + wave_prefix(m));
+        const uint32_t pid = lbuf_index(tile, s, nsamples, pl);
+        const uint32_t rel = pid - first_tile * nsamples * 64u;
         st.rayO[j] = vec4{rg.o.x, rg.o.y, rg.o.z, 0.0f};
         st.rayD[j] = vec4{rg.d.x, rg.d.y, rg.d.z, u2f((rg.dim & kMetaDimMask) | (rel << kMetaPidShift))};
         st.att[j] = vec4{1.0f, 1.0f, 1.0f, u2f(rg.offset)};
@@ -815,19 +866,25 @@ k_trace_shadow(DeviceScene S, ShadowQueue sq, vec4* __restrict__ Lbuf, Segments 
 // One wave per 8x8 tile.  A tile's entries of Lbuf are [pixel][sample]: eight samples of eight pixels are 8 x 128 contiguous bytes, so the
 // wave loads blocks of 64 pixels x 8 samples fully coalesced (eight lanes per 128-byte line), turns them through LDS, and every lane then
 // folds the eight samples of ITS pixel in sample order — the running mean is a sequential recurrence per pixel (kernel.metal:672-684).
-__global__ void __launch_bounds__(kBlock) k_accumulate(vec4* __restrict__ acc, const vec4* __restrict__ Lbuf,
-                                                        uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
-                                                        uint32_t nonfinite_policy, BatchCounters* __restrict__ ctr) {
+// ADAPTIVE (k_accumulate_adaptive): wave w folds virtual tile w < *active_count into image tile active[w], and also folds the running means
+// of (lum, lum^2) into `mom` with aov_fold / dn_lum (the bits of PT_AOV_MOMENTS .g / .b) and sets the tile's sample count.
+template <bool ADAPTIVE>
+__device__ __forceinline__ void accumulate_body(vec4* __restrict__ acc, const vec4* __restrict__ Lbuf, uint32_t npixels, uint32_t width,
+                                                uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy, BatchCounters* __restrict__ ctr,
+                                                const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count,
+                                                vec2* __restrict__ mom, uint32_t* __restrict__ tile_n) {
   constexpr uint32_t kRow = 9;  // vec4 per pixel row in LDS (8 samples + 1 of padding against bank conflicts)
   __shared__ vec4 stage[kBlock / 64][64 * kRow];
   const uint32_t lane = wave_lane(), w = threadIdx.x >> 6;
-  const uint32_t height = npixels / width, tilesX = (width + 7u) / 8u, tiles = tilesX * ((height + 7u) / 8u);
+  const uint32_t height = npixels / width, tilesX = (width + 7u) / 8u, tiles = ADAPTIVE ? *active_count : tilesX * ((height + 7u) / 8u);
   const uint32_t tile = blockIdx.x * (kBlock / 64) + w;   // (every wave of the block runs the same number of rounds: the barriers are uniform)
   const bool live = tile < tiles;
-  const uint32_t ty = live ? tile / tilesX : 0u, x = (tile - ty * tilesX) * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
+  const uint32_t itile = ADAPTIVE ? (live ? active[tile] : 0u) : tile;   // the image tile
+  const uint32_t ty = live ? itile / tilesX : 0u, x = (itile - ty * tilesX) * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
   const bool inside = live && x < width && y < height;
   const uint32_t p = y * width + x;
   vec4 a = inside ? acc[p] : vec4{0.0f, 0.0f, 0.0f, 0.0f};
+  vec2 m = ADAPTIVE && inside ? mom[p] : vec2{0.0f, 0.0f};
   for (uint32_t s0 = 0; s0 < nsamples; s0 += 8u) {
     const uint32_t nb = nsamples - s0 < 8u ? nsamples - s0 : 8u;
     __syncthreads();
@@ -848,6 +905,10 @@ __global__ void __launch_bounds__(kBlock) k_accumulate(vec4* __restrict__ acc, c
           if (nonfinite_policy == PT_NONFINITE_ZERO) L = v3(0.0f);
         }
         const uint32_t localFrameIdx = n0 + s0 + j;
+        if (ADAPTIVE) {
+          const float lum = dn_lum(L);
+          m = vec2{aov_fold(m.x, lum, localFrameIdx), aov_fold(m.y, lum * lum, localFrameIdx)};
+        }
         if (localFrameIdx > 0) {
           L = L + v3(a.x, a.y, a.z) * (float)localFrameIdx;
           L = L / (float)(localFrameIdx + 1);
@@ -857,6 +918,24 @@ __global__ void __launch_bounds__(kBlock) k_accumulate(vec4* __restrict__ acc, c
     }
   }
   if (inside) acc[p] = a;
+  if (ADAPTIVE) {
+    if (inside) mom[p] = m;
+    if (live && lane == 0) tile_n[itile] = n0 + nsamples;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_accumulate(vec4* __restrict__ acc, const vec4* __restrict__ Lbuf,
+                                                        uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
+                                                        uint32_t nonfinite_policy, BatchCounters* __restrict__ ctr) {
+  accumulate_body<false>(acc, Lbuf, npixels, width, nsamples, n0, nonfinite_policy, ctr, nullptr, nullptr, nullptr, nullptr);
+}
+
+__global__ void __launch_bounds__(kBlock) k_accumulate_adaptive(vec4* __restrict__ acc, const vec4* __restrict__ Lbuf,
+                                                                 uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
+                                                                 uint32_t nonfinite_policy, BatchCounters* __restrict__ ctr,
+                                                                 const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count,
+                                                                 vec2* __restrict__ mom, uint32_t* __restrict__ tile_n) {
+  accumulate_body<true>(acc, Lbuf, npixels, width, nsamples, n0, nonfinite_policy, ctr, active, active_count, mom, tile_n);
 }
 #else
 __global__ void __launch_bounds__(kBlock) k_accumulate(vec4* __restrict__ acc, const vec4* __restrict__ Lbuf,
@@ -1054,6 +1133,11 @@ void launch_raygen(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState
   const uint32_t tilesX = (S.width + 7) / 8, tilesY = (S.height + 7) / 8;
   hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, seg, ctr, first_sample, nsamples, tilesX, tilesY);
 }
+void launch_raygen_adaptive(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState st, vec4* Lbuf, Segments seg,
+                            uint32_t first_sample, uint32_t nsamples, const uint32_t* active, const uint32_t* active_count) {
+  const uint32_t tilesX = (S.width + 7) / 8;
+  hipLaunchKernelGGL(k_raygen_adaptive, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, seg, first_sample, nsamples, tilesX, active, active_count);
+}
 void launch_chunk_tables(hipStream_t s, Segments seg, uint32_t cur, BatchCounters* ctr, uint32_t bounce_closest,
                          uint32_t bounce_shadow, bool do_shadow) {
   hipLaunchKernelGGL(k_chunk_tables, dim3(kTableBlocks, 3), dim3(1024), 0, s, seg, cur, ctr, bounce_closest, bounce_shadow, do_shadow ? 1u : 0u);
@@ -1113,6 +1197,14 @@ void launch_accumulate(hipStream_t s, vec4* acc, const vec4* Lbuf, uint32_t npix
   hipLaunchKernelGGL(k_accumulate, dim3((npixels + kBlock - 1) / kBlock), dim3(kBlock), 0, s, acc, Lbuf, npixels, width, nsamples, n0,
                      nonfinite_policy, ctr);
 #endif
+}
+void launch_accumulate_adaptive(hipStream_t s, vec4* acc, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
+                                uint32_t nonfinite_policy, BatchCounters* ctr, const uint32_t* active, const uint32_t* active_count, vec2* mom,
+                                uint32_t* tile_n) {
+  static_assert(PT_PIXEL_MAJOR, "k_accumulate_adaptive stages the [pixel][sample] layout of a tile");
+  const uint32_t tiles = ((width + 7u) / 8u) * ((npixels / width + 7u) / 8u);   // one wave per tile that may still be active
+  hipLaunchKernelGGL(k_accumulate_adaptive, dim3((tiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, s, acc, Lbuf, npixels, width, nsamples,
+                     n0, nonfinite_policy, ctr, active, active_count, mom, tile_n);
 }
 void launch_accumulate_gmon(hipStream_t s, vec4* buckets, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
                             uint32_t samples_per_bucket, uint32_t gmon_buckets, uint32_t bucket_base, uint32_t nonfinite_policy, BatchCounters* ctr) {

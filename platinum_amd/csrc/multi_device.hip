@@ -722,6 +722,29 @@ int pt_read_denoised(pt_renderer* r, float* rgba_out) {
   return fail(PT_ERR_BAD_STATE, "pt_read_denoised: a device group does not keep AOVs");
 }
 
+// Adaptive sampling is per device: a group would have to agree on each tile's verdict across its members, which is not implemented
+int pt_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o) {
+  if (!is_group(r)) return dev_set_adaptive_options(r, o);
+  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (o->enabled) return fail(PT_ERR_UNSUPPORTED, "pt_set_adaptive_options: a device group does not sample adaptively");
+  for (auto* m : r->group->shards) { int rc = dev_set_adaptive_options(m, o); if (rc != PT_OK) return rc; }
+  return PT_OK;
+}
+
+// a group's render is uniform: every pixel holds the samples of all members
+int pt_read_sample_counts(pt_renderer* r, uint32_t* out) {
+  if (!is_group(r)) return dev_read_sample_counts(r, out);
+  if (!out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  DeviceGroup* grp = r->group;
+  if (!grp->started) return fail(PT_ERR_BAD_STATE, "pt_read_sample_counts before pt_start_render");
+  int rc = group_wait(r);
+  if (rc != PT_OK) return rc;
+  uint64_t n = 0;
+  for (auto* m : grp->shards) if (m->started) n += m->launched;
+  std::fill(out, out + (size_t)grp->params.width * grp->params.height, (uint32_t)n);
+  return PT_OK;
+}
+
 int pt_get_stats(pt_renderer* r, pt_stats* out) {
   if (!r || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
   return is_group(r) ? group_get_stats(r, out) : dev_get_stats(r, out);

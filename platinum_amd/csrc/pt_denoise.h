@@ -1,7 +1,7 @@
 // pt_denoise.h — first-hit AOVs and the edge-avoiding a-trous denoiser (DESIGN.md §3 "Denoiser").
 //
 //   stage_aov        : what one camera ray's first hit contributes to the AOV images (albedo, shading normal, distance)
-//   dn_prep_pixel    : demodulation, variance, depth gradient -> the filter's per-pixel inputs
+//   dn_prep_pixel    : demodulation, variance, depth gradient -> the filter's per-pixel inputs (dn_prep_pixel_counts: per-pixel N)
 //   dn_iterate_pixel : one 5x5 a-trous step (SVGF's spatial filter, Dammertz et al. 2010 / Schied et al. 2017, no temporal part)
 //
 // Written once, as plain C++ under PT_HD: denoise.hip runs it on the device, tests/emu/denoise_emu.cpp on the host, and the two
@@ -96,6 +96,14 @@ PT_HD void dn_prep_pixel(const vec4* acc, const vec4* albedo, const vec4* normal
   guide[p] = vec4{n.x, n.y, n.z, geo ? z : -1.0f};
   col[p] = valid ? vec4{I.x, I.y, I.z, v} : vec4{0.0f, 0.0f, 0.0f, -1.0f};
   aux[p] = vec4{am.x, am.y, am.z, gz};
+}
+
+// The prep of an adaptive render: N = the pixel's own sample count, that of its 8x8 tile (tile_n[(y / 8) * ceil(W / 8) + x / 8]);
+// otherwise dn_prep_pixel's arithmetic, unchanged.
+PT_HD void dn_prep_pixel_counts(const vec4* acc, const vec4* albedo, const vec4* normal, const vec4* moments, uint32_t W, uint32_t H,
+                                uint32_t x, uint32_t y, const uint32_t* tile_n, vec4* guide, vec4* col, vec4* aux) {
+  const float N = (float)tile_n[(y >> 3) * ((W + 7u) / 8u) + (x >> 3)];
+  dn_prep_pixel(acc, albedo, normal, moments, W, H, x, y, N, guide, col, aux);
 }
 
 // 3x3 binomial blur of v at (x, y) over the valid pixels of the centre's class, normalised by the weights used

@@ -10,6 +10,7 @@
 // No CPU path exists in this library: without a HIP device pt_create fails.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -75,9 +76,14 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
     }
   }
 #endif
+  // an adaptive render's batch covers the active tiles only: the three kernels that place a tile in the image read the current list
+  const bool ad = mode == BATCH_RENDER && r->adaptive;
+  const uint32_t* ad_list = ad ? r->ad_list[r->ad_cur].p : nullptr;
+  const uint32_t* ad_count = ad ? r->ad_count.p + r->ad_cur : nullptr;
   {
     ScopedTimer t(r, K_RAYGEN);
-    launch_raygen(s, r->grid, S, r->path_state(0), r->Lbuf.p, seg, ctr, first, ns);
+    if (ad) launch_raygen_adaptive(s, r->grid, S, r->path_state(0), r->Lbuf.p, seg, first, ns, ad_list, ad_count);
+    else launch_raygen(s, r->grid, S, r->path_state(0), r->Lbuf.p, seg, ctr, first, ns);
     launch_chunk_tables(s, seg, 0, ctr, 0, 0, false);
   }
   int cur = 0;
@@ -113,12 +119,31 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
       // the reference resolves after every frame with fullBuckets = gmonIdx + 1 (renderer_pt.cpp:164-179); only the last
       // resolve of a batch is observable
       launch_gmon(s, r->acc, r->gmon_buckets_d.p, npix, (f0 + ns - 1) / spb + 1 - r->gmon_bucket_base, r->gmon_cap);
+    } else if (ad) {
+      launch_accumulate_adaptive(s, r->acc, r->Lbuf.p, npix, S.width, ns, n0, r->params.nonfinite_policy, ctr, ad_list, ad_count, r->ad_mom.p,
+                                 r->ad_tile_n.p);
     } else {
       launch_accumulate(s, r->acc, r->Lbuf.p, npix, S.width, ns, n0, r->params.nonfinite_policy, ctr);
     }
-    if (r->aov)
+    if (r->aov && ad)
+      launch_accumulate_aov_adaptive(s, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * (size_t)npix, r->Abuf.p, r->Lbuf.p, S.width, S.height, ns,
+                                     n0, r->params.nonfinite_policy, ad_list, ad_count);
+    else if (r->aov)
       launch_accumulate_aov(s, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * (size_t)npix, r->Abuf.p, r->Lbuf.p, S.width, S.height, ns, n0,
                             r->params.nonfinite_policy);
+  }
+  // a batch that ends at a checkpoint (flush_pending never lets one straddle it): test the active tiles, compact the list into the other
+  // buffer, and send the new count to pinned host memory
+  if (ad && r->ad_next < r->total && n0 + ns == r->ad_next) {
+    {
+      ScopedTimer t(r, K_ACCUM);
+      PT_HIP(launch_adaptive_check(s, ad_list, ad_count, r->ad_list[r->ad_cur ^ 1].p, r->ad_count.p + (r->ad_cur ^ 1), r->ad_mom.p, S.width, S.height,
+                                   r->ad_next, r->adaptive_opts.threshold, r->ad_flags.p, r->ad_scratch.p, r->ad_scratch.n, r->ad_host_count));
+    }
+    PT_HIP(hipEventRecord(r->ad_event, s));
+    r->ad_event_valid = true;
+    r->ad_cur ^= 1;
+    r->ad_next += r->adaptive_opts.interval;
   }
   // BATCH_DEBUG still folds (to clear the per-wave statistics) but into a scratch Totals slot
   launch_fold_counters(s, ctr, mode == BATCH_DEBUG ? r->totals.p + 1 : r->totals.p, seg, count);
@@ -229,6 +254,7 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   pt_default_post_options(&r->post);
   pt_default_tonemap_options(&r->tonemap);
   pt_default_denoise_options(&r->denoise);
+  pt_default_adaptive_options(&r->adaptive_opts);
   r->device = device_ordinal;
   if (const char* e = getenv("PTAMD_REFILL")) r->refill_threshold = (uint32_t)atoi(e);
   if (const char* e = getenv("PTAMD_TILES_PER_SEG")) r->tiles_per_seg_override = (uint32_t)std::max(0, atoi(e));  // tuning knobs
@@ -277,6 +303,8 @@ void dev_destroy(pt_renderer* r) {
   r->drop_timed();
   r->release_all();  // the scene arrays, the queues AND the BVH builder's kept scratch (LbvhScratch has no destructor of its own)
   if (r->batch_done) (void)hipEventDestroy(r->batch_done);
+  if (r->ad_event) (void)hipEventDestroy(r->ad_event);
+  if (r->ad_host_count) (void)hipHostFree(r->ad_host_count);
   if (r->own_stream) (void)hipStreamDestroy(r->own_stream);
   delete r;
 }
@@ -294,6 +322,8 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
     return fail(PT_ERR_INVALID_ARGUMENT, "gmon_buckets must be 1..32 (gmon.metal:12 maxBuckets)");
   if (scene->instance_count && (!scene->instances || !scene->instance_materials || !scene->meshes))
     return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: null scene arrays");
+  if (r->adaptive_opts.enabled && (p->flags & PT_FLAG_GMON))
+    return fail(PT_ERR_UNSUPPORTED, "pt_start_render: adaptive sampling does not support PT_FLAG_GMON (a bucket would have to be resolved per tile count)");
   PT_HIP(hipSetDevice(r->device));
   if (r->stream) PT_HIP(hipStreamSynchronize(r->stream));
   r->drop_timed();
@@ -470,6 +500,8 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   const uint64_t npix = (uint64_t)p->width * p->height;
   const bool aov = r->denoise.enabled != 0;
   if (!aov) { r->Abuf.release(); r->aov_img.release(); }  // (an AOV-off render holds nothing more than before)
+  const bool adaptive = r->adaptive_opts.enabled != 0;
+  if (!adaptive) r->release_adaptive();                     // (nor does an adaptive-off render)
   // Queue segments (kernels.hip): one per 8x8 tile (a few tiles each once the image has more than 32640 of them), each with
   // room for its tiles under all samples in flight; queue_plan.h holds the sizing and every index-width limit.  The producers
   // (raygen, shade) are persistent grids whose waves take segments round-robin; the trace kernels claim chunks from a table,
@@ -533,6 +565,23 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
     PT_HIP(r->aov_img.alloc(3 * npix));
     PT_HIP(hipMemsetAsync(r->aov_img.p, 0, sizeof(vec4) * 3 * npix, r->stream));
   }
+  if (adaptive) {  // every tile starts active: list [0, tiles), count = tiles (adaptive.hip)
+    const uint32_t tiles = ((p->width + 7) / 8) * ((p->height + 7) / 8);
+    std::vector<uint32_t> iota(tiles);
+    for (uint32_t t = 0; t < tiles; t++) iota[t] = t;
+    PT_HIP(r->ad_list[0].upload(iota));
+    PT_HIP(r->ad_list[1].upload(iota));
+    PT_HIP(r->ad_count.upload(std::vector<uint32_t>{tiles, tiles}));
+    PT_HIP(r->ad_tile_n.alloc(tiles));
+    PT_HIP(hipMemsetAsync(r->ad_tile_n.p, 0, sizeof(uint32_t) * tiles, r->stream));
+    PT_HIP(r->ad_mom.alloc(npix));
+    PT_HIP(hipMemsetAsync(r->ad_mom.p, 0, sizeof(vec2) * npix, r->stream));
+    PT_HIP(r->ad_flags.alloc(tiles));
+    PT_HIP(r->ad_scratch.alloc(std::max<size_t>(1, adaptive_scratch_bytes(tiles))));
+    if (!r->ad_host_count) PT_HIP(hipHostMalloc((void**)&r->ad_host_count, sizeof(uint32_t), hipHostMallocDefault));
+    if (!r->ad_event) PT_HIP(hipEventCreateWithFlags(&r->ad_event, hipEventDisableTiming));
+    *r->ad_host_count = tiles;
+  }
   PT_HIP(hipMemsetAsync(r->totals.p, 0, sizeof(Totals), r->stream));
   PT_HIP(hipStreamSynchronize(r->stream));
 
@@ -545,9 +594,28 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   r->batch_done_valid = false;
   r->total = p->spp;
   r->aov = aov;
+  r->adaptive = adaptive;
+  r->ad_cur = 0;
+  r->ad_event_valid = false;
+  r->ad_next = r->adaptive_opts.min_spp;   // the first checkpoint (none when min_spp >= spp)
   r->started = true;
   r->render_start = std::chrono::steady_clock::now();
   r->timer_ms = 0;
+  return PT_OK;
+}
+
+// Tile-adaptive sampling: has the newest checkpoint enqueued completed with no tile left?  Never blocks: the count is read from pinned host
+// memory once the event behind its copy has completed.  Then the render is complete: what is accepted but not yet enqueued is dropped,
+// and pt_progress / pt_status report the whole render (batches already enqueued carry no tile).
+int adaptive_observe(pt_renderer* r) {
+  if (!r->ad_event_valid) return PT_OK;
+  const hipError_t q = hipEventQuery(r->ad_event);
+  if (q == hipErrorNotReady) { (void)hipGetLastError(); return PT_OK; }
+  if (q != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(PT_ERR_HIP, std::string("adaptive sampling: a checkpoint failed: ") + hipGetErrorString(q));
+  }
+  if (*(volatile uint32_t*)r->ad_host_count == 0) r->accumulated = r->launched = r->total;
   return PT_OK;
 }
 
@@ -558,7 +626,10 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
 // or until a full batch of `samples_in_flight` has gathered (enqueued behind the running one, so the GPU never idles).  A caller
 // slower than the GPU gets exactly the old behaviour (one batch per call); a tight render() loop converges to full batches.
 // The image does not depend on the batching: k_accumulate folds samples in index order.  `all`: enqueue everything now.
-int flush_pending(pt_renderer* r, bool all) {
+// An adaptive render also cuts a batch at the next checkpoint and stops once it has observed that no tile is active (adaptive_observe);
+// `sync_checkpoints` (pt_wait and the blocking reads) waits for each checkpoint it enqueues, so that no batch follows the last active tile.
+int flush_pending(pt_renderer* r, bool all, bool sync_checkpoints = false) {
+  if (r->adaptive) { const int rc = adaptive_observe(r); if (rc != PT_OK) return rc; }
   while (r->launched < r->accumulated) {
     const uint64_t pending = r->accumulated - r->launched;
     bool idle = true;
@@ -573,12 +644,19 @@ int flush_pending(pt_renderer* r, bool all) {
       }
     }
     if (!all && !idle && pending < r->samples_in_flight) break;
-    const uint32_t ns = (uint32_t)std::min<uint64_t>(pending, r->samples_in_flight);
+    uint32_t ns = (uint32_t)std::min<uint64_t>(pending, r->samples_in_flight);
+    const bool cut = r->adaptive && r->ad_next < r->total && r->launched + ns >= r->ad_next;   // batches never straddle a checkpoint
+    if (cut) ns = (uint32_t)(r->ad_next - r->launched);
     const int rc = enqueue_batch(r, r->params.first_sample + (uint32_t)r->launched, ns, (uint32_t)r->launched, BATCH_RENDER, nullptr);
     if (rc != PT_OK) return rc;
     r->launched += ns;
     r->batches++;
     if (r->batch_done && hipEventRecord(r->batch_done, r->stream) == hipSuccess) r->batch_done_valid = true;
+    if (cut && sync_checkpoints) {
+      PT_HIP(hipEventSynchronize(r->ad_event));
+      const int orc = adaptive_observe(r);
+      if (orc != PT_OK) return orc;
+    }
   }
   return PT_OK;
 }
@@ -598,8 +676,9 @@ int dev_render_step(pt_renderer* r, uint32_t max_spp) {
 int dev_wait(pt_renderer* r) {
   if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "null renderer");
   PT_HIP(hipSetDevice(r->device));
-  if (r->started) { const int rc = flush_pending(r, true); if (rc != PT_OK) return rc; }
+  if (r->started) { const int rc = flush_pending(r, true, true); if (rc != PT_OK) return rc; }
   PT_HIP(hipStreamSynchronize(r->stream));
+  if (r->started && r->adaptive) { const int rc = adaptive_observe(r); if (rc != PT_OK) return rc; }
   collect_timings(r);
   if (r->started && getenv("PTAMD_DUMP_CHUNKS")) {  // analysis aid: 64-ray chunks per bounce of the LAST batch (the counters are per batch)
     BatchCounters h{};
@@ -760,7 +839,8 @@ int enqueue_denoise(pt_renderer* r) {
   P.W = r->S.width; P.H = r->S.height;
   P.sigma_l = r->denoise.sigma_luminance; P.sigma_n = r->denoise.sigma_normal; P.sigma_z = r->denoise.sigma_depth;
   launch_denoise(r->stream, r->acc, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * npix, P.W, P.H, (uint32_t)r->launched, P,
-                 r->denoise.iterations, r->dn_guide.p, r->dn_aux.p, r->dn_col[0].p, r->dn_col[1].p, r->denoised.p);
+                 r->denoise.iterations, r->dn_guide.p, r->dn_aux.p, r->dn_col[0].p, r->dn_col[1].p, r->denoised.p,
+                 r->adaptive ? r->ad_tile_n.p : nullptr);   // an adaptive render: each pixel's own sample count
   PT_HIP(hipGetLastError());
   return PT_OK;
 }
@@ -784,6 +864,44 @@ int dev_read_denoised(pt_renderer* r, float* rgba_out) {
   if ((rc = enqueue_denoise(r)) != PT_OK) return rc;
   PT_HIP(hipStreamSynchronize(r->stream));
   PT_HIP(hipMemcpy(rgba_out, r->denoised.p, sizeof(vec4) * (size_t)r->S.width * r->S.height, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+extern "C" void pt_default_adaptive_options(pt_adaptive_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->threshold = 0.02f;
+  o->min_spp = 32;
+  o->interval = 32;
+}
+
+// (the options are checked before the renderer: a host without a device can exercise the validation)
+int dev_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o) {
+  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (!(o->threshold > 0.0f && o->threshold <= 3.4028234663852886e38f))
+    return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_adaptive_options: threshold must be finite and > 0");
+  if (o->min_spp < 2) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_adaptive_options: min_spp must be >= 2");
+  if (o->interval < 1) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_adaptive_options: interval must be >= 1");
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_adaptive_options: null renderer");
+  r->adaptive_opts = *o;
+  return PT_OK;
+}
+
+int dev_read_sample_counts(pt_renderer* r, uint32_t* out) {
+  if (!r || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (!r->started) return fail(PT_ERR_BAD_STATE, "pt_read_sample_counts before pt_start_render");
+  int rc = dev_wait(r);
+  if (rc != PT_OK) return rc;
+  const uint32_t W = r->S.width, H = r->S.height;
+  if (!r->adaptive) {
+    std::fill(out, out + (size_t)W * H, (uint32_t)r->launched);
+    return PT_OK;
+  }
+  const uint32_t tilesX = (W + 7) / 8;
+  std::vector<uint32_t> tn(r->ad_tile_n.n);
+  PT_HIP(hipMemcpy(tn.data(), r->ad_tile_n.p, sizeof(uint32_t) * tn.size(), hipMemcpyDeviceToHost));
+  for (uint32_t y = 0; y < H; y++)
+    for (uint32_t x = 0; x < W; x++) out[(size_t)y * W + x] = tn[(y >> 3) * tilesX + (x >> 3)];
   return PT_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "host_scene.h"
+#include "adaptive.h"
 #include "denoise.h"
 #include "kernels.h"
 #include "pt_bvh.h"
@@ -129,6 +130,19 @@ struct pt_renderer {
   DevBuf<vec4> Abuf;                // 2 vec4 per Lbuf entry: {albedo, t}, {normal, hit}
   DevBuf<vec4> aov_img;             // [PT_AOV_*][pixel] running means
   DevBuf<vec4> dn_guide, dn_aux, dn_col[2], denoised;  // the filter's per-pixel buffers and its output
+  // tile-adaptive sampling (adaptive.hip): only a render started with adaptive_opts.enabled allocates or launches any of it
+  pt_adaptive_options adaptive_opts{};
+  bool adaptive = false;            // this render samples adaptively
+  DevBuf<uint32_t> ad_list[2];      // the active tiles, ascending; [ad_cur] is the current list, the other one the next checkpoint's
+  DevBuf<uint32_t> ad_count;        // [2] the lists' lengths (device-side: batches read the current one)
+  DevBuf<uint32_t> ad_tile_n;       // [tile] samples folded into the tile's pixels
+  DevBuf<vec2> ad_mom;              // [pixel] running means of (lum, lum^2)
+  DevBuf<uint8_t> ad_flags, ad_scratch;  // the checkpoint's per-tile verdicts, the compaction's scratch
+  uint32_t* ad_host_count = nullptr;     // pinned: the active count after the newest checkpoint enqueued
+  hipEvent_t ad_event = nullptr;         // recorded behind the copy to ad_host_count
+  bool ad_event_valid = false;
+  int ad_cur = 0;
+  uint32_t ad_next = 0;                  // the next checkpoint's sample count (>= total: none left)
   uint32_t closest_grid = 0, shadow_grid = 0, closest_blocks_per_cu = PT_CLOSEST_WAVES, shadow_blocks_per_cu = PT_SHADOW_WAVES;  // persistent trace grids, each sized for its kernel's occupancy
   uint32_t last_batch_ns = 0, last_batch_first = 0;  // the batch Lbuf holds ($PTAMD_DEBUG_PIXEL)
   uint32_t nseg = 0, tiles_per_seg = 1, seg_bands = 4, tiles_per_seg_override = 0, nstats = 0, seg_cap = 0, blocks_per_cu = 6, shade_grid = 0, refill_threshold = 48;
@@ -175,6 +189,8 @@ struct pt_renderer {
     acc = nullptr;
     started = false;
     aov = false;
+    adaptive = false;
+    ad_event_valid = false;
     last_batch_ns = 0;
   }
   // bytes of path-queue memory this renderer already holds (reused by the next render: they count as free when the batch is sized)
@@ -193,6 +209,10 @@ struct pt_renderer {
     seg_active[0].release(); seg_active[1].release(); seg_shadow.release(); seg_poison.release(); wave_stats.release(); chunk_table[0].release(); chunk_table[1].release(); shade_order.release(); shade_cost.release(); gmon_buckets_d.release(); render_target.release();
     hit.release(); sq_o.release(); sq_d.release(); sq_c.release(); Lbuf.release(); acc_own.release(); spill.release();
     Abuf.release(); aov_img.release(); dn_guide.release(); dn_aux.release(); dn_col[0].release(); dn_col[1].release(); denoised.release();
+    release_adaptive();
+  }
+  void release_adaptive() {
+    ad_list[0].release(); ad_list[1].release(); ad_count.release(); ad_tile_n.release(); ad_mom.release(); ad_flags.release(); ad_scratch.release();
   }
   void drop_timed() {
     for (auto& t : timed) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
@@ -230,3 +250,5 @@ int dev_get_stats(pt_renderer* r, pt_stats* out);
 int dev_set_denoise_options(pt_renderer* r, const pt_denoise_options* o);
 int dev_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out);
 int dev_read_denoised(pt_renderer* r, float* rgba_out);
+int dev_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o);
+int dev_read_sample_counts(pt_renderer* r, uint32_t* out);

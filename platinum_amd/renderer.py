@@ -168,6 +168,32 @@ class Renderer:
         abi.check(self._lib, self._lib.pt_read_denoised(self._h, out.ctypes.data))
         return out
 
+    # tile-adaptive sampling (include/ptamd.h, an additive extension of ABI 5): no reference counterpart
+    def adaptiveOptions(self):
+        """The options in effect (pt_default_adaptive_options until setAdaptiveOptions is called)."""
+        if getattr(self, "_adaptive", None) is None:
+            self._adaptive = abi.AdaptiveOptions()
+            self._lib.pt_default_adaptive_options(C.byref(self._adaptive))
+        o = abi.AdaptiveOptions()
+        C.memmove(C.byref(o), C.byref(self._adaptive), C.sizeof(o))
+        return o
+
+    def setAdaptiveOptions(self, o=None, **fields):
+        """Sets `o` (default: the current options) with `fields` overriding it, e.g. setAdaptiveOptions(enabled=1, threshold=0.05).
+        The options take effect at the next startRender."""
+        o = self.adaptiveOptions() if o is None else o
+        for k, v in fields.items():
+            setattr(o, k, v)
+        abi.check(self._lib, self._lib.pt_set_adaptive_options(self._h, C.byref(o)))
+        self._adaptive = o
+
+    def readbackSampleCounts(self):
+        """(H, W) uint32: the samples folded into each pixel (its 8x8 tile's count; uniform for a non-adaptive render)."""
+        w, h = self.size
+        out = np.empty((h, w), dtype=np.uint32)
+        abi.check(self._lib, self._lib.pt_read_sample_counts(self._h, out.ctypes.data))
+        return out
+
     def setGmonOptions(self, cap=1.0):
         """gmonOptions().cap (renderer_pt.hpp:71)."""
         o = abi.GmonOptions(cap)

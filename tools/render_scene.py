@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--env", default="none", help="'sky' = procedural sky, or the path of an .exr / Radiance .hdr environment map")
     ap.add_argument("--exposure", type=float, default=0.0)
     ap.add_argument("--denoise", action="store_true", help="keep first-hit AOVs and write the image through the a-trous denoiser")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="THRESHOLD",
+                    help="tile-adaptive sampling: an 8x8 tile stops once every pixel's relative error is <= THRESHOLD (--spp is the maximum)")
     a = ap.parse_args()
     t0 = time.time()
     if a.scene.startswith("builtin:"):
@@ -51,6 +53,10 @@ def main():
     r = Renderer(device=0)
     if a.denoise:
         r.setDenoiseOptions(enabled=1, apply_to_target=1)
+    if a.adaptive is not None:
+        if a.gmon > 1:
+            ap.error("--adaptive does not combine with --gmon")
+        r.setAdaptiveOptions(enabled=1, threshold=a.adaptive)
     flags = abi.FLAG_MULTISCATTER_GGX | (abi.FLAG_GMON if a.gmon > 1 else 0)
     r.startRender(sc, tuple(a.size), a.spp, gmonBuckets=max(1, a.gmon), flags=flags, max_bounces=a.bounces, nonfinite_policy=abi.NONFINITE_ZERO)
     t1 = time.time()
@@ -62,6 +68,9 @@ def main():
     write_png_rgba8(a.output, img)
     st = r.stats()
     print(f"setup {t1 - t0:.2f} s (BVH {st.bvh_build_ms:.1f} ms), render {t2 - t1:.3f} s = {a.size[0] * a.size[1] * a.spp * a.bounces / (t2 - t1) / 1e6:.0f} Msamples/s, wrote {a.output}")
+    if a.adaptive is not None:
+        n = r.readbackSampleCounts()
+        print(f"adaptive: {st.paths} paths = {st.paths / (a.size[0] * a.size[1] * a.spp):.3f} of uniform, per-pixel samples {n.min()}..{n.max()}, mean {n.mean():.1f}")
 
 
 if __name__ == "__main__":
