@@ -1,7 +1,10 @@
 """Host side of the adaptive-sampling tests: the ctypes loader of tests/_build/libadaptive_emu.so (the host build of
 platinum_amd/csrc/pt_adaptive.h and of the denoiser's per-pixel-N prep, tests/emu/adaptive_emu.cpp) and a float64 numpy restatement of
-the criterion as DESIGN.md §3b states it.  TEST HARNESS, never imported by platinum_amd."""
+the criterion as DESIGN.md §3b states it; reference_render, a whole adaptive render on the host (denoise_lib.HostScene + the host
+criterion), and the configurations tests/test_adaptive_reference.py and tests/test_gpu_adaptive_matrix.py share.  TEST HARNESS, never
+imported by platinum_amd."""
 import ctypes as C
+import functools
 import os
 import subprocess
 import sys
@@ -90,3 +93,108 @@ def np_converged(m1, m2, n, threshold):
 def tile_view(img, H, W):
     """(tilesY, tilesX) list of the tiles' slices of an (H, W, ...) image."""
     return [[(slice(ty * 8, min(H, ty * 8 + 8)), slice(tx * 8, min(W, tx * 8 + 8))) for tx in range((W + 7) // 8)] for ty in range((H + 7) // 8)]
+
+
+# ---- a whole adaptive render on the host (DESIGN.md §3b), no GPU in the loop ------------------------------------------------------------
+def checkpoints(spp, min_spp, interval):
+    """The sample counts at which a render of `spp` samples takes a verdict: min_spp, min_spp + interval, ... below spp."""
+    return list(range(min_spp, spp, interval))
+
+
+def reference_render(scene, params, threshold, min_spp, interval, stop_at=None, trace=None):
+    """The adaptive render of `scene` under `params` (spp, first_sample, integrator, ... as the device gets them) on the host build of the
+    product's stage functions (denoise_lib.HostScene): samples are folded cumulatively, the host build of the criterion (host_tiles)
+    judges the moments at every checkpoint below spp, and a tile's accumulator, AOVs and count freeze at the first checkpoint where it
+    converges.  Returns (counts (H, W) uint32, acc, albedo, normal, moments).  `stop_at` = n: the state after n samples (active tiles
+    hold n).  `trace`, a list, receives (checkpoint, moments at it, tiles active before it) per checkpoint."""
+    import denoise_lib as dl
+    hs = dl.HostScene(scene, params)
+    H, W = hs.H, hs.W
+    spp, first = int(params.spp), int(params.first_sample)
+    end = spp if stop_at is None else min(int(stop_at), spp)
+    live = [np.zeros((H, W, 4), np.float32) for _ in range(4)]
+    out = [np.zeros((H, W, 4), np.float32) for _ in range(4)]
+    counts = np.zeros((H, W), np.uint32)
+    active = np.ones(((H + 7) // 8, (W + 7) // 8), bool)
+    tv = tile_view(counts, H, W)
+
+    def freeze(tiles, n):
+        for ty, tx in zip(*np.nonzero(tiles)):
+            s = tv[ty][tx]
+            counts[s] = n
+            for o, l in zip(out, live):
+                o[s] = l[s]
+
+    done = 0
+    cps = checkpoints(spp, min_spp, interval)
+    for c in sorted(set([c for c in cps if c <= end] + [end])):
+        if c > done:
+            hs.render(first + done, c - done, n0=done, into=live)
+            done = c
+        if c in cps and active.any():
+            if trace is not None:
+                trace.append((c, live[3].copy(), active.copy()))
+            conv = host_tiles(live[3], c, threshold) & active
+            freeze(conv, c)
+            active &= ~conv
+    freeze(active, end)
+    return (counts,) + tuple(out)
+
+
+def tile_counts(counts):
+    return counts[::8, ::8]
+
+
+def check_populated(counts, spp, W, H):
+    """The preconditions of a comparison with a reference: every class of tile takes part (else it could pass vacuously)."""
+    tc = tile_counts(counts)
+    assert np.array_equal(np.kron(tc, np.ones((8, 8), np.uint32))[:H, :W], counts)
+    distinct = sorted(set(tc.ravel().tolist()))
+    assert len(distinct) >= 5 and distinct[-1] == spp, distinct
+    early = float((tc < spp).mean())
+    assert 0.15 <= early <= 0.85, early
+    assert W % 8 and H % 8
+    edge = np.zeros(tc.shape, bool)
+    edge[-1, :] = edge[:, -1] = True     # the partial tiles
+    assert (tc[edge] < spp).any() and (tc[edge] == spp).any()
+    # (stopped early in the last tile row) + (in the last tile column): the corner tile counts in both
+    return distinct, early, int((tc[-1, :] < spp).sum() + (tc[:, -1] < spp).sum())
+
+
+def histogram(counts):
+    tc = tile_counts(counts)
+    return ", ".join("%d: %d" % (n, int((tc == n).sum())) for n in sorted(set(tc.ravel().tolist()))) + " (of %d)" % tc.size
+
+
+# ---- the configurations the reference tests and the GPU matrix share -------------------------------------------------------------------
+# scene, (W, H), bounces, spp, min_spp, interval, threshold: every count class is populated and partial edge tiles stop early and late
+CONFIGS = {
+    "cornell131": ("cornell", (131, 93), 4, 128, 16, 16, 0.2),
+    "cornell67": ("cornell", (67, 45), 4, 96, 5, 7, 0.3),
+    "textured99": ("textured", (99, 53), 6, 64, 8, 8, 0.5),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def config_scene(kind):
+    from platinum_amd import scenes
+    return scenes.cornell_scene("bench") if kind == "cornell" else scenes.textured_scene()
+
+
+def config_params(name, first_sample=0, integrator=None):
+    from platinum_amd import abi
+    from platinum_amd.renderer import make_params
+    _kind, (W, H), B, spp, _m, _i, _t = CONFIGS[name]
+    return make_params(W, H, spp, B, first_sample=first_sample, integrator=abi.INTEGRATOR_MIS if integrator is None else integrator)
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, min_spp=None, interval=None, first_sample=0, integrator=None, stop_at=None):
+    """reference_render of CONFIGS[name], once per process: a dict of counts / acc / albedo / normal / moments / trace (read only)."""
+    kind, _size, _B, _spp, m, i, thr = CONFIGS[name]
+    m, i = (m, i) if min_spp is None else (min_spp, interval)
+    trace = []
+    out = reference_render(config_scene(kind), config_params(name, first_sample, integrator), thr, m, i, stop_at=stop_at, trace=trace)
+    for a in out:
+        a.flags.writeable = False
+    return dict(zip(("counts", "acc", "albedo", "normal", "moments"), out), trace=trace)

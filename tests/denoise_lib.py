@@ -93,10 +93,13 @@ class HostScene:
         self.L.dn_host_stage_aov(self.h, sample, hits.ctypes.data, a.ctypes.data, n.ctypes.data)
         return a, n
 
-    def render(self, first, ns):
-        """Samples [first, first + ns): (accumulator, albedo, normal, moments) as the device folds them."""
-        imgs = [np.zeros((self.H, self.W, 4), np.float32) for _ in range(4)]
-        self.L.dn_host_render(self.h, first, ns, 0, *[i.ctypes.data for i in imgs])
+    def render(self, first, ns, n0=0, into=None):
+        """Samples [first, first + ns): (accumulator, albedo, normal, moments) as the device folds them.  `into` = four (H, W, 4) float32
+        images that already hold the running means of `n0` samples: the new samples are folded into them in place."""
+        imgs = [np.zeros((self.H, self.W, 4), np.float32) for _ in range(4)] if into is None else list(into)
+        for i in imgs:
+            assert i.dtype == np.float32 and i.shape == (self.H, self.W, 4) and i.flags.c_contiguous
+        self.L.dn_host_render(self.h, first, ns, n0, *[i.ctypes.data for i in imgs])
         return imgs
 
 

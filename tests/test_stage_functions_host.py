@@ -81,16 +81,20 @@ def test_no_answer_depends_on_the_last_bit_of_the_rays_reciprocal_direction(name
     sc = {"field3": lambda: scenes.field_scene(3), "textured": scenes.textured_scene}.get(name) or (lambda: scenes.random_scene(int(name[6:])))
     sc = sc()
     p = make_params(64, 36, 2, 6)
-    o, e = oracle_lib.OracleScene(sc, p), emu_lib.EmuScene(sc, p)
-    monkeypatch.delenv("EMU_RCP_ULP")
-    assert o.trace_primary(1).tobytes() == e.trace_primary(1).tobytes()
-    for s_ in (0, 1):
-        ro, ho = o.debug_sample(s_)
-        re_, he = e.debug_sample(s_)
-        nan = np.isnan(ro)
-        assert np.array_equal(ho, he) and np.array_equal(nan, np.isnan(re_))
-        assert np.array_equal(ro.view(np.uint32)[~nan], re_.view(np.uint32)[~nan])
-    emu_lib.EmuScene(sc, p)   # (the switch is process-wide in the harness: the next scene created without the variable turns it off again)
+    try:
+        o, e = oracle_lib.OracleScene(sc, p), emu_lib.EmuScene(sc, p)
+        monkeypatch.delenv("EMU_RCP_ULP")
+        assert o.trace_primary(1).tobytes() == e.trace_primary(1).tobytes()
+        for s_ in (0, 1):
+            ro, ho = o.debug_sample(s_)
+            re_, he = e.debug_sample(s_)
+            nan = np.isnan(ro)
+            assert np.array_equal(ho, he) and np.array_equal(nan, np.isnan(re_))
+            assert np.array_equal(ro.view(np.uint32)[~nan], re_.view(np.uint32)[~nan])
+    finally:
+        # the switch is process-wide in the harness: the next scene created without the variable turns it off again, whatever failed above
+        monkeypatch.delenv("EMU_RCP_ULP", raising=False)
+        emu_lib.EmuScene(sc, p)
 
 
 @pytest.mark.parametrize("pairs", [False, True])
