@@ -39,7 +39,8 @@ def lib():
     L.dn_host_filter.argtypes = [C.c_void_p] * 4 + [C.c_uint32] * 4 + [C.c_float] * 3 + [C.c_void_p]
     L.dn_host_stage_aov.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dn_host_lum.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    L.dn_host_render.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+    L.dn_host_render.restype = C.c_uint64
+    L.dn_host_render.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5
     L.dn_host_options_layout.argtypes = [C.POINTER(C.c_uint32 * 7)]
     _lib = L
     return L
@@ -79,6 +80,7 @@ class HostScene:
         if not self.h:
             raise RuntimeError("emu_create failed")
         self.W, self.H = params.width, params.height
+        self.nonfinite = 0      # non-finite samples met by render() so far (under either params.nonfinite_policy)
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -93,13 +95,18 @@ class HostScene:
         self.L.dn_host_stage_aov(self.h, sample, hits.ctypes.data, a.ctypes.data, n.ctypes.data)
         return a, n
 
-    def render(self, first, ns, n0=0, into=None):
-        """Samples [first, first + ns): (accumulator, albedo, normal, moments) as the device folds them.  `into` = four (H, W, 4) float32
-        images that already hold the running means of `n0` samples: the new samples are folded into them in place."""
+    def render(self, first, ns, n0=0, into=None, nonfinite=None):
+        """Samples [first, first + ns): (accumulator, albedo, normal, moments) as the device folds them, under the nonfinite_policy of the
+        params the scene was created with.  `into` = four (H, W, 4) float32 images that already hold the running means of `n0` samples: the
+        new samples are folded into them in place.  `nonfinite` = an (H, W) uint32 image, incremented where a sample was NaN / inf;
+        self.nonfinite grows by their number."""
         imgs = [np.zeros((self.H, self.W, 4), np.float32) for _ in range(4)] if into is None else list(into)
         for i in imgs:
             assert i.dtype == np.float32 and i.shape == (self.H, self.W, 4) and i.flags.c_contiguous
-        self.L.dn_host_render(self.h, first, ns, n0, *[i.ctypes.data for i in imgs])
+        if nonfinite is not None:
+            assert nonfinite.dtype == np.uint32 and nonfinite.shape == (self.H, self.W) and nonfinite.flags.c_contiguous
+        self.nonfinite += self.L.dn_host_render(self.h, first, ns, n0, *[i.ctypes.data for i in imgs],
+                                                None if nonfinite is None else nonfinite.ctypes.data)
         return imgs
 
 

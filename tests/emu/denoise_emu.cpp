@@ -74,14 +74,20 @@ void dn_host_lum(const float* rgba, size_t n, float* lum, float* lum2) {
 }
 
 // Samples [first, first + ns) of every pixel: the accumulator and the three AOV images, folded as k_accumulate / k_accumulate_aov do
-// (n0 samples already in them).  Single-threaded; for small images.
-void dn_host_render(void* h, uint32_t first, uint32_t ns, uint32_t n0, float* acc, float* albedo, float* normal, float* moments) {
+// (n0 samples already in them).  A sample that is not finite (the kernels' own test) is counted, and under PT_NONFINITE_ZERO (the policy of
+// the render params the scene was created with) replaced by black before the accumulator's fold (kernels.hip accumulate_body) and before
+// dn_lum (denoise.hip accumulate_aov_body).  Returns the number of such samples; `nonfinite_px` (W*H, may be null) is incremented at their
+// pixels.  Single-threaded; for small images.
+uint64_t dn_host_render(void* h, uint32_t first, uint32_t ns, uint32_t n0, float* acc, float* albedo, float* normal, float* moments,
+                        uint32_t* nonfinite_px) {
   Emu* e = (Emu*)h;
   const DeviceScene& S = e->S;
   const uint32_t W = S.width, H = S.height;
   std::vector<pt_hit_record> hits((size_t)W * H);
   std::vector<float> ab((size_t)W * H * 4), nb((size_t)W * H * 4);
   std::vector<uint32_t> lds(std::max(kLdsStack, kLdsStack6) + 1), spill(kSpillStack), pend(std::max(kPendLeaves, kPendLeaves6) + 1);
+  const bool zero = e->params.nonfinite_policy == PT_NONFINITE_ZERO;
+  uint64_t nonfinite = 0;
   for (uint32_t s = 0; s < ns; s++) {
     emu_trace_primary(h, first + s, hits.data());
     dn_host_stage_aov(h, first + s, hits.data(), ab.data(), nb.data());
@@ -89,7 +95,12 @@ void dn_host_render(void* h, uint32_t first, uint32_t ns, uint32_t n0, float* ac
     for (uint32_t y = 0; y < H; y++)
       for (uint32_t x = 0; x < W; x++) {
         const size_t p = (size_t)y * W + x;
-        const vec3 L = emu_path(e, x, y, first + s, lds.data(), spill.data(), pend.data());
+        vec3 L = emu_path(e, x, y, first + s, lds.data(), spill.data(), pend.data());
+        if (!(fabsf(L.x) <= 3.0e38f && fabsf(L.y) <= 3.0e38f && fabsf(L.z) <= 3.0e38f)) {  // NaN or inf
+          nonfinite++;
+          if (nonfinite_px) nonfinite_px[p]++;
+          if (zero) L = v3(0.0f);
+        }
         float* c = acc + 4 * p;
         const vec3 cm = aov_fold(v3(c[0], c[1], c[2]), L, n);
         c[0] = cm.x; c[1] = cm.y; c[2] = cm.z; c[3] = 1.0f;
@@ -105,6 +116,7 @@ void dn_host_render(void* h, uint32_t first, uint32_t ns, uint32_t n0, float* ac
         M[0] = m.x; M[1] = m.y; M[2] = m.z; M[3] = 0.0f;
       }
   }
+  return nonfinite;
 }
 
 // sizeof / offsetof of pt_denoise_options as this compiler lays it out, and the library's defaults as the header states them
