@@ -12,6 +12,7 @@
 
 #include "adaptive.h"
 #include "pt_adaptive.h"
+#include "pt_layout.h"
 
 namespace pt {
 
@@ -26,8 +27,8 @@ __global__ void __launch_bounds__(256) k_adaptive_check(const uint32_t* __restri
     if (lane == 0) flags[v] = 0;
     return;
   }
-  const uint32_t tile = list_in[v], tilesX = (W + 7u) / 8u;
-  const uint32_t ty = tile / tilesX, x = (tile - ty * tilesX) * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
+  const PixelXY q = tile_pixel(list_in[v], lane, tiles_x(W));
+  const uint32_t x = q.x, y = q.y;
   bool converged = true;   // pixels outside the image take no part
   if (x < W && y < H) {
     const vec2 m = mom[(size_t)y * W + x];
@@ -47,7 +48,7 @@ size_t adaptive_scratch_bytes(uint32_t tiles) {
 hipError_t launch_adaptive_check(hipStream_t s, const uint32_t* list_in, const uint32_t* count_in, uint32_t* list_out, uint32_t* count_out,
                                  const vec2* mom, uint32_t W, uint32_t H, uint32_t n, float threshold, uint8_t* flags, void* scratch,
                                  size_t scratch_bytes, uint32_t* host_count) {
-  const uint32_t tiles = ((W + 7u) / 8u) * ((H + 7u) / 8u);
+  const uint32_t tiles = tile_count(W, H);
   hipLaunchKernelGGL(k_adaptive_check, dim3((tiles + 3u) / 4u), dim3(256), 0, s, list_in, count_in, mom, W, H, tiles, n, threshold, flags);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

@@ -12,47 +12,21 @@
 
 #include "denoise.h"
 #include "pt_denoise.h"
-#include "queue_plan.h"
 
 namespace pt {
-
-// ---- queue / radiance-buffer indexing: the same functions as kernels.hip (seg_slot, segment_lbuf_base, lbuf_index) --------------
-#ifndef PT_SEG_GROUP
-#define PT_SEG_GROUP 16
-#endif
-#ifndef PT_PIXEL_MAJOR
-#define PT_PIXEL_MAJOR 1
-#endif
-static_assert(PT_SEG_GROUP == kSegGroupChunks, "queue_plan.h sizes the queue arrays for this interleaving");
-__device__ __forceinline__ uint32_t dn_wave_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ uint32_t dn_seg_slot(uint32_t nseg, uint32_t s, uint32_t r) {
-  const uint32_t k = r >> 6;
-  return (((k / PT_SEG_GROUP) * nseg + s) * PT_SEG_GROUP + (k % PT_SEG_GROUP)) * 64u + (r & 63u);
-}
-__device__ __forceinline__ uint32_t dn_segment_lbuf_base(const Segments& seg, uint32_t sg) {
-  const uint32_t per_band = seg.nseg / seg.bands;
-  return ((sg % seg.bands) * per_band + sg / seg.bands) * seg.tiles_per_seg * seg.nsamples * 64u;
-}
-__device__ __forceinline__ uint32_t dn_lbuf_index(uint32_t tile, uint32_t s, uint32_t nsamples, uint32_t lane) {
-#if PT_PIXEL_MAJOR
-  return (tile * 64u + lane) * nsamples + s;
-#else
-  return (tile * nsamples + s) * 64u + lane;
-#endif
-}
 
 // ---- k_aov: the bounce-0 queue (state buffer 0) -> Abuf.  Reads the queue only. ----------------------------------------------------
 // Abuf[2 * pid] = {albedo, t}, Abuf[2 * pid + 1] = {normal, 1} for a hit; {1, 1, 1, 0}, {0, 0, 0, 0} for a miss.
 __global__ void __launch_bounds__(256) k_aov(const DeviceScene* __restrict__ Sp, PathState st, const vec4* __restrict__ hit, Segments seg,
                                              vec4* __restrict__ Abuf) {
   const DeviceScene& S = *Sp;
-  const uint32_t lane = dn_wave_lane();
+  const uint32_t lane = wave_lane();
   const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = gridDim.x * (blockDim.x >> 6);
   for (uint32_t sg = wave; sg < seg.nseg; sg += nwaves) {
     const uint32_t n = seg.active[0][sg];
-    const uint32_t base = dn_segment_lbuf_base(seg, sg);
+    const uint32_t base = segment_lbuf_base(seg, sg);
     for (uint32_t k = lane; k < n; k += 64) {
-      const uint32_t i = dn_seg_slot(seg.nseg, sg, k);
+      const uint32_t i = seg_slot(seg.nseg, sg, k);
       const vec4 h4 = hit[i], d4 = st.rayD[i];
       const uint32_t pid = base + (f2u(d4.w) >> kMetaPidShift);
       AovSample a = aov_miss();
@@ -91,14 +65,14 @@ __device__ __forceinline__ void accumulate_aov_body(vec4* __restrict__ albedo, v
                                                     const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count) {
   constexpr uint32_t kRow = 9;
   __shared__ vec4 stage[3][64 * kRow];
-  const uint32_t lane = dn_wave_lane();
-  const uint32_t tilesX = (width + 7u) / 8u, tiles = ADAPTIVE ? *active_count : tilesX * ((height + 7u) / 8u);
+  const uint32_t lane = wave_lane();
+  const uint32_t tilesX = tiles_x(width), tiles = ADAPTIVE ? *active_count : tilesX * tiles_y(height);
   const uint32_t tile = blockIdx.x;
   const bool live = tile < tiles;
   const uint32_t itile = ADAPTIVE ? (live ? active[tile] : 0u) : tile;   // the image tile
-  const uint32_t ty = live ? itile / tilesX : 0u, x = (itile - ty * tilesX) * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
-  const bool inside = live && x < width && y < height;
-  const size_t p = (size_t)y * width + x;
+  const PixelXY q = tile_pixel(itile, lane, tilesX);
+  const bool inside = live && q.x < width && q.y < height;
+  const size_t p = (size_t)q.y * width + q.x;
   vec4 A = inside ? albedo[p] : vec4{0, 0, 0, 0}, N = inside ? normal[p] : vec4{0, 0, 0, 0}, M = inside ? moments[p] : vec4{0, 0, 0, 0};
   for (uint32_t s0 = 0; s0 < nsamples; s0 += 8u) {
     const uint32_t nb = nsamples - s0 < 8u ? nsamples - s0 : 8u;
@@ -106,9 +80,9 @@ __device__ __forceinline__ void accumulate_aov_body(vec4* __restrict__ albedo, v
     if (live) {
 #pragma unroll
       for (uint32_t i = 0; i < 8u; i++) {
-        const uint32_t px = i * 8u + (lane >> 3), j = lane & 7u;
+        const uint32_t px = i * 8u + (lane >> 3), j = lane & 7u;   // (the staging order, as k_accumulate)
         if (j < nb) {
-          const uint32_t pid = dn_lbuf_index(tile, s0 + j, nsamples, px);
+          const uint32_t pid = lbuf_index(tile, s0 + j, nsamples, px);
           stage[0][px * kRow + j] = Lbuf[pid];
           stage[1][px * kRow + j] = Abuf[2u * pid];
           stage[2][px * kRow + j] = Abuf[2u * pid + 1u];
@@ -183,8 +157,7 @@ void launch_aov(hipStream_t s, uint32_t grid, const DeviceScene* S_device, PathS
 
 void launch_accumulate_aov(hipStream_t s, vec4* albedo, vec4* normal, vec4* moments, const vec4* Abuf, const vec4* Lbuf, uint32_t width,
                            uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy) {
-  static_assert(PT_PIXEL_MAJOR, "k_accumulate_aov stages the [pixel][sample] layout of a tile");
-  const uint32_t tiles = ((width + 7u) / 8u) * ((height + 7u) / 8u);
+  const uint32_t tiles = tile_count(width, height);
   hipLaunchKernelGGL(k_accumulate_aov, dim3(tiles), dim3(64), 0, s, albedo, normal, moments, Abuf, Lbuf, width, height, nsamples, n0,
                      nonfinite_policy);
 }
@@ -192,7 +165,7 @@ void launch_accumulate_aov(hipStream_t s, vec4* albedo, vec4* normal, vec4* mome
 void launch_accumulate_aov_adaptive(hipStream_t s, vec4* albedo, vec4* normal, vec4* moments, const vec4* Abuf, const vec4* Lbuf, uint32_t width,
                                     uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy, const uint32_t* active,
                                     const uint32_t* active_count) {
-  const uint32_t tiles = ((width + 7u) / 8u) * ((height + 7u) / 8u);   // one block per tile that may still be active
+  const uint32_t tiles = tile_count(width, height);   // one block per tile that may still be active
   hipLaunchKernelGGL(k_accumulate_aov_adaptive, dim3(tiles), dim3(64), 0, s, albedo, normal, moments, Abuf, Lbuf, width, height, nsamples, n0,
                      nonfinite_policy, active, active_count);
 }

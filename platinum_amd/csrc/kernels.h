@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pt_device.h"
+#include "pt_layout.h"
 #include "pt_post.h"
 
 namespace pt {
@@ -11,8 +12,8 @@ constexpr int kBlock = 256;  // 4 waves; traversal kernels keep a 16 KiB LDS sta
 
 struct WaveStats { unsigned long long closest, shadow, shaded, paths; };  // per physical wave, owner-updated, reduced by k_fold_counters
 
-// Queue segments (kernels.hip): segment s = the queue share of tiles [s * tiles_per_seg, (s + 1) * tiles_per_seg) under all
-// samples of a batch; it owns `seg_cap` slots of every queue array (interleaved in groups of 16 chunks) and one count per queue.
+// Queue segments (kernels.hip): segment s = the queue share of `tiles_per_seg` consecutive tiles (pt_layout.h segment_first_tile) under
+// all samples of a batch; it owns `seg_cap` slots of every queue array (pt_layout.h seg_slot) and one count per queue.
 struct Segments {
   uint32_t* active[2];  // [state buffer][segment] live paths in the segment
   uint32_t* shadow;     // [segment] shadow rays in the segment
@@ -30,6 +31,10 @@ struct Segments {
   uint32_t nstats;      // WaveStats slots (>= waves of the largest producer grid)
   uint32_t refill_threshold; // trace kernels: refill a wave's idle lanes when fewer than this many still hold a ray (0 = only when all idle)
 };
+PT_HD uint32_t segment_first_tile(const Segments& seg, uint32_t sg) { return segment_first_tile(seg.nseg, seg.bands, seg.tiles_per_seg, sg); }
+PT_HD uint32_t segment_lbuf_base(const Segments& seg, uint32_t sg) { return segment_lbuf_base(seg.nseg, seg.bands, seg.tiles_per_seg, seg.nsamples, sg); }
+// lane of the wave (wave64)
+__device__ __forceinline__ uint32_t wave_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 void launch_raygen(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState st, vec4* Lbuf, Segments seg, BatchCounters* ctr,
                    uint32_t first_sample, uint32_t nsamples);
@@ -40,9 +45,6 @@ void launch_raygen_adaptive(hipStream_t s, uint32_t grid, const DeviceScene& S, 
 // `bounce_closest`) and, if do_shadow, of the shadow queue consumed at `bounce_shadow`.
 void launch_chunk_tables(hipStream_t s, Segments seg, uint32_t cur, BatchCounters* ctr, uint32_t bounce_closest,
                          uint32_t bounce_shadow, bool do_shadow);
-uint32_t seg_group_chunks();
-size_t lbuf_index_host(uint32_t tile, uint32_t s, uint32_t nsamples, uint32_t lane);   // kernels.hip lbuf_index, for the host (debug read-back)
-size_t lbuf_sample_stride_host();
 uint32_t trace_block_threads(bool two_level);
 uint32_t trace_blocks_per_cu_two_level();  // 256 (7 blocks per CU) for one BVH, 1024 (one block per CU) for the two-level structure
 void launch_trace_closest(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState st, vec4* hit, Segments seg, uint32_t cur,

@@ -6,7 +6,7 @@
 //
 // Queues are SEGMENTS.  A segment is the queue share of a few 8x8 pixel tiles (Segments::tiles_per_seg, 1 unless the image
 // has more than 32768 tiles) under all samples of the batch: segment s owns the slots {seg_slot(s, r) : r < seg_cap} of
-// every queue array (interleaved in groups of 16 chunks, see seg_slot) and one count per queue.  A segment is always processed by ONE wave
+// every queue array (interleaved in groups of 16 chunks, pt_layout.h seg_slot) and one count per queue.  A segment is always processed by ONE wave
 // at a time, front to back: k_raygen fills it, k_shade shades it and compacts the survivors (ballot + mbcnt prefix) into
 // the same segment of the other state buffer and its NEE rays into the same segment of the shadow queue.  Survivors <=
 // inputs, so a segment never overflows and NO atomic sits on the producer side.  (Round-1 measurement: with one global
@@ -50,8 +50,7 @@ __device__ __forceinline__ void st_stream(vec4* p, vec4 v) {
 }
 __device__ __forceinline__ void st_stream(uint32_t* p, uint32_t v) { __builtin_nontemporal_store(v, p); }
 
-// ---- wave helpers (wave64) -------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t wave_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+// ---- wave helpers (wave64; wave_lane is in kernels.h) --------------------------------------------------------------
 __device__ __forceinline__ uint32_t wave_prefix(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
@@ -62,20 +61,6 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 // physical wave id / count of the launch (blockDim.x is a multiple of 64)
 __device__ __forceinline__ uint32_t wave_index() { return blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); }
 __device__ __forceinline__ uint32_t wave_count() { return gridDim.x * (blockDim.x >> 6); }
-// Slot of entry r of segment s.  Segments are interleaved in GROUPS of PT_SEG_GROUP 64-entry chunks: chunks 16g .. 16g + 15 of a
-// segment are contiguous (16 KB per array), group g of neighbouring segments follows — a segment's entries are a few long runs
-// (the class-binned passes of k_shade gather from them; +1 % over single-chunk interleaving), while concurrently processed
-// segments still start in different memory channels (a plain segment-major layout cost the closest-hit kernel 1.4x in round 1).
-#ifndef PT_SEG_GROUP
-#define PT_SEG_GROUP 16
-#endif
-__device__ __forceinline__ uint32_t seg_slot(uint32_t nseg, uint32_t s, uint32_t r) {
-  const uint32_t k = r >> 6;
-  return (((k / PT_SEG_GROUP) * nseg + s) * PT_SEG_GROUP + (k % PT_SEG_GROUP)) * 64u + (r & 63u);
-}
-uint32_t seg_group_chunks() { return PT_SEG_GROUP; }
-static_assert(PT_SEG_GROUP == kSegGroupChunks, "queue_plan.h sizes the queue arrays for this interleaving");
-
 #ifdef PT_TAIL_PROBE
 #define PT_TAIL_BEGIN const unsigned long long tail_t0 = wall_clock64(); unsigned long long tail_take = 0, tail_setup = 0, tail_ta = 0;
 #define PT_TAIL_T(acc) { const unsigned long long tb_ = wall_clock64(); acc += tb_ - tail_ta; tail_ta = tb_; }
@@ -256,53 +241,10 @@ __global__ void __launch_bounds__(1024) k_chunk_tables(Segments seg, uint32_t cu
   }
 }
 
-// ---- the per-sample radiance buffer Lbuf -----------------------------------------------------------------------------
-// One vec4 per (pixel, sample in flight), laid out TILE-major: the entries of one 8x8 tile under all samples are contiguous (128 KB at 128
-// samples in flight) and a segment's rays all belong to its tile(s): the shadow kernel's read-modify-writes of a segment stay inside that
-// window (a [sample][pixel] layout spread them over planes 33 MB apart: every access its own line).  `pid` in the path state IS this index.
-// Inside a tile the order is [pixel][sample] (r4, PT_PIXEL_MAJOR; r1-r3 had [sample][pixel]): the camera rays of a chunk are 64 SAMPLES OF
-// ONE PIXEL (k_raygen), so a chunk's 64 entries are 1 KB contiguous here too, and k_accumulate folds a pixel's samples from consecutive words.
-#ifndef PT_PIXEL_MAJOR
-#define PT_PIXEL_MAJOR 1
-#endif
-__device__ __forceinline__ uint32_t lbuf_index(uint32_t tile, uint32_t s, uint32_t nsamples, uint32_t lane) {
-#if PT_PIXEL_MAJOR
-  return (tile * 64u + lane) * nsamples + s;
-#else
-  return (tile * nsamples + s) * 64u + lane;
-#endif
-}
-constexpr uint32_t kLbufSampleStride = PT_PIXEL_MAJOR ? 1u : 64u;  // distance between successive samples of one pixel
-// (host mirrors for the debug build's $PTAMD_DEBUG_PIXEL read-back: the layout this translation unit was compiled with)
-size_t lbuf_index_host(uint32_t tile, uint32_t s, uint32_t nsamples, uint32_t lane) {
-  return PT_PIXEL_MAJOR ? ((size_t)tile * 64u + lane) * nsamples + s : ((size_t)tile * nsamples + s) * 64u + lane;
-}
-size_t lbuf_sample_stride_host() { return kLbufSampleStride; }
-__device__ __forceinline__ uint32_t lbuf_index_of_pixel(uint32_t p, uint32_t W, uint32_t s, uint32_t nsamples) {
-  const uint32_t y = p / W, x = p - y * W, tilesX = (W + 7u) / 8u;
-  return lbuf_index((y >> 3) * tilesX + (x >> 3), s, nsamples, (y & 7u) * 8u + (x & 7u));
-}
-// A segment's window of Lbuf starts at its first tile; a path's entry is that base + the relative index it carries in rayD.w.
-__device__ __forceinline__ uint32_t segment_first_tile(const Segments& seg, uint32_t sg) {
-  // consecutive segments cycle over `bands` horizontal bands of the image (the chunk tables list the segments in order, so the
-  // rays in flight in a trace kernel come from `bands` neighbourhoods instead of one)
-  const uint32_t per_band = seg.nseg / seg.bands;  // nseg is a multiple of bands
-  return ((sg % seg.bands) * per_band + sg / seg.bands) * seg.tiles_per_seg;
-}
-__device__ __forceinline__ uint32_t segment_lbuf_base(const Segments& seg, uint32_t sg) { return segment_first_tile(seg, sg) * seg.nsamples * 64u; }
-// the segment a queue slot belongs to (inverse of seg_slot)
-__device__ __forceinline__ uint32_t slot_segment(uint32_t nseg, uint32_t slot) { return ((slot >> 6) / PT_SEG_GROUP) % nseg; }
-// the pixel (row-major) of a pid of a ONE-sample batch (the debug entry points: pt_trace_primary, pt_debug_sample)
-__device__ __forceinline__ uint32_t pixel_of_pid_1spp(uint32_t pid, uint32_t W) {
-  const uint32_t lane = pid & 63u, tile = pid >> 6, tilesX = (W + 7u) / 8u;
-  const uint32_t ty = tile / tilesX, tx = tile - ty * tilesX;
-  return (ty * 8u + (lane >> 3)) * W + tx * 8u + (lane & 7u);
-}
-
 // ---- raygen ------------------------------------------------------------------------------------------------------
 // Segment s = T consecutive tiles under all samples of the batch.  One wave iteration emits 64 camera rays; lanes outside the image (partial
-// edge tiles) are squeezed out.  r4 (PT_PIXEL_MAJOR): the 64 rays of an iteration are consecutive SAMPLES OF ONE PIXEL (pixel-major,
-// sample-minor through the tile) where r1-r3 emitted one sample of the tile's 64 pixels.  The samples of a pixel differ by a sub-pixel
+// edge tiles) are squeezed out.  r4: the 64 rays of an iteration are consecutive SAMPLES OF ONE PIXEL (pixel-major, sample-minor through
+// the tile) where r1-r3 emitted one sample of the tile's 64 pixels.  The samples of a pixel differ by a sub-pixel
 // jitter, so the lanes of a bounce-0 chunk walk the same nodes and test the same triangles: their loads fall on the same addresses (one
 // L1 look-up instead of 64), they finish together, and their hits shade one triangle of one material.  Nothing else knows the order of a
 // segment's entries: a path finds its radiance entry through `pid`, which is computed here from (tile, pixel, sample).
@@ -318,18 +260,12 @@ __global__ void __launch_bounds__(kBlock) k_raygen(DeviceScene S, PathState st, 
     for (uint32_t k = 0; k < seg.tiles_per_seg * nsamples; k++) {
       const uint32_t tile = first_tile + k / nsamples;
       if (tile >= tiles) break;  // wave-uniform
-#if PT_PIXEL_MAJOR
       const uint32_t r = (k % nsamples) * 64u + lane;   // ray r of the tile's 64 * nsamples, pixel-major
       const uint32_t pl = r / nsamples, s = r - pl * nsamples;
-#else
-      const uint32_t pl = lane, s = k % nsamples;
-#endif
-      const uint32_t ty = tile / tilesX;
-      const uint32_t x = (tile - ty * tilesX) * 8 + (pl & 7);
-      const uint32_t y = ty * 8 + (pl >> 3);
-      const bool valid = x < S.width && y < S.height;
+      const PixelXY q = tile_pixel(tile, pl, tilesX);
+      const bool valid = q.x < S.width && q.y < S.height;
       RayGenOut rg;
-      if (valid) rg = stage_raygen(S, x, y, first_sample + s);
+      if (valid) rg = stage_raygen(S, q.x, q.y, first_sample + s);
       const unsigned long long m = __ballot(valid);
       if (valid) {
         const uint32_t j = seg_slot(seg.nseg, sg, n_out + wave_prefix(m));
@@ -354,7 +290,8 @@ __global__ void __launch_bounds__(kBlock) k_raygen(DeviceScene S, PathState st, 
 
 // Tile-adaptive sampling: k_raygen over the VIRTUAL tiles 0 .. *active_count - 1, the still active tiles of the render; virtual tile v
 // is image tile active[v] (an ascending list).  Lbuf, the segments and the pids are dense over virtual tiles: only the pixel position
-// of a ray looks the list up, and segments past the active count emit nothing.  (A kernel of its own: k_raygen's code is left as it is.)
+// of a ray looks the list up, and segments past the active count emit nothing.  (A kernel of its own: as one template with k_raygen,
+// the merged k_raygen missed the speed margin set for it: profiles/HISTORY.md §10.)
 __global__ void __launch_bounds__(kBlock) k_raygen_adaptive(DeviceScene S, PathState st, vec4* __restrict__ Lbuf, Segments seg,
                                                              uint32_t first_sample, uint32_t nsamples, uint32_t tilesX,
                                                              const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count) {
@@ -367,19 +304,12 @@ __global__ void __launch_bounds__(kBlock) k_raygen_adaptive(DeviceScene S, PathS
     for (uint32_t k = 0; k < seg.tiles_per_seg * nsamples; k++) {
       const uint32_t tile = first_tile + k / nsamples;
       if (tile >= tiles) break;  // wave-uniform
-#if PT_PIXEL_MAJOR
       const uint32_t r = (k % nsamples) * 64u + lane;
       const uint32_t pl = r / nsamples, s = r - pl * nsamples;
-#else
-      const uint32_t pl = lane, s = k % nsamples;
-#endif
-      const uint32_t itile = active[tile];   // the image tile
-      const uint32_t ty = itile / tilesX;
-      const uint32_t x = (itile - ty * tilesX) * 8 + (pl & 7);
-      const uint32_t y = ty * 8 + (pl >> 3);
-      const bool valid = x < S.width && y < S.height;
+      const PixelXY q = tile_pixel(active[tile], pl, tilesX);   // of the image tile
+      const bool valid = q.x < S.width && q.y < S.height;
       RayGenOut rg;
-      if (valid) rg = stage_raygen(S, x, y, first_sample + s);
+      if (valid) rg = stage_raygen(S, q.x, q.y, first_sample + s);
       const unsigned long long m = __ballot(valid);
       if (valid) {
         const uint32_t j = seg_slot(seg.nseg, sg, n_out + wave_prefix(m));
@@ -862,7 +792,6 @@ k_trace_shadow(DeviceScene S, ShadowQueue sq, vec4* __restrict__ Lbuf, Segments 
 }
 
 // ---- accumulate (kernel.metal:672-684): running mean, one sample at a time, in sample order --------------------------
-#if PT_PIXEL_MAJOR
 // One wave per 8x8 tile.  A tile's entries of Lbuf are [pixel][sample]: eight samples of eight pixels are 8 x 128 contiguous bytes, so the
 // wave loads blocks of 64 pixels x 8 samples fully coalesced (eight lanes per 128-byte line), turns them through LDS, and every lane then
 // folds the eight samples of ITS pixel in sample order — the running mean is a sequential recurrence per pixel (kernel.metal:672-684).
@@ -876,13 +805,13 @@ __device__ __forceinline__ void accumulate_body(vec4* __restrict__ acc, const ve
   constexpr uint32_t kRow = 9;  // vec4 per pixel row in LDS (8 samples + 1 of padding against bank conflicts)
   __shared__ vec4 stage[kBlock / 64][64 * kRow];
   const uint32_t lane = wave_lane(), w = threadIdx.x >> 6;
-  const uint32_t height = npixels / width, tilesX = (width + 7u) / 8u, tiles = ADAPTIVE ? *active_count : tilesX * ((height + 7u) / 8u);
+  const uint32_t height = npixels / width, tilesX = tiles_x(width), tiles = ADAPTIVE ? *active_count : tilesX * tiles_y(height);
   const uint32_t tile = blockIdx.x * (kBlock / 64) + w;   // (every wave of the block runs the same number of rounds: the barriers are uniform)
   const bool live = tile < tiles;
   const uint32_t itile = ADAPTIVE ? (live ? active[tile] : 0u) : tile;   // the image tile
-  const uint32_t ty = live ? itile / tilesX : 0u, x = (itile - ty * tilesX) * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
-  const bool inside = live && x < width && y < height;
-  const uint32_t p = y * width + x;
+  const PixelXY q = tile_pixel(itile, lane, tilesX);
+  const bool inside = live && q.x < width && q.y < height;
+  const uint32_t p = q.y * width + q.x;
   vec4 a = inside ? acc[p] : vec4{0.0f, 0.0f, 0.0f, 0.0f};
   vec2 m = ADAPTIVE && inside ? mom[p] : vec2{0.0f, 0.0f};
   for (uint32_t s0 = 0; s0 < nsamples; s0 += 8u) {
@@ -891,8 +820,8 @@ __device__ __forceinline__ void accumulate_body(vec4* __restrict__ acc, const ve
     if (live) {
 #pragma unroll
       for (uint32_t i = 0; i < 8u; i++) {
-        const uint32_t px = i * 8u + (lane >> 3), j = lane & 7u;
-        if (j < nb) stage[w][px * kRow + j] = ld_stream(&Lbuf[(tile * 64u + px) * nsamples + s0 + j]);
+        const uint32_t px = i * 8u + (lane >> 3), j = lane & 7u;   // (the staging order: eight lanes per pixel, one per sample)
+        if (j < nb) stage[w][px * kRow + j] = ld_stream(&Lbuf[lbuf_index(tile, s0 + j, nsamples, px)]);
       }
     }
     __syncthreads();
@@ -937,31 +866,6 @@ __global__ void __launch_bounds__(kBlock) k_accumulate_adaptive(vec4* __restrict
                                                                  vec2* __restrict__ mom, uint32_t* __restrict__ tile_n) {
   accumulate_body<true>(acc, Lbuf, npixels, width, nsamples, n0, nonfinite_policy, ctr, active, active_count, mom, tile_n);
 }
-#else
-__global__ void __launch_bounds__(kBlock) k_accumulate(vec4* __restrict__ acc, const vec4* __restrict__ Lbuf,
-                                                        uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
-                                                        uint32_t nonfinite_policy, BatchCounters* __restrict__ ctr) {
-  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
-  if (p >= npixels) return;
-  vec4 a = acc[p];
-  const uint32_t l0 = lbuf_index_of_pixel(p, width, 0, nsamples);
-  for (uint32_t s = 0; s < nsamples; s++) {
-    const vec4 L4 = Lbuf[l0 + s * kLbufSampleStride];
-    vec3 L = v3(L4.x, L4.y, L4.z);
-    if (!(fabsf(L.x) <= 3.0e38f && fabsf(L.y) <= 3.0e38f && fabsf(L.z) <= 3.0e38f)) {  // NaN or inf
-      atomicAdd(&ctr->nonfinite, 1u);
-      if (nonfinite_policy == PT_NONFINITE_ZERO) L = v3(0.0f);
-    }
-    const uint32_t localFrameIdx = n0 + s;
-    if (localFrameIdx > 0) {
-      L = L + v3(a.x, a.y, a.z) * (float)localFrameIdx;
-      L = L / (float)(localFrameIdx + 1);
-    }
-    a = vec4{L.x, L.y, L.z, 1.0f};
-  }
-  acc[p] = a;
-}
-#endif
 
 // ---- GMoN ---------------------------------------------------------------------------------------------
 // Accumulate into the bucket images exactly as the reference does with RendererFlags_GMoN: sample f goes to bucket
@@ -974,13 +878,13 @@ __global__ void __launch_bounds__(kBlock) k_accumulate_gmon(vec4* __restrict__ b
   const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
   if (p >= npixels) return;
   const uint32_t l0 = lbuf_index_of_pixel(p, width, 0, nsamples);
-  constexpr uint32_t kGroup = PT_PIXEL_MAJOR ? 8u : 1u;  // (as k_accumulate: one 128-byte line of samples per round of loads)
+  constexpr uint32_t kGroup = 8u;  // (as k_accumulate: one 128-byte line of samples per round of loads)
   vec4 v[kGroup];
   for (uint32_t s = 0; s < nsamples; s++) {
     if (s % kGroup == 0) {
 #pragma unroll
       for (uint32_t j = 0; j < kGroup; j++)
-        if (s + j < nsamples) v[j] = ld_stream(&Lbuf[l0 + (s + j) * kLbufSampleStride]);
+        if (s + j < nsamples) v[j] = ld_stream(&Lbuf[l0 + (s + j)]);   // (a pixel's samples are consecutive: lbuf_index)
     }
     vec4 L4 = v[0];
 #pragma unroll
@@ -1130,13 +1034,11 @@ __global__ void __launch_bounds__(kBlock) k_hit_records(DeviceScene S, PathState
 // ---- launchers (host) ---------------------------------------------------------------------------------------------------
 void launch_raygen(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState st, vec4* Lbuf, Segments seg, BatchCounters* ctr,
                    uint32_t first_sample, uint32_t nsamples) {
-  const uint32_t tilesX = (S.width + 7) / 8, tilesY = (S.height + 7) / 8;
-  hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, seg, ctr, first_sample, nsamples, tilesX, tilesY);
+  hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, seg, ctr, first_sample, nsamples, tiles_x(S.width), tiles_y(S.height));
 }
 void launch_raygen_adaptive(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState st, vec4* Lbuf, Segments seg,
                             uint32_t first_sample, uint32_t nsamples, const uint32_t* active, const uint32_t* active_count) {
-  const uint32_t tilesX = (S.width + 7) / 8;
-  hipLaunchKernelGGL(k_raygen_adaptive, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, seg, first_sample, nsamples, tilesX, active, active_count);
+  hipLaunchKernelGGL(k_raygen_adaptive, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, seg, first_sample, nsamples, tiles_x(S.width), active, active_count);
 }
 void launch_chunk_tables(hipStream_t s, Segments seg, uint32_t cur, BatchCounters* ctr, uint32_t bounce_closest,
                          uint32_t bounce_shadow, bool do_shadow) {
@@ -1189,20 +1091,14 @@ void launch_trace_shadow(hipStream_t s, uint32_t grid, const DeviceScene& S, Sha
 }
 void launch_accumulate(hipStream_t s, vec4* acc, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
                        uint32_t nonfinite_policy, BatchCounters* ctr) {
-#if PT_PIXEL_MAJOR
-  const uint32_t tiles = ((width + 7u) / 8u) * ((npixels / width + 7u) / 8u);   // one wave per 8x8 tile
+  const uint32_t tiles = tile_count(width, npixels / width);   // one wave per 8x8 tile
   hipLaunchKernelGGL(k_accumulate, dim3((tiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, s, acc, Lbuf, npixels, width, nsamples, n0,
                      nonfinite_policy, ctr);
-#else
-  hipLaunchKernelGGL(k_accumulate, dim3((npixels + kBlock - 1) / kBlock), dim3(kBlock), 0, s, acc, Lbuf, npixels, width, nsamples, n0,
-                     nonfinite_policy, ctr);
-#endif
 }
 void launch_accumulate_adaptive(hipStream_t s, vec4* acc, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
                                 uint32_t nonfinite_policy, BatchCounters* ctr, const uint32_t* active, const uint32_t* active_count, vec2* mom,
                                 uint32_t* tile_n) {
-  static_assert(PT_PIXEL_MAJOR, "k_accumulate_adaptive stages the [pixel][sample] layout of a tile");
-  const uint32_t tiles = ((width + 7u) / 8u) * ((npixels / width + 7u) / 8u);   // one wave per tile that may still be active
+  const uint32_t tiles = tile_count(width, npixels / width);   // one wave per tile that may still be active
   hipLaunchKernelGGL(k_accumulate_adaptive, dim3((tiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, s, acc, Lbuf, npixels, width, nsamples,
                      n0, nonfinite_policy, ctr, active, active_count, mom, tile_n);
 }

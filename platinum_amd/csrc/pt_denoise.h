@@ -13,6 +13,7 @@
 //   col   {I.rgb, v}  demodulated colour and its variance; v = -1 marks a pixel that is never a tap (its colour is not finite)
 //   aux   {max(a, 1e-3).rgb, gz}  the remodulation albedo and the depth gradient (read for the centre pixel only)
 #pragma once
+#include "pt_layout.h"
 #include "pt_shade.h"
 
 namespace pt {
@@ -98,11 +99,11 @@ PT_HD void dn_prep_pixel(const vec4* acc, const vec4* albedo, const vec4* normal
   aux[p] = vec4{am.x, am.y, am.z, gz};
 }
 
-// The prep of an adaptive render: N = the pixel's own sample count, that of its 8x8 tile (tile_n[(y / 8) * ceil(W / 8) + x / 8]);
+// The prep of an adaptive render: N = the pixel's own sample count, that of its 8x8 tile (tile_n[tile_of_pixel]);
 // otherwise dn_prep_pixel's arithmetic, unchanged.
 PT_HD void dn_prep_pixel_counts(const vec4* acc, const vec4* albedo, const vec4* normal, const vec4* moments, uint32_t W, uint32_t H,
                                 uint32_t x, uint32_t y, const uint32_t* tile_n, vec4* guide, vec4* col, vec4* aux) {
-  const float N = (float)tile_n[(y >> 3) * ((W + 7u) / 8u) + (x >> 3)];
+  const float N = (float)tile_n[tile_of_pixel(x, y, W)];
   dn_prep_pixel(acc, albedo, normal, moments, W, H, x, y, N, guide, col, aux);
 }
 

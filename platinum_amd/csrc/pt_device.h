@@ -235,7 +235,7 @@ struct DeviceScene {
 // ---- wavefront state (SoA, one element per path slot; ping-pong between bounces) ---------------------------------
 // rayO.w  = pdf of the BSDF sample that generated this ray (lastSample.pdf, kernel.metal:574)
 // rayD.w  = bits: [9:0] next Halton dimension, [10] lastSample was specular (kernel.metal:561), [31:11] the path's entry of the
-//           per-sample radiance buffer, relative to the window of its segment (kernels.hip lbuf_index; a path never leaves its segment)
+//           per-sample radiance buffer, relative to the window of its segment (pt_layout.h lbuf_index; a path never leaves its segment)
 // att.w   = bits: Halton offset of this (pixel, sample) (samplers.metal:154-156)
 struct PathState {
   vec4* rayO;

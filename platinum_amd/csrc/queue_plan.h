@@ -1,7 +1,7 @@
 // queue_plan.h — how pt_start_render sizes the wavefront queues (pure host arithmetic; exported as pt_plan_queues for tests).
 //
 // A SEGMENT is the queue share of `tiles_per_seg` 8x8 pixel tiles under all `samples_in_flight` samples of a batch
-// (kernels.hip).  What bounds the numbers:
+// (kernels.hip; pt_layout.h holds the index maps).  What bounds the numbers:
 //   * slot numbers inside a segment travel through k_shade's per-wave class bins as 16-bit values  -> seg_cap <= 65536
 //   * a path's radiance-buffer entry relative to its segment rides in 21 bits of rayD.w            -> seg_cap <= 2^21 (implied)
 //   * the chunk tables pack (chunk << 16) | segment                                                 -> nseg <= 65536, chunks < 65536
@@ -13,12 +13,12 @@
 #include <cstdint>
 
 #include "../../include/ptamd.h"
+#include "pt_layout.h"
 
 namespace pt {
 
 constexpr uint32_t kMaxSegments = 32768;      // chunk tables: 16 bits of segment id; k_chunk_tables' per-block slice <= 1024 segments
 constexpr uint32_t kMaxSegmentSlots = 65536;  // k_shade: uint16_t slot numbers in the class bins
-constexpr uint32_t kSegGroupChunks = 16;      // kernels.hip PT_SEG_GROUP
 
 // returns PT_OK, or PT_ERR_INVALID_ARGUMENT / PT_ERR_UNSUPPORTED with *why set
 inline int plan_queues(uint32_t width, uint32_t height, uint32_t spp, uint32_t samples_in_flight, uint64_t free_hbm_bytes,
@@ -28,7 +28,7 @@ inline int plan_queues(uint32_t width, uint32_t height, uint32_t spp, uint32_t s
   if ((uint64_t)width * height > (1ull << 28)) { *why = "image too large"; return PT_ERR_INVALID_ARGUMENT; }
   if (seg_bands == 0) seg_bands = 1;
   const uint64_t npix = (uint64_t)width * height;
-  const uint64_t tiles = (uint64_t)((width + 7) / 8) * ((height + 7) / 8);
+  const uint64_t tiles = tile_count(width, height);
   uint32_t sif = samples_in_flight;
   if (sif == 0) {
     // As many samples of the frame in flight as a quarter of the free HBM holds (~200 B of queue state per path), up to 128:
@@ -51,8 +51,7 @@ inline int plan_queues(uint32_t width, uint32_t height, uint32_t spp, uint32_t s
   out->tiles_per_seg = tps;
   out->nseg = nseg;
   out->seg_cap = tps * sif * 64;
-  const uint64_t K = out->seg_cap / 64;
-  out->capacity = (uint64_t)nseg * ((K + kSegGroupChunks - 1) / kSegGroupChunks * kSegGroupChunks) * 64;  // >= npix * sif
+  out->capacity = seg_queue_slots(nseg, out->seg_cap);  // >= npix * sif
   out->lbuf_entries = tiles * 64 * sif;
   return PT_OK;
 }

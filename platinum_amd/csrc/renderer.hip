@@ -59,7 +59,7 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
   const DeviceScene& S = r->S;
   hipStream_t s = r->stream;
   BatchCounters* ctr = r->ctr.p;
-  // the per-bounce hit log is indexed by pixel through pixel_of_pid_1spp (kernels.hip): it only exists for one-sample batches
+  // the per-bounce hit log is indexed by pixel through pixel_of_pid_1spp (pt_layout.h): it only exists for one-sample batches
   if (hitlog && ns != 1) return fail(PT_ERR_INVALID_ARGUMENT, "the hit log is kept for one-sample batches only");
   if (ns == 0 || ns > r->samples_in_flight) return fail(PT_ERR_INVALID_ARGUMENT, "batch larger than the queues");
   PT_HIP(hipMemsetAsync(ctr, 0, sizeof(BatchCounters), s));
@@ -70,8 +70,7 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
   if (const char* e = getenv("PTAMD_DEBUG_RAY")) {  // debug build only: "x,y,sample,bounce" -> the closest-hit kernel prints that ray's traversal
     uint32_t x = 0, y = 0, sm = 0, b = 0;
     if (sscanf(e, "%u,%u,%u,%u", &x, &y, &sm, &b) == 4 && sm >= first && sm < first + ns) {
-      const uint32_t tilesX = (S.width + 7) / 8;
-      const uint32_t v[2] = {(((y >> 3) * tilesX + (x >> 3)) * 64u + (y & 7) * 8u + (x & 7)) * ns + (sm - first), b + 1u};
+      const uint32_t v[2] = {lbuf_index(tile_of_pixel(x, y, S.width), sm - first, ns, lane_of_pixel(x, y)), b + 1u};
       PT_HIP(hipMemcpyAsync(&ctr->_pad[0], v, 8, hipMemcpyHostToDevice, s));
     }
   }
@@ -536,7 +535,7 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   }
   PT_HIP(r->hit.alloc(r->capacity));
   PT_HIP(r->sq_o.alloc(r->capacity)); PT_HIP(r->sq_d.alloc(r->capacity)); PT_HIP(r->sq_c.alloc(r->capacity));
-  PT_HIP(r->Lbuf.alloc((size_t)((p->width + 7) / 8) * ((p->height + 7) / 8) * 64 * sif));  // tile-major, whole tiles (kernels.hip lbuf_index)
+  PT_HIP(r->Lbuf.alloc((size_t)tile_count(p->width, p->height) * 64 * sif));  // tile-major, whole tiles (pt_layout.h lbuf_index)
   for (int k = 0; k < 2; k++) PT_HIP(r->seg_active[k].alloc(r->nseg));
   PT_HIP(r->seg_shadow.alloc(r->nseg));
   PT_HIP(r->seg_poison.alloc(r->nseg));
@@ -566,7 +565,7 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
     PT_HIP(hipMemsetAsync(r->aov_img.p, 0, sizeof(vec4) * 3 * npix, r->stream));
   }
   if (adaptive) {  // every tile starts active: list [0, tiles), count = tiles (adaptive.hip)
-    const uint32_t tiles = ((p->width + 7) / 8) * ((p->height + 7) / 8);
+    const uint32_t tiles = tile_count(p->width, p->height);
     std::vector<uint32_t> iota(tiles);
     for (uint32_t t = 0; t < tiles; t++) iota[t] = t;
     PT_HIP(r->ad_list[0].upload(iota));
@@ -720,12 +719,11 @@ int dev_wait(pt_renderer* r) {
     if (const char* e = getenv("PTAMD_DEBUG_PIXEL")) {  // analysis aid: "x,y" -> the per-sample radiance of that pixel in the LAST batch
       uint32_t x = 0, y = 0;
       if (sscanf(e, "%u,%u", &x, &y) == 2 && x < r->S.width && y < r->S.height) {
-        const uint32_t tilesX = (r->S.width + 7) / 8, ns = r->last_batch_ns;
-        const uint32_t tile = (y >> 3) * tilesX + (x >> 3), pl = (y & 7) * 8 + (x & 7);
-        const size_t at0 = lbuf_index_host(tile, 0, ns, pl), stride = lbuf_sample_stride_host();   // the layout kernels.hip was compiled with
+        const uint32_t ns = r->last_batch_ns;
+        const size_t at0 = lbuf_index(tile_of_pixel(x, y, r->S.width), 0, ns, lane_of_pixel(x, y));   // the pixel's ns samples are consecutive
         std::vector<vec4> v(ns);
-        bool ok = at0 + (size_t)(ns - 1) * stride < r->Lbuf.n;   // (a restart with another size / batch before any new batch: last_batch_ns is reset then, this is the belt)
-        for (uint32_t k = 0; ok && k < ns; k++) ok = hipMemcpy(&v[k], r->Lbuf.p + at0 + (size_t)k * stride, sizeof(vec4), hipMemcpyDeviceToHost) == hipSuccess;
+        bool ok = at0 + ns <= r->Lbuf.n;   // (a restart with another size / batch before any new batch: last_batch_ns is reset then, this is the belt)
+        if (ok) ok = hipMemcpy(v.data(), r->Lbuf.p + at0, sizeof(vec4) * ns, hipMemcpyDeviceToHost) == hipSuccess;
         if (!ok) (void)hipGetLastError();   // an analysis aid must not leave an error for the next batch's hipGetLastError()
         for (uint32_t k = 0; ok && k < ns; k++) {
           uint32_t b[3]; memcpy(b, &v[k], 12);
@@ -897,11 +895,10 @@ int dev_read_sample_counts(pt_renderer* r, uint32_t* out) {
     std::fill(out, out + (size_t)W * H, (uint32_t)r->launched);
     return PT_OK;
   }
-  const uint32_t tilesX = (W + 7) / 8;
   std::vector<uint32_t> tn(r->ad_tile_n.n);
   PT_HIP(hipMemcpy(tn.data(), r->ad_tile_n.p, sizeof(uint32_t) * tn.size(), hipMemcpyDeviceToHost));
   for (uint32_t y = 0; y < H; y++)
-    for (uint32_t x = 0; x < W; x++) out[(size_t)y * W + x] = tn[(y >> 3) * tilesX + (x >> 3)];
+    for (uint32_t x = 0; x < W; x++) out[(size_t)y * W + x] = tn[tile_of_pixel(x, y, W)];
   return PT_OK;
 }
 
@@ -1044,12 +1041,12 @@ int dev_debug_sample(pt_renderer* r, uint32_t sample_idx, float* radiance_out, i
   PT_HIP(hipStreamSynchronize(r->stream));
   r->drop_timed();
   if (radiance_out) {  // Lbuf of a one-sample batch is [tile][lane]: bring it back and put it in image order
-    const uint32_t W = r->S.width, H = r->S.height, tilesX = (W + 7) / 8, tilesY = (H + 7) / 8;
-    std::vector<vec4> tiled((size_t)tilesX * tilesY * 64);
+    const uint32_t W = r->S.width, H = r->S.height;
+    std::vector<vec4> tiled((size_t)tile_count(W, H) * 64);
     PT_HIP(hipMemcpy(tiled.data(), r->Lbuf.p, sizeof(vec4) * tiled.size(), hipMemcpyDeviceToHost));
     for (uint32_t y = 0; y < H; y++)
       for (uint32_t x = 0; x < W; x++) {
-        const vec4& v = tiled[((size_t)(y >> 3) * tilesX + (x >> 3)) * 64 + (y & 7) * 8 + (x & 7)];
+        const vec4& v = tiled[lbuf_index(tile_of_pixel(x, y, W), 0, 1, lane_of_pixel(x, y))];
         float* o = radiance_out + ((size_t)y * W + x) * 4;
         o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
       }

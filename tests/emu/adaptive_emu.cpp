@@ -14,12 +14,11 @@ void ad_host_error(const float* m1, const float* m2, size_t count, uint32_t n, f
 // The verdict of every 8x8 tile of a W*H PT_AOV_MOMENTS image (g, b = m1, m2) after n samples, as k_adaptive_check reaches it:
 // converged[tile] = 1 when every pixel of the tile inside the image passes adaptive_pixel_converged.
 void ad_host_tiles(const float* moments, uint32_t W, uint32_t H, uint32_t n, float threshold, uint8_t* converged) {
-  const uint32_t tilesX = (W + 7) / 8, tilesY = (H + 7) / 8;
-  for (uint32_t t = 0; t < tilesX * tilesY; t++) converged[t] = 1;
+  for (uint32_t t = 0; t < tile_count(W, H); t++) converged[t] = 1;
   for (uint32_t y = 0; y < H; y++)
     for (uint32_t x = 0; x < W; x++) {
       const float* m = moments + 4 * ((size_t)y * W + x);
-      if (!adaptive_pixel_converged(m[1], m[2], n, threshold)) converged[(y / 8) * tilesX + x / 8] = 0;
+      if (!adaptive_pixel_converged(m[1], m[2], n, threshold)) converged[tile_of_pixel(x, y, W)] = 0;
     }
 }
 
@@ -34,10 +33,12 @@ void ad_host_filter_counts(const float* acc, const float* albedo, const float* n
     for (size_t p = 0; p < npix; p++) o[p] = vec4{a[p].x, a[p].y, a[p].z, 1.0f};
     return;
   }
-  const uint32_t tilesX = (W + 7) / 8, tilesY = (H + 7) / 8;
-  std::vector<uint32_t> tile_n((size_t)tilesX * tilesY);
-  for (uint32_t ty = 0; ty < tilesY; ty++)
-    for (uint32_t tx = 0; tx < tilesX; tx++) tile_n[(size_t)ty * tilesX + tx] = counts[(size_t)(ty * 8) * W + tx * 8];
+  const uint32_t tilesX = tiles_x(W);
+  std::vector<uint32_t> tile_n(tile_count(W, H));
+  for (uint32_t t = 0; t < tile_n.size(); t++) {   // every pixel of a tile holds the same count: take its first
+    const PixelXY p = tile_pixel(t, 0, tilesX);
+    tile_n[t] = counts[(size_t)p.y * W + p.x];
+  }
   std::vector<vec4> guide(npix), aux(npix), col0(npix), col1(npix);
   for (uint32_t y = 0; y < H; y++)
     for (uint32_t x = 0; x < W; x++)

@@ -28,6 +28,7 @@ static inline void emu_perturb_rcp(pt::vec3& inv) {
 }
 #define PT_TEST_PERTURB_RCP(v) emu_perturb_rcp(v)
 #include "../../platinum_amd/csrc/host_scene.h"
+#include "../../platinum_amd/csrc/pt_layout.h"
 #include "../../platinum_amd/csrc/pt_shade.h"
 
 using namespace pt;
@@ -769,12 +770,14 @@ void emu_packet_probe(void* h, uint32_t sample, double out[6]) {
   const DeviceScene& S = e->S;
   std::vector<uint32_t> lds(std::max(kLdsStack, kLdsStack6) + 1), spill(kSpillStack), pend(std::max(kPendLeaves, kPendLeaves6) + 1);
   double packets = 0, pn = 0, pt_ = 0, rn = 0, rt = 0, mism = 0;
-  for (uint32_t ty = 0; ty < (S.height + 7) / 8; ty++)
-    for (uint32_t tx = 0; tx < (S.width + 7) / 8; tx++) {
+  const uint32_t tilesX = tiles_x(S.width);
+  for (uint32_t ty = 0; ty < tiles_y(S.height); ty++)
+    for (uint32_t tx = 0; tx < tilesX; tx++) {
       struct R { vec3 o, d, inv; RayHit best; bool on; } r[64];
       int n = 0;
       for (uint32_t l = 0; l < 64; l++) {
-        const uint32_t x = tx * 8 + (l & 7), y = ty * 8 + (l >> 3);
+        const PixelXY p = tile_pixel(ty * tilesX + tx, l, tilesX);
+        const uint32_t x = p.x, y = p.y;
         if (x >= S.width || y >= S.height) continue;
         const RayGenOut rg = stage_raygen(S, x, y, sample);
         R& q = r[n++];
@@ -868,7 +871,9 @@ void emu_origin_sort_probe(void* h, uint32_t tile_x, uint32_t tile_y, uint32_t n
   std::vector<R> rays;
   for (uint32_t pl = 0; pl < 64; pl++)
     for (uint32_t smp = 0; smp < ns; smp++) {
-      const uint32_t x = tile_x * 8 + (pl & 7), y = tile_y * 8 + (pl >> 3);
+      const uint32_t tilesX = tiles_x(S.width);
+      const PixelXY p = tile_pixel(tile_y * tilesX + tile_x, pl, tilesX);
+      const uint32_t x = p.x, y = p.y;
       if (x >= S.width || y >= S.height) continue;
       RayGenOut rg = stage_raygen(S, x, y, smp);
       vec3 o = rg.o, d = rg.d, att = v3(1.0f);
@@ -956,7 +961,9 @@ static void gen_tile_rays(const Emu* e, uint32_t tile_x, uint32_t tile_y, uint32
   std::vector<uint32_t> tmp;
   for (uint32_t pl = 0; pl < 64; pl++)
     for (uint32_t smp = 0; smp < ns; smp++) {
-      const uint32_t x = tile_x * 8 + (pl & 7), y = tile_y * 8 + (pl >> 3);
+      const uint32_t tilesX = tiles_x(S.width);
+      const PixelXY p = tile_pixel(tile_y * tilesX + tile_x, pl, tilesX);
+      const uint32_t x = p.x, y = p.y;
       if (x >= S.width || y >= S.height) continue;
       RayGenOut rg = stage_raygen(S, x, y, smp);
       vec3 o = rg.o, d = rg.d, att = v3(1.0f);
@@ -1071,8 +1078,8 @@ void emu_l2_probe(void* h, uint32_t bounce, uint32_t ns, uint32_t s0, uint32_t T
   const DeviceScene& S = e->S;
   for (int i = 0; i < 18; i++) out[i] = 0;
   if (!S.wide6) return;
-  const uint32_t tilesX = (S.width + 7) / 8, tilesY = (S.height + 7) / 8, tiles = tilesX * tilesY, per_band = tiles / 4;
-  // today's table order: segment sg = 4 * idx + band  ->  tile band * per_band + idx (kernels.hip segment_first_tile)
+  const uint32_t tilesX = tiles_x(S.width), tiles = tile_count(S.width, S.height), per_band = tiles / 4;
+  // today's table order: segment sg = 4 * idx + band  ->  tile band * per_band + idx (pt_layout.h segment_first_tile)
   std::vector<uint32_t> seg_tile;
   for (uint32_t idx = s0; idx < s0 + T && idx < per_band; idx++) for (uint32_t band = 0; band < 4; band++) seg_tile.push_back(band * per_band + idx);
   std::vector<std::vector<ProbeRay>> tr(seg_tile.size());

@@ -1,5 +1,6 @@
 #!/bin/bash
-# usage: tools/build_variant.sh <tag> [-DFLAG ...] — libptamd_<tag>.so = the library with kernels.hip (+ renderer.hip) compiled under extra flags
+# usage: tools/build_variant.sh <tag> [-DFLAG ...] — libptamd_<tag>.so = the library with every translation unit that sees the layout and
+# kernel switches (kernels, denoise, adaptive, renderer: all include pt_layout.h) compiled under extra flags
 # (experiments only; select with PTAMD_LIB=platinum_amd/csrc/libptamd_<tag>.so; tools/ab.sh benches them)
 set -e
 tag=$1; shift
@@ -7,6 +8,10 @@ cd "$(dirname "$0")/../platinum_amd/csrc"
 make -s all
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -Wno-unused-result"
 /opt/rocm/bin/hipcc $F -mllvm -disable-machine-licm "$@" -c kernels.hip -o /tmp/kernels_$tag.o   # same flags as the Makefile's kernels.o
-/opt/rocm/bin/hipcc $F "$@" -c renderer.hip -o /tmp/renderer_$tag.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o libptamd_$tag.so /tmp/renderer_$tag.o /tmp/kernels_$tag.o multi_device.o lbvh.o scene_io.o scene_gltf.o scene_image.o scene_jpeg.o -lz -ldl -lpthread
+objs=/tmp/kernels_$tag.o
+for u in denoise adaptive renderer; do
+  /opt/rocm/bin/hipcc $F "$@" -c $u.hip -o /tmp/${u}_$tag.o
+  objs="$objs /tmp/${u}_$tag.o"
+done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o libptamd_$tag.so $objs multi_device.o lbvh.o scene_io.o scene_gltf.o scene_image.o scene_jpeg.o -lz -ldl -lpthread
 echo built libptamd_$tag.so
