@@ -435,6 +435,31 @@ int pt_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o);
  * pt_read_accumulator. */
 int pt_read_sample_counts(pt_renderer* r, uint32_t* out);
 
+/* ---- render regions (NEW, an additive extension of ABI 5: new entry points and one new struct, no existing struct changed) ----
+ * A render started while `enabled` is set samples only the pixels [x0, x1) x [y0, y1) of the frame (top-left origin): the region R.
+ * The sampler is a function of (pixel, sample index), so the render is a restriction of the full-frame one: every accumulator and AOV
+ * pixel inside R holds the bits it holds without a region, for any samples_in_flight and any sequence of pt_render_step calls;
+ * outside R the accumulator, the AOVs and the denoised image are all-zero bits, alpha included, and pt_read_sample_counts returns 0.
+ * pt_stats.paths counts the paths of R only (area(R) * spp for a uniform render).  spp, progress, status and batching are unchanged;
+ * enabled = 1 with R equal to the whole frame gives the bits of a render without a region in every output.
+ * The denoiser filters R as if it were the whole image: taps outside R are skipped like taps outside the image, the depth gradient is
+ * one-sided at R's border and the variance blur sees R only.  Post-processing and present run over the full frame, on R plus zeros.
+ * With adaptive sampling the first active tiles are those R touches, and a tile's verdict is taken over its pixels inside R only (a
+ * border tile may stop earlier than in a full-frame adaptive render); everything else is as stated above for adaptive sampling.
+ * pt_trace_primary, pt_debug_sample and pt_measure_traversal stay full-frame.  The queues are sized for the frame (pt_plan_queues).
+ * Refused with PT_ERR_UNSUPPORTED: PT_FLAG_GMON together with enabled (at pt_start_render), and enabled = 1 on a device group.
+ * pt_start_render returns PT_ERR_INVALID_ARGUMENT when x1 > width or y1 > height. */
+typedef struct pt_render_region {
+  uint32_t enabled;         /* read at pt_start_render; default 0: the whole frame */
+  uint32_t x0, y0, x1, y1;  /* pixels [x0, x1) x [y0, y1) */
+} pt_render_region;
+void pt_default_render_region(pt_render_region* o);
+/* PT_ERR_INVALID_ARGUMENT for enabled with x0 >= x1 or y0 >= y1 */
+int pt_set_render_region(pt_renderer* r, const pt_render_region* o);
+/* Pure host arithmetic (exported for tests, like pt_plan_queues): the 8x8 image tiles (row-major, (W + 7) / 8 per row) a region
+ * activates, ascending; every tile when enabled = 0.  Writes up to `capacity` of them and their total number to *count. */
+int pt_region_tiles(uint32_t width, uint32_t height, const pt_render_region* o, uint32_t* tiles_out, uint32_t capacity, uint32_t* count);
+
 const char* pt_last_error(void);
 
 /* ---------------------------------------------------------------------------------------------------------- */

@@ -34,6 +34,8 @@
  *   (no counterpart)                                             pt_adaptive_options& adaptiveOptions() / setAdaptiveOptions(...),
  *                                                                readbackSampleCounts(): tile-adaptive sampling (ptamd.h, ABI 5 extension);
  *                                                                handed over at startRender
+ *   (no counterpart)                                             pt_render_region& renderRegion() / setRenderRegion(...): sample only a pixel
+ *                                                                rectangle of the frame (ptamd.h, ABI 5 extension); handed over at startRender
  * Error behaviour as the reference's: nothing throws; a failing call prints "renderer_pt: <message>" to stderr (the
  * reference prints and asserts, renderer_pt.cpp:402, 1044) and leaves the object in Status_Blocked; lastError() keeps the text.
  * Threading as the reference's: one caller thread per Renderer.
@@ -108,6 +110,7 @@ public:
     p.accel_structure = m_accelStructure;
     if (!check(pt_set_denoise_options(m_pt, &m_denoise))) return;   // (`enabled` is read here)
     if (!check(pt_set_adaptive_options(m_pt, &m_adaptive))) return;  // (read here)
+    if (!check(pt_set_render_region(m_pt, &m_region))) return;       // (read here)
     if (!check(pt_start_render(m_pt, &scene, &p))) return;
     m_size = uint2{p.width, p.height};
     m_started = true;
@@ -206,6 +209,11 @@ public:
     if (!check(pt_read_sample_counts(m_pt, out.data()))) out.clear();
     return out;
   }
+  // Render regions (ptamd.h, an additive extension of ABI 5): the next startRender samples only the pixels [x0, x1) x [y0, y1); everything
+  // outside stays zero, alpha included.  Edited in place like adaptiveOptions(); enabled = 0 (the default) is the whole frame.
+  [[nodiscard]] constexpr pt_render_region& renderRegion() { return m_region; }
+  void setRenderRegion(const pt_render_region& o) { m_region = o; }
+  void setRenderRegion(uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) { m_region = pt_render_region{1u, x0, y0, x1, y1}; }
   void wait() const { if (m_pt && m_started) check(pt_wait(m_pt)); }
   [[nodiscard]] bool ok() const { return m_pt != nullptr && m_lastError.empty(); }
   [[nodiscard]] const std::string& lastError() const { return m_lastError; }
@@ -218,6 +226,7 @@ private:
     m_outputSpace = defaults.output_space;   // Display P3 (renderer_pt.hpp:182)
     pt_default_denoise_options(&m_denoise);
     pt_default_adaptive_options(&m_adaptive);
+    pt_default_render_region(&m_region);
     std::vector<int32_t> ord(devices, devices + count);
     pt_create_info ci{};
     ci.abi_version = PT_ABI_VERSION;
@@ -259,6 +268,7 @@ private:
   pt_gmon_options m_gmonOptions{1.0f};
   pt_denoise_options m_denoise{};
   pt_adaptive_options m_adaptive{};
+  pt_render_region m_region{};
   mutable void* m_presentStream = nullptr;
   mutable std::string m_lastError;
 };

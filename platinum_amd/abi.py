@@ -180,6 +180,11 @@ class AdaptiveOptions(C.Structure):
     _fields_ = [("enabled", C.c_uint32), ("threshold", C.c_float), ("min_spp", C.c_uint32), ("interval", C.c_uint32)]
 
 
+class RenderRegion(C.Structure):
+    """pt_render_region: pixels [x0, x1) x [y0, y1), top-left origin; enabled 0 = the whole frame."""
+    _fields_ = [("enabled", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("x1", C.c_uint32), ("y1", C.c_uint32)]
+
+
 class HitRecord(C.Structure):
     _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("instance", C.c_int32), ("primitive", C.c_int32)]
 
@@ -242,6 +247,9 @@ SYMBOLS = [
     ("pt_default_adaptive_options", None, [C.POINTER(AdaptiveOptions)]),
     ("pt_set_adaptive_options", C.c_int, [C.c_void_p, C.POINTER(AdaptiveOptions)]),
     ("pt_read_sample_counts", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("pt_default_render_region", None, [C.POINTER(RenderRegion)]),
+    ("pt_set_render_region", C.c_int, [C.c_void_p, C.POINTER(RenderRegion)]),
+    ("pt_region_tiles", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(RenderRegion), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("pt_last_error", C.c_char_p, []),
     ("pt_get_constants", C.c_int, [C.c_void_p, C.POINTER(Constants)]),
     ("pt_get_lights", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),

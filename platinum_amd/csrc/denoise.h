@@ -12,15 +12,17 @@ void launch_aov(hipStream_t s, uint32_t grid, const DeviceScene* S_device, PathS
 // After k_accumulate / k_gmon: Abuf and Lbuf of the batch folded into the three AOV images (n0 samples already in them).
 void launch_accumulate_aov(hipStream_t s, vec4* albedo, vec4* normal, vec4* moments, const vec4* Abuf, const vec4* Lbuf, uint32_t width,
                            uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy);
-// The same over the active tiles of an adaptive render (kernels.h launch_raygen_adaptive: Abuf and Lbuf dense over virtual tiles).
+// The same over the active tiles of an adaptive or region render (kernels.h launch_raygen_adaptive: Abuf and Lbuf dense over virtual tiles;
+// max_active and rect as launch_accumulate_adaptive).
 void launch_accumulate_aov_adaptive(hipStream_t s, vec4* albedo, vec4* normal, vec4* moments, const vec4* Abuf, const vec4* Lbuf, uint32_t width,
                                     uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy, const uint32_t* active,
-                                    const uint32_t* active_count);
-// The filter over the current image: prep, `iterations` a-trous steps, the last one remodulated into `out` (W*H vec4).
+                                    const uint32_t* active_count, uint32_t max_active, const Rect& rect);
+// The filter over the rectangle `rect` of the current W x H image, as if the rectangle were the whole image (the whole frame: {0, 0, W, H}):
+// prep, `iterations` a-trous steps, the last one remodulated into `out` (W*H vec4; pixels outside rect are left as they are).
 // guide / aux / col0 / col1 are W*H vec4 of scratch each; nsamples = samples folded into the AOVs, or, with tile_n (an adaptive render),
-// tile_n[8x8 tile] = the samples folded into each pixel of that tile.
+// tile_n[8x8 tile of the frame] = the samples folded into each pixel of that tile.
 void launch_denoise(hipStream_t s, const vec4* acc, const vec4* albedo, const vec4* normal, const vec4* moments, uint32_t W, uint32_t H,
                     uint32_t nsamples, const DenoiseParams& P, uint32_t iterations, vec4* guide, vec4* aux, vec4* col0, vec4* col1, vec4* out,
-                    const uint32_t* tile_n = nullptr);
+                    const uint32_t* tile_n, const Rect& rect);
 
 }  // namespace pt

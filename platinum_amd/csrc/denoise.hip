@@ -5,6 +5,8 @@
 //                     (k_accumulate_aov_adaptive: the same over the active tiles of an adaptive render)
 //   k_dn_prep         demodulation, variance, depth gradient (k_dn_prep_counts: with per-pixel sample counts, adaptive renders)
 //   k_atrous          one 5x5 step per launch (ping-pong); the last one remodulates
+// The filter runs over a rectangle of the frame as if it were the whole image (a render region): its kernels take W x H of
+// the rectangle, the frame's width as the row pitch, and pointers to the rectangle's first pixel.
 // Only a render started with AOVs enabled launches any of them (renderer.hip enqueue_batch).
 //
 // Compiled with -ffp-contract=off (deterministic fp32 contract, pt_math.h).
@@ -57,12 +59,12 @@ __global__ void __launch_bounds__(256) k_aov(const DeviceScene* __restrict__ Sp,
 // Abuf), fully coalesced; every lane then folds the eight samples of its pixel in sample order.  One wave per block: the three
 // staging areas take 27 KB.
 // ADAPTIVE (k_accumulate_aov_adaptive, tile-adaptive sampling): block v folds virtual tile v < *active_count into image tile active[v]
-// (kernels.hip k_accumulate_adaptive); Abuf and Lbuf are dense over virtual tiles.
+// (kernels.hip k_accumulate_adaptive); Abuf and Lbuf are dense over virtual tiles.  It folds the pixels inside `rect`.
 template <bool ADAPTIVE>
 __device__ __forceinline__ void accumulate_aov_body(vec4* __restrict__ albedo, vec4* __restrict__ normal, vec4* __restrict__ moments,
                                                     const vec4* __restrict__ Abuf, const vec4* __restrict__ Lbuf, uint32_t width,
                                                     uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy,
-                                                    const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count) {
+                                                    const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count, Rect rect) {
   constexpr uint32_t kRow = 9;
   __shared__ vec4 stage[3][64 * kRow];
   const uint32_t lane = wave_lane();
@@ -71,7 +73,7 @@ __device__ __forceinline__ void accumulate_aov_body(vec4* __restrict__ albedo, v
   const bool live = tile < tiles;
   const uint32_t itile = ADAPTIVE ? (live ? active[tile] : 0u) : tile;   // the image tile
   const PixelXY q = tile_pixel(itile, lane, tilesX);
-  const bool inside = live && q.x < width && q.y < height;
+  const bool inside = live && (ADAPTIVE ? rect_contains(rect, q.x, q.y) : q.x < width && q.y < height);
   const size_t p = (size_t)q.y * width + q.x;
   vec4 A = inside ? albedo[p] : vec4{0, 0, 0, 0}, N = inside ? normal[p] : vec4{0, 0, 0, 0}, M = inside ? moments[p] : vec4{0, 0, 0, 0};
   for (uint32_t s0 = 0; s0 < nsamples; s0 += 8u) {
@@ -112,43 +114,51 @@ __device__ __forceinline__ void accumulate_aov_body(vec4* __restrict__ albedo, v
 __global__ void __launch_bounds__(64) k_accumulate_aov(vec4* __restrict__ albedo, vec4* __restrict__ normal, vec4* __restrict__ moments,
                                                         const vec4* __restrict__ Abuf, const vec4* __restrict__ Lbuf, uint32_t width,
                                                         uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy) {
-  accumulate_aov_body<false>(albedo, normal, moments, Abuf, Lbuf, width, height, nsamples, n0, nonfinite_policy, nullptr, nullptr);
+  accumulate_aov_body<false>(albedo, normal, moments, Abuf, Lbuf, width, height, nsamples, n0, nonfinite_policy, nullptr, nullptr, Rect{});
 }
 
 __global__ void __launch_bounds__(64) k_accumulate_aov_adaptive(vec4* __restrict__ albedo, vec4* __restrict__ normal, vec4* __restrict__ moments,
                                                                  const vec4* __restrict__ Abuf, const vec4* __restrict__ Lbuf, uint32_t width,
                                                                  uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy,
-                                                                 const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count) {
-  accumulate_aov_body<true>(albedo, normal, moments, Abuf, Lbuf, width, height, nsamples, n0, nonfinite_policy, active, active_count);
+                                                                 const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count,
+                                                                 Rect rect) {
+  accumulate_aov_body<true>(albedo, normal, moments, Abuf, Lbuf, width, height, nsamples, n0, nonfinite_policy, active, active_count, rect);
 }
 
 // ---- the filter: 16x16 pixel blocks -----------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_dn_prep(const vec4* __restrict__ acc, const vec4* __restrict__ albedo, const vec4* __restrict__ normal,
-                                                 const vec4* __restrict__ moments, uint32_t W, uint32_t H, float N, vec4* __restrict__ guide,
-                                                 vec4* __restrict__ col, vec4* __restrict__ aux) {
+                                                 const vec4* __restrict__ moments, uint32_t W, uint32_t H, uint32_t pitch, float N,
+                                                 vec4* __restrict__ guide, vec4* __restrict__ col, vec4* __restrict__ aux) {
   const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
-  if (x < W && y < H) dn_prep_pixel(acc, albedo, normal, moments, W, H, x, y, N, guide, col, aux);
+  if (x < W && y < H) dn_prep_pixel(acc, albedo, normal, moments, W, H, pitch, x, y, N, guide, col, aux);
 }
 
-// the prep of an adaptive render: N = the pixel's own sample count, its tile's (dn_prep_pixel_counts)
+// the prep of an adaptive render: N = the pixel's own sample count, its tile's (dn_prep_pixel_counts); the tile is that of the pixel
+// in the frame, (x0 + x, y0 + y)
 __global__ void __launch_bounds__(256) k_dn_prep_counts(const vec4* __restrict__ acc, const vec4* __restrict__ albedo, const vec4* __restrict__ normal,
-                                                        const vec4* __restrict__ moments, uint32_t W, uint32_t H, const uint32_t* __restrict__ tile_n,
-                                                        vec4* __restrict__ guide, vec4* __restrict__ col, vec4* __restrict__ aux) {
+                                                        const vec4* __restrict__ moments, uint32_t W, uint32_t H, uint32_t pitch, uint32_t x0,
+                                                        uint32_t y0, const uint32_t* __restrict__ tile_n, vec4* __restrict__ guide,
+                                                        vec4* __restrict__ col, vec4* __restrict__ aux) {
   const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
-  if (x < W && y < H) dn_prep_pixel_counts(acc, albedo, normal, moments, W, H, x, y, tile_n, guide, col, aux);
+  if (x < W && y < H) dn_prep_pixel_counts(acc, albedo, normal, moments, W, H, pitch, x0, y0, x, y, tile_n, guide, col, aux);
 }
 
 __global__ void __launch_bounds__(256) k_atrous(const vec4* __restrict__ guide, const vec4* __restrict__ aux, const vec4* __restrict__ col_in,
                                                 vec4* __restrict__ col_out, const vec4* __restrict__ acc, vec4* __restrict__ out, DenoiseParams P,
-                                                uint32_t step, uint32_t last) {
+                                                uint32_t pitch, uint32_t step, uint32_t last) {
   const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
-  if (x < P.W && y < P.H) dn_iterate_pixel(guide, aux, col_in, col_out, acc, out, P, x, y, step, last != 0);
+  if (x < P.W && y < P.H) dn_iterate_pixel(guide, aux, col_in, col_out, acc, out, P, pitch, x, y, step, last != 0);
 }
 
 // iterations 0: demodulation and remodulation only, which is the identity: the accumulator itself (alpha 1)
-__global__ void __launch_bounds__(256) k_dn_copy(const vec4* __restrict__ acc, vec4* __restrict__ out, uint32_t npix) {
-  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-  if (p < npix) { const vec4 c = acc[p]; out[p] = vec4{c.x, c.y, c.z, 1.0f}; }
+__global__ void __launch_bounds__(256) k_dn_copy(const vec4* __restrict__ acc, vec4* __restrict__ out, uint32_t W, uint32_t H, uint32_t pitch) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < W * H) {
+    const uint32_t y = i / W;
+    const size_t p = (size_t)y * pitch + (i - y * W);
+    const vec4 c = acc[p];
+    out[p] = vec4{c.x, c.y, c.z, 1.0f};
+  }
 }
 
 void launch_aov(hipStream_t s, uint32_t grid, const DeviceScene* S_device, PathState st, const vec4* hit, Segments seg, vec4* Abuf) {
@@ -164,26 +174,34 @@ void launch_accumulate_aov(hipStream_t s, vec4* albedo, vec4* normal, vec4* mome
 
 void launch_accumulate_aov_adaptive(hipStream_t s, vec4* albedo, vec4* normal, vec4* moments, const vec4* Abuf, const vec4* Lbuf, uint32_t width,
                                     uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy, const uint32_t* active,
-                                    const uint32_t* active_count) {
-  const uint32_t tiles = tile_count(width, height);   // one block per tile that may still be active
-  hipLaunchKernelGGL(k_accumulate_aov_adaptive, dim3(tiles), dim3(64), 0, s, albedo, normal, moments, Abuf, Lbuf, width, height, nsamples, n0,
-                     nonfinite_policy, active, active_count);
+                                    const uint32_t* active_count, uint32_t max_active, const Rect& rect) {
+  // one block per tile that may still be active
+  hipLaunchKernelGGL(k_accumulate_aov_adaptive, dim3(max_active), dim3(64), 0, s, albedo, normal, moments, Abuf, Lbuf, width, height, nsamples, n0,
+                     nonfinite_policy, active, active_count, rect);
 }
 
 void launch_denoise(hipStream_t s, const vec4* acc, const vec4* albedo, const vec4* normal, const vec4* moments, uint32_t W, uint32_t H,
-                    uint32_t nsamples, const DenoiseParams& P, uint32_t iterations, vec4* guide, vec4* aux, vec4* col0, vec4* col1, vec4* out,
-                    const uint32_t* tile_n) {
+                    uint32_t nsamples, const DenoiseParams& Pf, uint32_t iterations, vec4* guide, vec4* aux, vec4* col0, vec4* col1, vec4* out,
+                    const uint32_t* tile_n, const Rect& rect) {
+  // the rectangle as an image of its own: its size, the frame's width as the pitch, every image from the rectangle's first pixel on
+  const uint32_t pitch = W, x0 = rect.x0, y0 = rect.y0;
+  const size_t org = (size_t)y0 * pitch + x0;
+  W = rect.x1 - rect.x0; H = rect.y1 - rect.y0;
+  DenoiseParams P = Pf;
+  P.W = W; P.H = H;
+  acc += org; albedo += org; normal += org; moments += org; out += org;
   if (iterations == 0) {
-    hipLaunchKernelGGL(k_dn_copy, dim3((W * H + 255u) / 256u), dim3(256), 0, s, acc, out, W * H);
+    hipLaunchKernelGGL(k_dn_copy, dim3((W * H + 255u) / 256u), dim3(256), 0, s, acc, out, W, H, pitch);
     return;
   }
+  guide += org; aux += org; col0 += org; col1 += org;
   const dim3 grid((W + 15u) / 16u, (H + 15u) / 16u), block(16, 16);
-  if (tile_n) hipLaunchKernelGGL(k_dn_prep_counts, grid, block, 0, s, acc, albedo, normal, moments, W, H, tile_n, guide, col0, aux);
-  else hipLaunchKernelGGL(k_dn_prep, grid, block, 0, s, acc, albedo, normal, moments, W, H, (float)nsamples, guide, col0, aux);
+  if (tile_n) hipLaunchKernelGGL(k_dn_prep_counts, grid, block, 0, s, acc, albedo, normal, moments, W, H, pitch, x0, y0, tile_n, guide, col0, aux);
+  else hipLaunchKernelGGL(k_dn_prep, grid, block, 0, s, acc, albedo, normal, moments, W, H, pitch, (float)nsamples, guide, col0, aux);
   vec4* cin = col0;
   vec4* cout = col1;
   for (uint32_t i = 0; i < iterations; i++) {
-    hipLaunchKernelGGL(k_atrous, grid, block, 0, s, guide, aux, cin, cout, acc, out, P, 1u << i, i + 1 == iterations ? 1u : 0u);
+    hipLaunchKernelGGL(k_atrous, grid, block, 0, s, guide, aux, cin, cout, acc, out, P, pitch, 1u << i, i + 1 == iterations ? 1u : 0u);
     vec4* t = cin; cin = cout; cout = t;
   }
 }

@@ -291,9 +291,10 @@ __global__ void __launch_bounds__(kBlock) k_raygen(DeviceScene S, PathState st, 
 // Tile-adaptive sampling: k_raygen over the VIRTUAL tiles 0 .. *active_count - 1, the still active tiles of the render; virtual tile v
 // is image tile active[v] (an ascending list).  Lbuf, the segments and the pids are dense over virtual tiles: only the pixel position
 // of a ray looks the list up, and segments past the active count emit nothing.  (A kernel of its own: as one template with k_raygen,
-// the merged k_raygen missed the speed margin set for it: profiles/HISTORY.md §10.)
+// the merged k_raygen missed the speed margin set for it: profiles/HISTORY.md §10.)  A pixel starts a path when it lies in `rect`: the
+// whole frame, or the render region, whose border tiles leave the Lbuf entries of their pixels outside it unwritten.
 __global__ void __launch_bounds__(kBlock) k_raygen_adaptive(DeviceScene S, PathState st, vec4* __restrict__ Lbuf, Segments seg,
-                                                             uint32_t first_sample, uint32_t nsamples, uint32_t tilesX,
+                                                             uint32_t first_sample, uint32_t nsamples, uint32_t tilesX, Rect rect,
                                                              const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count) {
   const uint32_t lane = wave_lane();
   const uint32_t tiles = *active_count;   // virtual tiles
@@ -307,7 +308,7 @@ __global__ void __launch_bounds__(kBlock) k_raygen_adaptive(DeviceScene S, PathS
       const uint32_t r = (k % nsamples) * 64u + lane;
       const uint32_t pl = r / nsamples, s = r - pl * nsamples;
       const PixelXY q = tile_pixel(active[tile], pl, tilesX);   // of the image tile
-      const bool valid = q.x < S.width && q.y < S.height;
+      const bool valid = rect_contains(rect, q.x, q.y);
       RayGenOut rg;
       if (valid) rg = stage_raygen(S, q.x, q.y, first_sample + s);
       const unsigned long long m = __ballot(valid);
@@ -796,12 +797,13 @@ k_trace_shadow(DeviceScene S, ShadowQueue sq, vec4* __restrict__ Lbuf, Segments 
 // wave loads blocks of 64 pixels x 8 samples fully coalesced (eight lanes per 128-byte line), turns them through LDS, and every lane then
 // folds the eight samples of ITS pixel in sample order — the running mean is a sequential recurrence per pixel (kernel.metal:672-684).
 // ADAPTIVE (k_accumulate_adaptive): wave w folds virtual tile w < *active_count into image tile active[w], and also folds the running means
-// of (lum, lum^2) into `mom` with aov_fold / dn_lum (the bits of PT_AOV_MOMENTS .g / .b) and sets the tile's sample count.
+// of (lum, lum^2) into `mom` with aov_fold / dn_lum (the bits of PT_AOV_MOMENTS .g / .b) and sets the tile's sample count.  It folds the
+// pixels inside `rect` (the whole frame or the render region, as k_raygen_adaptive); `mom` is null when no checkpoint will read it.
 template <bool ADAPTIVE>
 __device__ __forceinline__ void accumulate_body(vec4* __restrict__ acc, const vec4* __restrict__ Lbuf, uint32_t npixels, uint32_t width,
                                                 uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy, BatchCounters* __restrict__ ctr,
                                                 const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count,
-                                                vec2* __restrict__ mom, uint32_t* __restrict__ tile_n) {
+                                                vec2* __restrict__ mom, uint32_t* __restrict__ tile_n, Rect rect) {
   constexpr uint32_t kRow = 9;  // vec4 per pixel row in LDS (8 samples + 1 of padding against bank conflicts)
   __shared__ vec4 stage[kBlock / 64][64 * kRow];
   const uint32_t lane = wave_lane(), w = threadIdx.x >> 6;
@@ -810,10 +812,10 @@ __device__ __forceinline__ void accumulate_body(vec4* __restrict__ acc, const ve
   const bool live = tile < tiles;
   const uint32_t itile = ADAPTIVE ? (live ? active[tile] : 0u) : tile;   // the image tile
   const PixelXY q = tile_pixel(itile, lane, tilesX);
-  const bool inside = live && q.x < width && q.y < height;
+  const bool inside = live && (ADAPTIVE ? rect_contains(rect, q.x, q.y) : q.x < width && q.y < height);
   const uint32_t p = q.y * width + q.x;
   vec4 a = inside ? acc[p] : vec4{0.0f, 0.0f, 0.0f, 0.0f};
-  vec2 m = ADAPTIVE && inside ? mom[p] : vec2{0.0f, 0.0f};
+  vec2 m = ADAPTIVE && inside && mom ? mom[p] : vec2{0.0f, 0.0f};
   for (uint32_t s0 = 0; s0 < nsamples; s0 += 8u) {
     const uint32_t nb = nsamples - s0 < 8u ? nsamples - s0 : 8u;
     __syncthreads();
@@ -848,7 +850,7 @@ __device__ __forceinline__ void accumulate_body(vec4* __restrict__ acc, const ve
   }
   if (inside) acc[p] = a;
   if (ADAPTIVE) {
-    if (inside) mom[p] = m;
+    if (inside && mom) mom[p] = m;
     if (live && lane == 0) tile_n[itile] = n0 + nsamples;
   }
 }
@@ -856,15 +858,15 @@ __device__ __forceinline__ void accumulate_body(vec4* __restrict__ acc, const ve
 __global__ void __launch_bounds__(kBlock) k_accumulate(vec4* __restrict__ acc, const vec4* __restrict__ Lbuf,
                                                         uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
                                                         uint32_t nonfinite_policy, BatchCounters* __restrict__ ctr) {
-  accumulate_body<false>(acc, Lbuf, npixels, width, nsamples, n0, nonfinite_policy, ctr, nullptr, nullptr, nullptr, nullptr);
+  accumulate_body<false>(acc, Lbuf, npixels, width, nsamples, n0, nonfinite_policy, ctr, nullptr, nullptr, nullptr, nullptr, Rect{});
 }
 
 __global__ void __launch_bounds__(kBlock) k_accumulate_adaptive(vec4* __restrict__ acc, const vec4* __restrict__ Lbuf,
                                                                  uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
                                                                  uint32_t nonfinite_policy, BatchCounters* __restrict__ ctr,
                                                                  const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count,
-                                                                 vec2* __restrict__ mom, uint32_t* __restrict__ tile_n) {
-  accumulate_body<true>(acc, Lbuf, npixels, width, nsamples, n0, nonfinite_policy, ctr, active, active_count, mom, tile_n);
+                                                                 vec2* __restrict__ mom, uint32_t* __restrict__ tile_n, Rect rect) {
+  accumulate_body<true>(acc, Lbuf, npixels, width, nsamples, n0, nonfinite_policy, ctr, active, active_count, mom, tile_n, rect);
 }
 
 // ---- GMoN ---------------------------------------------------------------------------------------------
@@ -1037,8 +1039,9 @@ void launch_raygen(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState
   hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, seg, ctr, first_sample, nsamples, tiles_x(S.width), tiles_y(S.height));
 }
 void launch_raygen_adaptive(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState st, vec4* Lbuf, Segments seg,
-                            uint32_t first_sample, uint32_t nsamples, const uint32_t* active, const uint32_t* active_count) {
-  hipLaunchKernelGGL(k_raygen_adaptive, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, seg, first_sample, nsamples, tiles_x(S.width), active, active_count);
+                            uint32_t first_sample, uint32_t nsamples, const Rect& rect, const uint32_t* active, const uint32_t* active_count) {
+  hipLaunchKernelGGL(k_raygen_adaptive, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, seg, first_sample, nsamples, tiles_x(S.width), rect, active,
+                     active_count);
 }
 void launch_chunk_tables(hipStream_t s, Segments seg, uint32_t cur, BatchCounters* ctr, uint32_t bounce_closest,
                          uint32_t bounce_shadow, bool do_shadow) {
@@ -1096,11 +1099,11 @@ void launch_accumulate(hipStream_t s, vec4* acc, const vec4* Lbuf, uint32_t npix
                      nonfinite_policy, ctr);
 }
 void launch_accumulate_adaptive(hipStream_t s, vec4* acc, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
-                                uint32_t nonfinite_policy, BatchCounters* ctr, const uint32_t* active, const uint32_t* active_count, vec2* mom,
-                                uint32_t* tile_n) {
-  const uint32_t tiles = tile_count(width, npixels / width);   // one wave per tile that may still be active
+                                uint32_t nonfinite_policy, BatchCounters* ctr, const uint32_t* active, const uint32_t* active_count,
+                                uint32_t max_active, vec2* mom, uint32_t* tile_n, const Rect& rect) {
+  const uint32_t tiles = max_active;   // one wave per tile that may still be active
   hipLaunchKernelGGL(k_accumulate_adaptive, dim3((tiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, s, acc, Lbuf, npixels, width, nsamples,
-                     n0, nonfinite_policy, ctr, active, active_count, mom, tile_n);
+                     n0, nonfinite_policy, ctr, active, active_count, mom, tile_n, rect);
 }
 void launch_accumulate_gmon(hipStream_t s, vec4* buckets, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
                             uint32_t samples_per_bucket, uint32_t gmon_buckets, uint32_t bucket_base, uint32_t nonfinite_policy, BatchCounters* ctr) {

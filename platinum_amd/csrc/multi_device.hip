@@ -731,6 +731,15 @@ int pt_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o) {
   return PT_OK;
 }
 
+// A render region is per device too: the members' accumulators are merged over the whole frame
+int pt_set_render_region(pt_renderer* r, const pt_render_region* o) {
+  if (!is_group(r)) return dev_set_render_region(r, o);
+  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (o->enabled) return fail(PT_ERR_UNSUPPORTED, "pt_set_render_region: a device group does not render regions");
+  for (auto* m : r->group->shards) { int rc = dev_set_render_region(m, o); if (rc != PT_OK) return rc; }
+  return PT_OK;
+}
+
 // a group's render is uniform: every pixel holds the samples of all members
 int pt_read_sample_counts(pt_renderer* r, uint32_t* out) {
   if (!is_group(r)) return dev_read_sample_counts(r, out);

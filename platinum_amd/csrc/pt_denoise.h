@@ -8,6 +8,9 @@
 // agree bit for bit (-ffp-contract=off, IEEE divide / sqrt, the deterministic exp2 / log2 of pt_math.h).  Taps are summed in a fixed
 // order (row-major over dy, then dx).
 //
+// Every image is addressed as y * pitch + x with (x, y) inside W x H.  pitch = W for a whole image; a render region is
+// filtered as an image of its own by passing pointers to its first pixel and the frame's width as the pitch.
+//
 // Per-pixel buffers of the filter (W*H vec4 each):
 //   guide {n.xyz, z}  normalised mean shading normal and mean first-hit distance; z = -1 marks a BACKGROUND pixel (h < 0.5)
 //   col   {I.rgb, v}  demodulated colour and its variance; v = -1 marks a pixel that is never a tap (its colour is not finite)
@@ -58,8 +61,8 @@ PT_HD float dn_powr(float x, float y) { return x <= 0.0f ? 0.0f : dn_exp2(y * lo
 PT_HD bool dn_finite(float x) { return fabsf(x) <= 3.4028234663852886e38f; }
 
 // depth of a pixel for the gradient: z = t / h of a geometry pixel; false for background
-PT_HD bool dn_depth(const vec4* normal, const vec4* moments, uint32_t W, uint32_t x, uint32_t y, float* z) {
-  const size_t p = (size_t)y * W + x;
+PT_HD bool dn_depth(const vec4* normal, const vec4* moments, uint32_t pitch, uint32_t x, uint32_t y, float* z) {
+  const size_t p = (size_t)y * pitch + x;
   const float h = normal[p].w;
   if (!(h >= 0.5f)) return false;
   *z = moments[p].x / h;
@@ -68,8 +71,8 @@ PT_HD bool dn_depth(const vec4* normal, const vec4* moments, uint32_t W, uint32_
 
 // Prep pass for pixel (x, y): `acc` = the accumulator (GMoN-resolved when GMoN is on), N = samples folded into the AOVs.
 PT_HD void dn_prep_pixel(const vec4* acc, const vec4* albedo, const vec4* normal, const vec4* moments, uint32_t W, uint32_t H,
-                         uint32_t x, uint32_t y, float N, vec4* guide, vec4* col, vec4* aux) {
-  const size_t p = (size_t)y * W + x;
+                         uint32_t pitch, uint32_t x, uint32_t y, float N, vec4* guide, vec4* col, vec4* aux) {
+  const size_t p = (size_t)y * pitch + x;
   const vec4 c4 = acc[p], a4 = albedo[p], n4 = normal[p], m4 = moments[p];
   const vec3 c = v3(c4.x, c4.y, c4.z), a = v3(a4.x, a4.y, a4.z);
   const vec3 am = v3(fmaxf(a.x, kDnAlbedoMin), fmaxf(a.y, kDnAlbedoMin), fmaxf(a.z, kDnAlbedoMin));
@@ -77,7 +80,7 @@ PT_HD void dn_prep_pixel(const vec4* acc, const vec4* albedo, const vec4* normal
   const float la = fmaxf(dn_lum(a), kDnAlbedoMin);
   const float v = fmaxf(0.0f, m4.z - m4.y * m4.y) / (N * (la * la));
   float z = 0.0f, gz = 0.0f;
-  const bool geo = dn_depth(normal, moments, W, x, y, &z);
+  const bool geo = dn_depth(normal, moments, pitch, x, y, &z);
   vec3 n = v3(0.0f);
   if (geo) {
     const vec3 nn = v3(n4.x, n4.y, n4.z);
@@ -87,8 +90,8 @@ PT_HD void dn_prep_pixel(const vec4* acc, const vec4* albedo, const vec4* normal
     float g[2];
     for (int axis = 0; axis < 2; axis++) {
       float zm = 0.0f, zp = 0.0f;
-      const bool hm = axis == 0 ? (x > 0 && dn_depth(normal, moments, W, x - 1, y, &zm)) : (y > 0 && dn_depth(normal, moments, W, x, y - 1, &zm));
-      const bool hp = axis == 0 ? (x + 1 < W && dn_depth(normal, moments, W, x + 1, y, &zp)) : (y + 1 < H && dn_depth(normal, moments, W, x, y + 1, &zp));
+      const bool hm = axis == 0 ? (x > 0 && dn_depth(normal, moments, pitch, x - 1, y, &zm)) : (y > 0 && dn_depth(normal, moments, pitch, x, y - 1, &zm));
+      const bool hp = axis == 0 ? (x + 1 < W && dn_depth(normal, moments, pitch, x + 1, y, &zp)) : (y + 1 < H && dn_depth(normal, moments, pitch, x, y + 1, &zp));
       g[axis] = hm && hp ? fabsf(zp - zm) * 0.5f : hp ? fabsf(zp - z) : hm ? fabsf(z - zm) : 0.0f;
     }
     gz = fmaxf(g[0], g[1]);
@@ -98,24 +101,34 @@ PT_HD void dn_prep_pixel(const vec4* acc, const vec4* albedo, const vec4* normal
   col[p] = valid ? vec4{I.x, I.y, I.z, v} : vec4{0.0f, 0.0f, 0.0f, -1.0f};
   aux[p] = vec4{am.x, am.y, am.z, gz};
 }
+PT_HD void dn_prep_pixel(const vec4* acc, const vec4* albedo, const vec4* normal, const vec4* moments, uint32_t W, uint32_t H,
+                         uint32_t x, uint32_t y, float N, vec4* guide, vec4* col, vec4* aux) {
+  dn_prep_pixel(acc, albedo, normal, moments, W, H, W, x, y, N, guide, col, aux);
+}
 
 // The prep of an adaptive render: N = the pixel's own sample count, that of its 8x8 tile (tile_n[tile_of_pixel]);
 // otherwise dn_prep_pixel's arithmetic, unchanged.
+// (x0, y0): where the image's first pixel lies in the frame the tiles are cut from, `pitch` that frame's width (a render region).
+PT_HD void dn_prep_pixel_counts(const vec4* acc, const vec4* albedo, const vec4* normal, const vec4* moments, uint32_t W, uint32_t H,
+                                uint32_t pitch, uint32_t x0, uint32_t y0, uint32_t x, uint32_t y, const uint32_t* tile_n, vec4* guide,
+                                vec4* col, vec4* aux) {
+  const float N = (float)tile_n[tile_of_pixel(x0 + x, y0 + y, pitch)];
+  dn_prep_pixel(acc, albedo, normal, moments, W, H, pitch, x, y, N, guide, col, aux);
+}
 PT_HD void dn_prep_pixel_counts(const vec4* acc, const vec4* albedo, const vec4* normal, const vec4* moments, uint32_t W, uint32_t H,
                                 uint32_t x, uint32_t y, const uint32_t* tile_n, vec4* guide, vec4* col, vec4* aux) {
-  const float N = (float)tile_n[tile_of_pixel(x, y, W)];
-  dn_prep_pixel(acc, albedo, normal, moments, W, H, x, y, N, guide, col, aux);
+  dn_prep_pixel_counts(acc, albedo, normal, moments, W, H, W, 0u, 0u, x, y, tile_n, guide, col, aux);
 }
 
 // 3x3 binomial blur of v at (x, y) over the valid pixels of the centre's class, normalised by the weights used
-PT_HD float dn_blur_variance(const vec4* guide, const vec4* col, const DenoiseParams& P, uint32_t x, uint32_t y, bool geo) {
+PT_HD float dn_blur_variance(const vec4* guide, const vec4* col, const DenoiseParams& P, uint32_t pitch, uint32_t x, uint32_t y, bool geo) {
   const float k3[3] = {0.25f, 0.5f, 0.25f};
   float sw = 0.0f, sv = 0.0f;
   for (int dy = -1; dy <= 1; dy++)
     for (int dx = -1; dx <= 1; dx++) {
       const int qx = (int)x + dx, qy = (int)y + dy;
       if (qx < 0 || qy < 0 || qx >= (int)P.W || qy >= (int)P.H) continue;
-      const size_t q = (size_t)qy * P.W + (uint32_t)qx;
+      const size_t q = (size_t)qy * pitch + (uint32_t)qx;
       const float vq = col[q].w;
       if (!(vq >= 0.0f) || (guide[q].w >= 0.0f) != geo) continue;
       const float w = k3[dx + 1] * k3[dy + 1];
@@ -128,8 +141,8 @@ PT_HD float dn_blur_variance(const vec4* guide, const vec4* col, const DenoisePa
 // One a-trous step at pixel (x, y) with step `s`.  `last`: remodulate, out[p] = colour (alpha 1); `acc` supplies the value of a pixel
 // that is not a tap.  Otherwise col_out[p] = {I', v'}.
 PT_HD void dn_iterate_pixel(const vec4* guide, const vec4* aux, const vec4* col_in, vec4* col_out, const vec4* acc, vec4* out,
-                            const DenoiseParams& P, uint32_t x, uint32_t y, uint32_t s, bool last) {
-  const size_t p = (size_t)y * P.W + x;
+                            const DenoiseParams& P, uint32_t pitch, uint32_t x, uint32_t y, uint32_t s, bool last) {
+  const size_t p = (size_t)y * pitch + x;
   const vec4 cp = col_in[p];
   if (!(cp.w >= 0.0f)) {  // not finite: keeps its value, never a tap
     if (last) { const vec4 c = acc[p]; out[p] = vec4{c.x, c.y, c.z, 1.0f}; }
@@ -141,7 +154,7 @@ PT_HD void dn_iterate_pixel(const vec4* guide, const vec4* aux, const vec4* col_
   const vec3 np = v3(gp.x, gp.y, gp.z);
   const float gz = aux[p].w;
   const float lp = dn_lum(v3(cp.x, cp.y, cp.z));
-  const float dl = P.sigma_l * sqrtf(dn_blur_variance(guide, col_in, P, x, y, geo)) + kDnEps;
+  const float dl = P.sigma_l * sqrtf(dn_blur_variance(guide, col_in, P, pitch, x, y, geo)) + kDnEps;
   const float k5[5] = {1.0f / 16.0f, 0.25f, 0.375f, 0.25f, 1.0f / 16.0f};
   float sw = 0.0f, sv = 0.0f;
   vec3 sI = v3(0.0f);
@@ -149,7 +162,7 @@ PT_HD void dn_iterate_pixel(const vec4* guide, const vec4* aux, const vec4* col_
     for (int dx = -2; dx <= 2; dx++) {
       const int qx = (int)x + dx * (int)s, qy = (int)y + dy * (int)s;
       if (qx < 0 || qy < 0 || qx >= (int)P.W || qy >= (int)P.H) continue;
-      const size_t q = (size_t)qy * P.W + (uint32_t)qx;
+      const size_t q = (size_t)qy * pitch + (uint32_t)qx;
       const vec4 cq = col_in[q];
       if (!(cq.w >= 0.0f)) continue;
       const vec4 gq = guide[q];
@@ -175,6 +188,10 @@ PT_HD void dn_iterate_pixel(const vec4* guide, const vec4* aux, const vec4* col_
   } else {
     col_out[p] = vec4{I.x, I.y, I.z, v};
   }
+}
+PT_HD void dn_iterate_pixel(const vec4* guide, const vec4* aux, const vec4* col_in, vec4* col_out, const vec4* acc, vec4* out,
+                            const DenoiseParams& P, uint32_t x, uint32_t y, uint32_t s, bool last) {
+  dn_iterate_pixel(guide, aux, col_in, col_out, acc, out, P, P.W, x, y, s, last);
 }
 
 }  // namespace pt

@@ -22,6 +22,21 @@ PT_HD PixelXY tile_pixel(uint32_t tile, uint32_t lane, uint32_t tilesX) {
   return {(tile - ty * tilesX) * 8u + (lane & 7u), ty * 8u + (lane >> 3)};
 }
 
+// A pixel rectangle [x0, x1) x [y0, y1), top-left origin: what a render samples (a render region; the whole frame
+// otherwise).  The kernels that place a virtual tile in the image take it as their validity test.
+struct Rect { uint32_t x0, y0, x1, y1; };
+PT_HD bool rect_contains(const Rect& r, uint32_t x, uint32_t y) { return x >= r.x0 && x < r.x1 && y >= r.y0 && y < r.y1; }
+// The image tiles a non-empty rectangle inside a W-wide image touches, ascending: rows of tiles [y0 / 8, (y1 - 1) / 8], in each the tiles
+// [x0 / 8, (x1 - 1) / 8].  Writes the first `capacity` of them to `out` (may be null) and returns their number.
+PT_HD uint32_t rect_tiles(const Rect& r, uint32_t W, uint32_t* out, uint32_t capacity) {
+  const uint32_t tilesX = tiles_x(W), tx0 = r.x0 >> 3, tx1 = (r.x1 - 1u) >> 3, ty0 = r.y0 >> 3, ty1 = (r.y1 - 1u) >> 3;
+  uint32_t n = 0;
+  for (uint32_t ty = ty0; ty <= ty1; ty++)
+    for (uint32_t tx = tx0; tx <= tx1; tx++, n++)
+      if (out && n < capacity) out[n] = ty * tilesX + tx;
+  return n;
+}
+
 // ---- the per-sample radiance buffer Lbuf -----------------------------------------------------------------------------
 // One vec4 per (pixel, sample in flight), laid out TILE-major: the entries of one 8x8 tile under all samples are contiguous (128 KB at 128
 // samples in flight) and a segment's rays all belong to its tile(s): the shadow kernel's read-modify-writes of a segment stay inside that

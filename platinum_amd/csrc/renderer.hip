@@ -75,13 +75,14 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
     }
   }
 #endif
-  // an adaptive render's batch covers the active tiles only: the three kernels that place a tile in the image read the current list
-  const bool ad = mode == BATCH_RENDER && r->adaptive;
+  // an adaptive or region render's batch covers the active tiles only: the three kernels that place a tile in the image read the current
+  // list, and take the render's rectangle as their validity test
+  const bool ad = mode == BATCH_RENDER && r->vtiles;
   const uint32_t* ad_list = ad ? r->ad_list[r->ad_cur].p : nullptr;
   const uint32_t* ad_count = ad ? r->ad_count.p + r->ad_cur : nullptr;
   {
     ScopedTimer t(r, K_RAYGEN);
-    if (ad) launch_raygen_adaptive(s, r->grid, S, r->path_state(0), r->Lbuf.p, seg, first, ns, ad_list, ad_count);
+    if (ad) launch_raygen_adaptive(s, r->grid, S, r->path_state(0), r->Lbuf.p, seg, first, ns, r->rect, ad_list, ad_count);
     else launch_raygen(s, r->grid, S, r->path_state(0), r->Lbuf.p, seg, ctr, first, ns);
     launch_chunk_tables(s, seg, 0, ctr, 0, 0, false);
   }
@@ -119,25 +120,26 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
       // resolve of a batch is observable
       launch_gmon(s, r->acc, r->gmon_buckets_d.p, npix, (f0 + ns - 1) / spb + 1 - r->gmon_bucket_base, r->gmon_cap);
     } else if (ad) {
-      launch_accumulate_adaptive(s, r->acc, r->Lbuf.p, npix, S.width, ns, n0, r->params.nonfinite_policy, ctr, ad_list, ad_count, r->ad_mom.p,
-                                 r->ad_tile_n.p);
+      launch_accumulate_adaptive(s, r->acc, r->Lbuf.p, npix, S.width, ns, n0, r->params.nonfinite_policy, ctr, ad_list, ad_count, r->ad_tiles0,
+                                 r->adaptive ? r->ad_mom.p : nullptr, r->ad_tile_n.p, r->rect);
     } else {
       launch_accumulate(s, r->acc, r->Lbuf.p, npix, S.width, ns, n0, r->params.nonfinite_policy, ctr);
     }
     if (r->aov && ad)
       launch_accumulate_aov_adaptive(s, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * (size_t)npix, r->Abuf.p, r->Lbuf.p, S.width, S.height, ns,
-                                     n0, r->params.nonfinite_policy, ad_list, ad_count);
+                                     n0, r->params.nonfinite_policy, ad_list, ad_count, r->ad_tiles0, r->rect);
     else if (r->aov)
       launch_accumulate_aov(s, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * (size_t)npix, r->Abuf.p, r->Lbuf.p, S.width, S.height, ns, n0,
                             r->params.nonfinite_policy);
   }
   // a batch that ends at a checkpoint (flush_pending never lets one straddle it): test the active tiles, compact the list into the other
   // buffer, and send the new count to pinned host memory
-  if (ad && r->ad_next < r->total && n0 + ns == r->ad_next) {
+  if (ad && r->adaptive && r->ad_next < r->total && n0 + ns == r->ad_next) {
     {
       ScopedTimer t(r, K_ACCUM);
-      PT_HIP(launch_adaptive_check(s, ad_list, ad_count, r->ad_list[r->ad_cur ^ 1].p, r->ad_count.p + (r->ad_cur ^ 1), r->ad_mom.p, S.width, S.height,
-                                   r->ad_next, r->adaptive_opts.threshold, r->ad_flags.p, r->ad_scratch.p, r->ad_scratch.n, r->ad_host_count));
+      PT_HIP(launch_adaptive_check(s, ad_list, ad_count, r->ad_list[r->ad_cur ^ 1].p, r->ad_count.p + (r->ad_cur ^ 1), r->ad_mom.p, S.width, r->rect,
+                                   r->ad_tiles0, r->ad_next, r->adaptive_opts.threshold, r->ad_flags.p, r->ad_scratch.p, r->ad_scratch.n,
+                                   r->ad_host_count));
     }
     PT_HIP(hipEventRecord(r->ad_event, s));
     r->ad_event_valid = true;
@@ -254,6 +256,7 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   pt_default_tonemap_options(&r->tonemap);
   pt_default_denoise_options(&r->denoise);
   pt_default_adaptive_options(&r->adaptive_opts);
+  pt_default_render_region(&r->region_opts);
   r->device = device_ordinal;
   if (const char* e = getenv("PTAMD_REFILL")) r->refill_threshold = (uint32_t)atoi(e);
   if (const char* e = getenv("PTAMD_TILES_PER_SEG")) r->tiles_per_seg_override = (uint32_t)std::max(0, atoi(e));  // tuning knobs
@@ -323,6 +326,15 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
     return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: null scene arrays");
   if (r->adaptive_opts.enabled && (p->flags & PT_FLAG_GMON))
     return fail(PT_ERR_UNSUPPORTED, "pt_start_render: adaptive sampling does not support PT_FLAG_GMON (a bucket would have to be resolved per tile count)");
+  if (r->region_opts.enabled) {
+    const pt_render_region& g = r->region_opts;
+    if (g.x1 > p->width || g.y1 > p->height)
+      return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: the render region [" + std::to_string(g.x0) + ", " + std::to_string(g.x1) + ") x [" +
+                                               std::to_string(g.y0) + ", " + std::to_string(g.y1) + ") does not fit the " +
+                                               std::to_string(p->width) + " x " + std::to_string(p->height) + " image");
+    if (p->flags & PT_FLAG_GMON)
+      return fail(PT_ERR_UNSUPPORTED, "pt_start_render: a render region does not support PT_FLAG_GMON (the GMoN kernels index the radiance buffer by image pixel)");
+  }
   PT_HIP(hipSetDevice(r->device));
   if (r->stream) PT_HIP(hipStreamSynchronize(r->stream));
   r->drop_timed();
@@ -500,7 +512,10 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   const bool aov = r->denoise.enabled != 0;
   if (!aov) { r->Abuf.release(); r->aov_img.release(); }  // (an AOV-off render holds nothing more than before)
   const bool adaptive = r->adaptive_opts.enabled != 0;
-  if (!adaptive) r->release_adaptive();                     // (nor does an adaptive-off render)
+  const bool region = r->region_opts.enabled != 0;
+  if (!adaptive) r->release_checkpoints();                  // (nor does an adaptive-off render;
+  if (!adaptive && !region) r->release_adaptive();          //  a region render keeps the tile lists and counts, which both use)
+  const Rect rect = region ? Rect{r->region_opts.x0, r->region_opts.y0, r->region_opts.x1, r->region_opts.y1} : Rect{0u, 0u, p->width, p->height};
   // Queue segments (kernels.hip): one per 8x8 tile (a few tiles each once the image has more than 32640 of them), each with
   // room for its tiles under all samples in flight; queue_plan.h holds the sizing and every index-width limit.  The producers
   // (raygen, shade) are persistent grids whose waves take segments round-robin; the trace kernels claim chunks from a table,
@@ -564,22 +579,26 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
     PT_HIP(r->aov_img.alloc(3 * npix));
     PT_HIP(hipMemsetAsync(r->aov_img.p, 0, sizeof(vec4) * 3 * npix, r->stream));
   }
-  if (adaptive) {  // every tile starts active: list [0, tiles), count = tiles (adaptive.hip)
+  if (adaptive || region) {  // every tile the rectangle touches starts active (the whole frame: [0, tiles)), ascending (adaptive.hip)
     const uint32_t tiles = tile_count(p->width, p->height);
-    std::vector<uint32_t> iota(tiles);
-    for (uint32_t t = 0; t < tiles; t++) iota[t] = t;
-    PT_HIP(r->ad_list[0].upload(iota));
-    PT_HIP(r->ad_list[1].upload(iota));
-    PT_HIP(r->ad_count.upload(std::vector<uint32_t>{tiles, tiles}));
+    std::vector<uint32_t> first(rect_tiles(rect, p->width, nullptr, 0));
+    (void)rect_tiles(rect, p->width, first.data(), (uint32_t)first.size());
+    const uint32_t active = (uint32_t)first.size();
+    r->ad_tiles0 = active;
+    PT_HIP(r->ad_list[0].upload(first));
+    PT_HIP(r->ad_list[1].upload(first));
+    PT_HIP(r->ad_count.upload(std::vector<uint32_t>{active, active}));
     PT_HIP(r->ad_tile_n.alloc(tiles));
     PT_HIP(hipMemsetAsync(r->ad_tile_n.p, 0, sizeof(uint32_t) * tiles, r->stream));
-    PT_HIP(r->ad_mom.alloc(npix));
-    PT_HIP(hipMemsetAsync(r->ad_mom.p, 0, sizeof(vec2) * npix, r->stream));
-    PT_HIP(r->ad_flags.alloc(tiles));
-    PT_HIP(r->ad_scratch.alloc(std::max<size_t>(1, adaptive_scratch_bytes(tiles))));
-    if (!r->ad_host_count) PT_HIP(hipHostMalloc((void**)&r->ad_host_count, sizeof(uint32_t), hipHostMallocDefault));
-    if (!r->ad_event) PT_HIP(hipEventCreateWithFlags(&r->ad_event, hipEventDisableTiming));
-    *r->ad_host_count = tiles;
+    if (adaptive) {
+      PT_HIP(r->ad_mom.alloc(npix));
+      PT_HIP(hipMemsetAsync(r->ad_mom.p, 0, sizeof(vec2) * npix, r->stream));
+      PT_HIP(r->ad_flags.alloc(active));
+      PT_HIP(r->ad_scratch.alloc(std::max<size_t>(1, adaptive_scratch_bytes(active))));
+      if (!r->ad_host_count) PT_HIP(hipHostMalloc((void**)&r->ad_host_count, sizeof(uint32_t), hipHostMallocDefault));
+      if (!r->ad_event) PT_HIP(hipEventCreateWithFlags(&r->ad_event, hipEventDisableTiming));
+      *r->ad_host_count = active;
+    }
   }
   PT_HIP(hipMemsetAsync(r->totals.p, 0, sizeof(Totals), r->stream));
   PT_HIP(hipStreamSynchronize(r->stream));
@@ -594,6 +613,9 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   r->total = p->spp;
   r->aov = aov;
   r->adaptive = adaptive;
+  r->region = region;
+  r->vtiles = adaptive || region;
+  r->rect = rect;
   r->ad_cur = 0;
   r->ad_event_valid = false;
   r->ad_next = r->adaptive_opts.min_spp;   // the first checkpoint (none when min_spp >= spp)
@@ -829,6 +851,7 @@ int enqueue_denoise(pt_renderer* r) {
   { const int rc = flush_pending(r, true); if (rc != PT_OK) return rc; }
   const size_t npix = (size_t)r->S.width * r->S.height;
   PT_HIP(r->denoised.alloc(npix));
+  if (r->region) PT_HIP(hipMemsetAsync(r->denoised.p, 0, sizeof(vec4) * npix, r->stream));   // the filter writes the region only
   if (r->denoise.iterations) {
     PT_HIP(r->dn_guide.alloc(npix)); PT_HIP(r->dn_aux.alloc(npix));
     PT_HIP(r->dn_col[0].alloc(npix)); PT_HIP(r->dn_col[1].alloc(npix));
@@ -838,7 +861,8 @@ int enqueue_denoise(pt_renderer* r) {
   P.sigma_l = r->denoise.sigma_luminance; P.sigma_n = r->denoise.sigma_normal; P.sigma_z = r->denoise.sigma_depth;
   launch_denoise(r->stream, r->acc, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * npix, P.W, P.H, (uint32_t)r->launched, P,
                  r->denoise.iterations, r->dn_guide.p, r->dn_aux.p, r->dn_col[0].p, r->dn_col[1].p, r->denoised.p,
-                 r->adaptive ? r->ad_tile_n.p : nullptr);   // an adaptive render: each pixel's own sample count
+                 r->adaptive ? r->ad_tile_n.p : nullptr,   // an adaptive render: each pixel's own sample count
+                 r->rect);                                   // a region render: the region as an image of its own
   PT_HIP(hipGetLastError());
   return PT_OK;
 }
@@ -891,14 +915,44 @@ int dev_read_sample_counts(pt_renderer* r, uint32_t* out) {
   int rc = dev_wait(r);
   if (rc != PT_OK) return rc;
   const uint32_t W = r->S.width, H = r->S.height;
-  if (!r->adaptive) {
+  if (!r->vtiles) {
     std::fill(out, out + (size_t)W * H, (uint32_t)r->launched);
     return PT_OK;
   }
+  // per tile; a region render without adaptive sampling folds every batch into every tile of its list: the same numbers.  Pixels outside the
+  // render's rectangle hold no sample.
   std::vector<uint32_t> tn(r->ad_tile_n.n);
   PT_HIP(hipMemcpy(tn.data(), r->ad_tile_n.p, sizeof(uint32_t) * tn.size(), hipMemcpyDeviceToHost));
   for (uint32_t y = 0; y < H; y++)
-    for (uint32_t x = 0; x < W; x++) out[(size_t)y * W + x] = tn[tile_of_pixel(x, y, W)];
+    for (uint32_t x = 0; x < W; x++) out[(size_t)y * W + x] = rect_contains(r->rect, x, y) ? tn[tile_of_pixel(x, y, W)] : 0u;
+  return PT_OK;
+}
+
+extern "C" void pt_default_render_region(pt_render_region* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+}
+
+// (the options are checked before the renderer, as dev_set_adaptive_options)
+int dev_set_render_region(pt_renderer* r, const pt_render_region* o) {
+  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (o->enabled && (o->x0 >= o->x1 || o->y0 >= o->y1))
+    return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_render_region: the region is empty (x0 < x1 and y0 < y1 are required)");
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_render_region: null renderer");
+  r->region_opts = *o;
+  return PT_OK;
+}
+
+extern "C" int pt_region_tiles(uint32_t width, uint32_t height, const pt_render_region* o, uint32_t* tiles_out, uint32_t capacity, uint32_t* count) {
+  if (!o || !count || (capacity && !tiles_out)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_region_tiles: null argument");
+  if (width == 0 || height == 0) return fail(PT_ERR_INVALID_ARGUMENT, "pt_region_tiles: empty image");
+  Rect rect{0u, 0u, width, height};
+  if (o->enabled) {
+    if (o->x0 >= o->x1 || o->y0 >= o->y1) return fail(PT_ERR_INVALID_ARGUMENT, "pt_region_tiles: the region is empty");
+    if (o->x1 > width || o->y1 > height) return fail(PT_ERR_INVALID_ARGUMENT, "pt_region_tiles: the region does not fit the image");
+    rect = Rect{o->x0, o->y0, o->x1, o->y1};
+  }
+  *count = rect_tiles(rect, width, tiles_out, capacity);
   return PT_OK;
 }
 

@@ -143,6 +143,14 @@ struct pt_renderer {
   bool ad_event_valid = false;
   int ad_cur = 0;
   uint32_t ad_next = 0;                  // the next checkpoint's sample count (>= total: none left)
+  // render region: a render started with region_opts.enabled samples the pixels of `rect` only.  It runs through the
+  // virtual-tile path of adaptive sampling (`vtiles`): the first active list holds the tiles the rectangle touches, and without adaptive
+  // sampling it never changes.  ad_list / ad_count / ad_tile_n serve both; ad_mom / ad_flags / ad_scratch only an adaptive render.
+  pt_render_region region_opts{};
+  bool region = false;              // this render samples a region
+  bool vtiles = false;              // adaptive || region: batches address virtual tiles through ad_list
+  Rect rect{};                      // what this render samples: the region, or the whole frame
+  uint32_t ad_tiles0 = 0;           // length of the first active list: the lists' capacity, the most tiles a batch can cover
   uint32_t closest_grid = 0, shadow_grid = 0, closest_blocks_per_cu = PT_CLOSEST_WAVES, shadow_blocks_per_cu = PT_SHADOW_WAVES;  // persistent trace grids, each sized for its kernel's occupancy
   uint32_t last_batch_ns = 0, last_batch_first = 0;  // the batch Lbuf holds ($PTAMD_DEBUG_PIXEL)
   uint32_t nseg = 0, tiles_per_seg = 1, seg_bands = 4, tiles_per_seg_override = 0, nstats = 0, seg_cap = 0, blocks_per_cu = 6, shade_grid = 0, refill_threshold = 48;
@@ -190,6 +198,8 @@ struct pt_renderer {
     started = false;
     aov = false;
     adaptive = false;
+    region = false;
+    vtiles = false;
     ad_event_valid = false;
     last_batch_ns = 0;
   }
@@ -212,8 +222,11 @@ struct pt_renderer {
     release_adaptive();
   }
   void release_adaptive() {
-    ad_list[0].release(); ad_list[1].release(); ad_count.release(); ad_tile_n.release(); ad_mom.release(); ad_flags.release(); ad_scratch.release();
+    release_checkpoints();
+    ad_list[0].release(); ad_list[1].release(); ad_count.release(); ad_tile_n.release();
   }
+  // what only the checkpoints of adaptive sampling use (a region render without adaptive sampling holds the lists and counts alone)
+  void release_checkpoints() { ad_mom.release(); ad_flags.release(); ad_scratch.release(); }
   void drop_timed() {
     for (auto& t : timed) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
     timed.clear();
@@ -252,3 +265,4 @@ int dev_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out);
 int dev_read_denoised(pt_renderer* r, float* rgba_out);
 int dev_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o);
 int dev_read_sample_counts(pt_renderer* r, uint32_t* out);
+int dev_set_render_region(pt_renderer* r, const pt_render_region* o);

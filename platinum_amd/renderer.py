@@ -194,6 +194,29 @@ class Renderer:
         abi.check(self._lib, self._lib.pt_read_sample_counts(self._h, out.ctypes.data))
         return out
 
+    # render regions (include/ptamd.h, an additive extension of ABI 5): no reference counterpart
+    def renderRegion(self):
+        """The region in effect (pt_default_render_region, the whole frame, until setRenderRegion is called)."""
+        if getattr(self, "_region", None) is None:
+            self._region = abi.RenderRegion()
+            self._lib.pt_default_render_region(C.byref(self._region))
+        o = abi.RenderRegion()
+        C.memmove(C.byref(o), C.byref(self._region), C.sizeof(o))
+        return o
+
+    def setRenderRegion(self, x0, y0, x1, y1):
+        """The next startRender samples only the pixels [x0, x1) x [y0, y1) (top-left origin)."""
+        o = abi.RenderRegion(1, x0, y0, x1, y1)
+        abi.check(self._lib, self._lib.pt_set_render_region(self._h, C.byref(o)))
+        self._region = o
+
+    def clearRenderRegion(self):
+        """The next startRender samples the whole frame again."""
+        o = abi.RenderRegion()
+        self._lib.pt_default_render_region(C.byref(o))
+        abi.check(self._lib, self._lib.pt_set_render_region(self._h, C.byref(o)))
+        self._region = o
+
     def setGmonOptions(self, cap=1.0):
         """gmonOptions().cap (renderer_pt.hpp:71)."""
         o = abi.GmonOptions(cap)

@@ -1,0 +1,229 @@
+"""CPU: render regions: the pt_render_region ABI and its validation, pt_region_tiles against a numpy enumeration, the
+host-only region reference (region_lib.reference_region_render) against the host's uniform renders and against the full-frame adaptive
+reference, the C++ header's accessors, and the resource budgets of the kernels that took the rectangle predicate, a pitch or an origin."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import adaptive_lib as al  # noqa: E402
+import denoise_lib as dl  # noqa: E402
+import region_lib as rl  # noqa: E402
+from platinum_amd import abi  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+# ---- ABI ---------------------------------------------------------------------------------------------------------------------------------
+def test_render_region_abi():
+    layout = rl.region_layout()
+    assert layout[0] == C.sizeof(abi.RenderRegion) == 20
+    for name, off in zip(("enabled", "x0", "y0", "x1", "y1"), layout[1:]):
+        assert getattr(abi.RenderRegion, name).offset == off, name
+    assert layout[1:] == [0, 4, 8, 12, 16]
+    lib = abi.load_library()
+    o = abi.RenderRegion(7, 7, 7, 7, 7)
+    lib.pt_default_render_region(C.byref(o))
+    assert (o.enabled, o.x0, o.y0, o.x1, o.y1) == (0, 0, 0, 0, 0)
+    assert abi.PT_ABI_VERSION == 5
+    # validation runs before the renderer is looked at: with a null renderer, valid options get as far as "null renderer"
+    assert lib.pt_set_render_region(None, C.byref(o)) == -1 and b"null renderer" in lib.pt_last_error()
+    ok = abi.RenderRegion(1, 5, 3, 45, 30)
+    assert lib.pt_set_render_region(None, C.byref(ok)) == -1 and b"null renderer" in lib.pt_last_error()
+    for rect in ((5, 3, 5, 30), (6, 3, 5, 30), (5, 3, 45, 3), (5, 30, 45, 3), (0, 0, 0, 0)):
+        bad = abi.RenderRegion(1, *rect)
+        assert lib.pt_set_render_region(None, C.byref(bad)) == -1, rect
+        assert b"empty" in lib.pt_last_error() and b"null renderer" not in lib.pt_last_error(), (rect, lib.pt_last_error())
+        # a disabled region is not looked at
+        off = abi.RenderRegion(0, *rect)
+        assert lib.pt_set_render_region(None, C.byref(off)) == -1 and b"null renderer" in lib.pt_last_error(), rect
+    assert lib.pt_set_render_region(None, None) == -1
+
+
+# ---- pt_region_tiles ---------------------------------------------------------------------------------------------------------------------
+def _region_tiles(W, H, rect, capacity=None, enabled=1):
+    lib = abi.load_library()
+    o = abi.RenderRegion(enabled, *rect)
+    n = C.c_uint32(0xFFFFFFFF)
+    if capacity is None:
+        abi.check(lib, lib.pt_region_tiles(W, H, C.byref(o), None, 0, C.byref(n)))
+        capacity = n.value
+    out = np.full(capacity + 3, 0xDEADBEEF, np.uint32)
+    abi.check(lib, lib.pt_region_tiles(W, H, C.byref(o), out.ctypes.data, capacity, C.byref(n)))
+    assert (out[capacity:] == 0xDEADBEEF).all()          # nothing past the capacity is written
+    return out[:min(capacity, n.value)], n.value
+
+
+def _rects(W, H):
+    return {
+        "aligned": (8, 8, 40, 32),
+        "unaligned": (5, 3, 45, 30),
+        "corner pixel": (W - 1, H - 1, W, H),            # a single pixel in the partial corner tile
+        "column": (31, 0, 32, H),
+        "row": (0, H // 2, W, H // 2 + 1),
+        "ends on a tile edge": (3, 5, 48, 40),
+        "full": (0, 0, W, H),
+    }
+
+
+@pytest.mark.parametrize("W,H", [(71, 45), (67, 45), (2051, 1029)])
+def test_region_tiles_match_a_numpy_enumeration(W, H):
+    assert W % 8 and H % 8
+    for what, rect in _rects(W, H).items():
+        want = rl.np_region_tiles(W, H, rect)
+        got, n = _region_tiles(W, H, rect)
+        assert n == want.size and np.array_equal(got, want), (what, rect)
+        assert (np.diff(got.astype(np.int64)) > 0).all(), what
+        # the kernels' validity test built for the host marks exactly the rectangle
+        if W < 100:
+            assert np.array_equal(rl.host_mask(W, H, rect), rl.mask(W, H, rect)), what
+        # an undersized capacity: the first tiles, and the whole number
+        for cap in sorted({0, 1, want.size // 2, max(want.size - 1, 0)}):
+            part, n2 = _region_tiles(W, H, rect, capacity=cap)
+            assert n2 == want.size and np.array_equal(part, want[:cap]), (what, cap)
+    tiles = ((W + 7) // 8) * ((H + 7) // 8)
+    got, n = _region_tiles(W, H, (0, 0, W, H))
+    assert n == tiles and np.array_equal(got, np.arange(tiles))
+    # a disabled region is the whole frame whatever its fields say
+    got, n = _region_tiles(W, H, (5, 3, 4, 2), enabled=0)
+    assert n == tiles and np.array_equal(got, np.arange(tiles))
+    assert _region_tiles(W, H, (W - 1, H - 1, W, H))[0].tolist() == [tiles - 1]
+
+
+def test_region_tiles_validation():
+    lib = abi.load_library()
+    n = C.c_uint32()
+    buf = np.zeros(4, np.uint32)
+    for W, H, rect in ((67, 45, (5, 3, 68, 30)), (67, 45, (5, 3, 45, 46)), (67, 45, (5, 3, 5, 30)), (0, 45, (0, 0, 1, 1)), (67, 0, (0, 0, 1, 1))):
+        o = abi.RenderRegion(1, *rect)
+        assert lib.pt_region_tiles(W, H, C.byref(o), buf.ctypes.data, 4, C.byref(n)) == -1, (W, H, rect)
+    o = abi.RenderRegion(1, 0, 0, 8, 8)
+    assert lib.pt_region_tiles(67, 45, None, buf.ctypes.data, 4, C.byref(n)) == -1
+    assert lib.pt_region_tiles(67, 45, C.byref(o), buf.ctypes.data, 4, None) == -1
+    assert lib.pt_region_tiles(67, 45, C.byref(o), None, 4, C.byref(n)) == -1
+
+
+# ---- the region reference ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["cornell67", "textured99"])
+def test_region_reference(name):
+    """The reference of an adaptive region render: populated count classes, border tiles that stop earlier than in the full-frame adaptive
+    render (their pixels outside the rectangle no longer vote), zeros outside, and per count class the host's uniform render of that count."""
+    kind, (W, H), _B, spp, m, i, _thr, _policy = al.config(name)
+    rect = rl.REGIONS[name]
+    x0, y0, x1, y1 = rect
+    assert (x0 % 8 or y0 % 8) and (x1 % 8 or y1 % 8) and x1 <= W and y1 <= H
+    ref = rl.reference_region_render(name)
+    full = al.reference(name)
+    inside = rl.mask(W, H, rect)
+    tiles = rl.tile_count_map(W, H, rect, ref["counts"])
+    assert sorted(ty * ((W + 7) // 8) + tx for ty, tx in tiles) == rl.np_region_tiles(W, H, rect).tolist()
+    classes = sorted(set(tiles.values()))
+    assert len(classes) >= 5 and classes[-1] == spp and set(classes) <= set(al.checkpoints(spp, m, i)) | {spp}, classes
+    # border tiles: partly inside the rectangle
+    slices = rl.tile_slices(W, H, rect)
+    border = [k for k, (sy, sx) in slices.items()
+              if (sy.stop - sy.start, sx.stop - sx.start) != (min(8, H - k[0] * 8), min(8, W - k[1] * 8))]
+    full_tc = al.tile_counts(full["counts"])
+    earlier = [k for k in border if tiles[k] < full_tc[k]]
+    assert len(earlier) >= 1, (border, tiles)
+    # a tile that lies inside the rectangle whole is judged as in the full-frame render; no tile of the region stops later than there
+    for k, n in tiles.items():
+        assert n <= full_tc[k] and (k in border or n == full_tc[k]), (k, n, full_tc[k])
+    print("%s %s: %d tiles, count classes %s, %d of %d border tiles stop earlier than in the full-frame render" % (
+        name, rect, len(tiles), classes, len(earlier), len(border)))
+    # outside: all-zero bits, alpha included, no samples
+    for key in ("acc", "albedo", "normal", "moments"):
+        assert not _bits(ref[key])[~inside].any(), key
+    assert not ref["counts"][~inside].any() and (ref["counts"][inside] >= m).all()
+    assert ref["paths"] == sum(n * (sy.stop - sy.start) * (sx.stop - sx.start) for (n, (sy, sx)) in ((tiles[k], slices[k]) for k in tiles))
+    # per count class: the rectangle's pixels of that count equal the uniform render of that many samples
+    hs = dl.HostScene(al.config_scene(kind), al.config_params(name))
+    for n in classes:
+        uni = hs.render(0, n)
+        sel = inside & (ref["counts"] == n)
+        assert sel.any()
+        for key, u in zip(("acc", "albedo", "normal", "moments"), uni):
+            assert np.array_equal(_bits(ref[key])[sel], _bits(u)[sel]), (n, key)
+
+
+def test_region_reference_of_the_whole_frame_is_the_adaptive_reference():
+    name = "cornell67"
+    _kind, (W, H), *_ = al.config(name)
+    ref, full = rl.reference_region_render(name, (0, 0, W, H)), al.reference(name)
+    assert np.array_equal(ref["counts"], full["counts"])
+    for key in ("acc", "albedo", "normal", "moments"):
+        assert np.array_equal(_bits(ref[key]), _bits(full[key])), key
+
+
+# ---- above the ABI -----------------------------------------------------------------------------------------------------------------------
+def test_cpp_header_has_the_region_accessors(tmp_path):
+    tu = tmp_path / "region_accessors.cpp"
+    tu.write_text('#include "ptamd_renderer.hpp"\n'
+                  "int main() {\n"
+                  "  ptamd::renderer_pt::Renderer* r = nullptr;\n"
+                  "  if (r) {\n"
+                  "    r->setRenderRegion(5, 3, 45, 30);\n"
+                  "    pt_render_region& g = r->renderRegion();\n"
+                  "    g.enabled = 0;\n"
+                  "    pt_render_region o;\n"
+                  "    pt_default_render_region(&o);\n"
+                  "    r->setRenderRegion(o);\n"
+                  "    uint32_t n = 0;\n"
+                  "    (void)pt_region_tiles(67, 45, &o, nullptr, 0, &n);\n"
+                  "  }\n"
+                  "  static_assert(sizeof(pt_render_region) == 20, \"pt_render_region\");\n"
+                  "  return 0;\n"
+                  "}\n")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(tu)])
+
+
+def test_python_wrapper_has_the_region_accessors():
+    from platinum_amd.renderer import Renderer
+    for member in ("renderRegion", "setRenderRegion", "clearRenderRegion"):
+        assert callable(getattr(Renderer, member)), member
+
+
+# ---- kernel budgets ----------------------------------------------------------------------------------------------------------------------
+# kernel -> (max VGPRs, min waves per SIMD, max LDS bytes): the kernels that took the rectangle predicate, a row pitch or an origin.  The
+# virtual-tile kernels mirror the full-frame kernels and stay inside their budgets (tests/test_kernel_resources.py BUDGET for the first two;
+# k_accumulate_aov's own resource line, 150 VGPRs at 2 waves per SIMD with its 27 KB of staging, for the third).  The filter kernels and the
+# checkpoint are launched with 256 threads and no LDS and were built for full occupancy: 64 VGPRs is what 8 waves per SIMD leave a lane.
+REGION_BUDGET = {
+    "k_accumulate_aov_adaptive": (150, 2, 27 * 1024),
+    "k_adaptive_check": (64, 8, 0),
+    "k_dn_prep": (64, 8, 0),
+    "k_dn_prep_counts": (64, 8, 0),
+    "k_atrous": (64, 8, 0),
+    "k_dn_copy": (64, 8, 0),
+}
+
+
+def test_region_kernels_stay_inside_the_budgets_of_the_kernels_they_mirror():
+    from test_kernel_resources import BUDGET
+    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh")], capture_output=True, text=True, timeout=600).stdout
+    lines = {}
+    for line in out.splitlines():
+        mt = re.match(r"(.+?) VGPRs (\d+) scratch (\d+) spill (\d+) occ (\d+) LDS (\d+)", line.strip())
+        if mt:
+            lines[mt.group(1)] = (line.strip(), tuple(int(x) for x in mt.groups()[1:]))
+    budgets = {"k_raygen_adaptive": BUDGET["k_raygen"], "k_accumulate_adaptive": BUDGET["k_accumulate"]}
+    budgets.update({k: (v, 0, occ, lds) for k, (v, occ, lds) in REGION_BUDGET.items()})
+    for name, (vgpr, scratch, occ, lds) in budgets.items():
+        assert name in lines, (name, sorted(lines))
+        v, s, spill, o, l = lines[name][1]
+        assert v <= vgpr and s <= scratch == 0 and spill == 0 and o >= occ and l <= lds, lines[name][0]
+    # k_accumulate_aov is the kernel k_accumulate_aov_adaptive mirrors: the budget above is its own line
+    v, s, spill, o, l = lines["k_accumulate_aov"][1]
+    assert (v, s, spill, o) == (150, 0, 0, 2) and l <= 27 * 1024, lines["k_accumulate_aov"][0]
+    # a render without a region and without adaptive sampling launches the kernels it launched before, as they were
+    assert lines["k_raygen"][0] == "k_raygen VGPRs 48 scratch 0 spill 0 occ 8 LDS 0"
+    assert lines["k_accumulate"][0] == "k_accumulate VGPRs 54 scratch 0 spill 0 occ 4 LDS 36864"

@@ -6,6 +6,7 @@ tracing (GMoN optional), fused post-process + tonemap — to an 8-bit PNG.
     python tools/render_scene.py tests/golden/scene_fixture/mini.json out.png --size 640 360 --spp 64
     python tools/render_scene.py model.glb out.png --camera-pos 0 1.5 6 --camera-target 0 1 0 --env sky
     python tools/render_scene.py builtin:c5 out.png --size 960 540 --spp 32 --bounces 12
+    python tools/render_scene.py builtin:c3 corner.png --size 1920 1080 --spp 4096 --region 1200,600,1500,800
 """
 import argparse, os, struct, sys, time, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -35,7 +36,19 @@ def main():
     ap.add_argument("--denoise", action="store_true", help="keep first-hit AOVs and write the image through the a-trous denoiser")
     ap.add_argument("--adaptive", type=float, default=None, metavar="THRESHOLD",
                     help="tile-adaptive sampling: an 8x8 tile stops once every pixel's relative error is <= THRESHOLD (--spp is the maximum)")
+    ap.add_argument("--region", default=None, metavar="X0,Y0,X1,Y1",
+                    help="render region: sample only the pixels [X0, X1) x [Y0, Y1) (top-left origin); the rest of the image stays empty (alpha 0)")
     a = ap.parse_args()
+    region = None
+    if a.region is not None:
+        try:
+            region = tuple(int(v) for v in a.region.split(","))
+        except ValueError:
+            region = ()
+        if len(region) != 4 or min(region) < 0 or region[0] >= region[2] or region[1] >= region[3] or region[2] > a.size[0] or region[3] > a.size[1]:
+            ap.error("--region takes X0,Y0,X1,Y1 with 0 <= X0 < X1 <= width and 0 <= Y0 < Y1 <= height")
+        if a.gmon > 1:
+            ap.error("--region does not combine with --gmon")
     t0 = time.time()
     if a.scene.startswith("builtin:"):
         factory, *_ = scenes.CONFIGS[a.scene.split(":", 1)[1]]
@@ -57,6 +70,8 @@ def main():
         if a.gmon > 1:
             ap.error("--adaptive does not combine with --gmon")
         r.setAdaptiveOptions(enabled=1, threshold=a.adaptive)
+    if region is not None:
+        r.setRenderRegion(*region)
     flags = abi.FLAG_MULTISCATTER_GGX | (abi.FLAG_GMON if a.gmon > 1 else 0)
     r.startRender(sc, tuple(a.size), a.spp, gmonBuckets=max(1, a.gmon), flags=flags, max_bounces=a.bounces, nonfinite_policy=abi.NONFINITE_ZERO)
     t1 = time.time()
@@ -70,7 +85,12 @@ def main():
     print(f"setup {t1 - t0:.2f} s (BVH {st.bvh_build_ms:.1f} ms), render {t2 - t1:.3f} s = {a.size[0] * a.size[1] * a.spp * a.bounces / (t2 - t1) / 1e6:.0f} Msamples/s, wrote {a.output}")
     if a.adaptive is not None:
         n = r.readbackSampleCounts()
-        print(f"adaptive: {st.paths} paths = {st.paths / (a.size[0] * a.size[1] * a.spp):.3f} of uniform, per-pixel samples {n.min()}..{n.max()}, mean {n.mean():.1f}")
+        if region is not None:
+            n = n[region[1]:region[3], region[0]:region[2]]
+        print(f"adaptive: {st.paths} paths = {st.paths / (n.size * a.spp):.3f} of uniform, per-pixel samples {n.min()}..{n.max()}, mean {n.mean():.1f}")
+    if region is not None:
+        area = (region[2] - region[0]) * (region[3] - region[1])
+        print(f"region: {area} of {a.size[0] * a.size[1]} pixels; {st.paths} paths = {st.paths / (a.size[0] * a.size[1] * a.spp):.4f} of the full frame's {a.size[0] * a.size[1] * a.spp}")
 
 
 if __name__ == "__main__":
