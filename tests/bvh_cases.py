@@ -1,0 +1,44 @@
+"""The cases tests/test_gpu_bvh_builder.py renders (tests/test_bvh_layouts_host.py checks the oracle's slot coverage of each of them) and the
+brute-force references they share within one session — TEST INFRASTRUCTURE.  The scenes themselves: tests/bvh_layouts.py."""
+import bvh_layouts as L
+
+SIZES = (2, 3, 4, 5, 6, 7, 8, 9, 16, 17, 18, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 1026, 1280, 2047, 2048, 2049, 4096, 4097)
+LAYOUT_SIZES = (9, 1024, 1025, 2049)
+PAIRED_SIZES = (2, 1024, 1025)
+VARIANT_SIZES = (2, 5, 257, 1024, 1025, 2049)
+VARIANT_LAYOUTS = ("scatter", "expo", "coincident")
+INSTANCE_SIZES = (2, 3, 1024, 1025)
+LEGACY_SIZES = (2, 1024, 1025, 2049)
+
+
+def layout_cases():
+    """(n, layout, paired) of the layouts test."""
+    c = [(n, lay, False) for lay in L.LAYOUTS for n in LAYOUT_SIZES] + [(4097, "coincident", False)]
+    return c + [(n, "scatter", True) for n in PAIRED_SIZES]
+
+
+def mosaic_cases():
+    """Every (n, layout, paired) some GPU test builds a mosaic for, once each."""
+    c = [(n, "scatter", False) for n in SIZES] + layout_cases() + [(n, lay, False) for lay in VARIANT_LAYOUTS for n in VARIANT_SIZES]
+    return sorted(set(c), key=lambda t: (L.LAYOUTS.index(t[1]), t[2], t[0]))
+
+
+_REFERENCES = {}
+
+
+def reference(n, layout, paired=False, paths=True):
+    """The BRUTE-FORCE oracle's answers for one case, computed once per session and shared by every structure variant that renders the case:
+    {"primary": [records of sample s for s in SAMPLES]; with `paths` also "radiance", "hits": debug_sample(0) at 1 spp, 2 bounces}.  Read-only."""
+    ref = _REFERENCES.setdefault((n, layout, paired), {})
+    todo = ("primary" not in ref, paths and "hits" not in ref)
+    if any(todo):
+        import oracle_lib
+        from platinum_amd.renderer import make_params
+        sc, W, H, _, _ = L.build(n, layout, paired)
+        if todo[0]:
+            ref["primary"] = L.oracle_primary(sc, W, H, False)
+        if todo[1]:
+            ref["radiance"], ref["hits"] = oracle_lib.OracleScene(sc, make_params(W, H, 1, 2), use_bvh=False).debug_sample(0)
+        for a in ref["primary"] + [ref[k] for k in ("radiance", "hits") if k in ref]:
+            a.flags.writeable = False
+    return ref
