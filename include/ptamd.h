@@ -324,7 +324,7 @@ uint64_t pt_render_time_ms(const pt_renderer* r);
 /* Renderer::gmonOptions() (renderer_pt.hpp:71; pt_shader_defs.hpp:164-166 GmonOptions). With PT_FLAG_GMON the samples
  * are accumulated into `gmon_buckets` bucket images (bucket = sample / ceil(spp / buckets), renderer_pt.cpp:124-139)
  * and the accumulator holds their Gini-weighted median-of-means (shaders/gmon.metal), recomputed after every batch. */
-typedef struct pt_gmon_options { float cap; } pt_gmon_options; /* default 1.0 */
+typedef struct pt_gmon_options { float cap; } pt_gmon_options; /* default 1.0; 0 <= cap <= 1, else PT_ERR_INVALID_ARGUMENT */
 int pt_set_gmon_options(pt_renderer* r, const pt_gmon_options* options);
 /* One bucket image (W*H*4 floats), for parity checks. */
 int pt_read_gmon_bucket(pt_renderer* r, uint32_t bucket, float* rgba_out);

@@ -15,7 +15,11 @@ inline float3 mix3(float3 a, float3 b, float t) { return a + (b - a) * t; }
 inline float log2s(float x) { return x > 0.0f ? log2_det(x) : -std::numeric_limits<float>::infinity(); }
 inline float3 log2v(float3 v) { return {log2s(v.x), log2s(v.y), log2s(v.z)}; }
 inline float exp2s(float x) { return x < -125.0f ? 0.0f : (x > 125.0f ? std::numeric_limits<float>::infinity() : exp2_det(x)); }
-inline float3 exp2v(float3 v) { return {exp2_det(v.x), exp2_det(v.y), exp2_det(v.z)}; }
+// exp2_det / powr_det over the whole float range (+inf above, 0 below; in-range arguments unchanged), like pt_post.h's pp_exp2 / pp_powr
+inline float exp2g(float x) { return x >= 128.0f ? std::numeric_limits<float>::infinity() : (x < -127.0f ? 0.0f : exp2_det(x)); }
+inline float powrg(float x, float y) { return x <= 0.0f ? 0.0f : exp2g(y * log2_det(x)); }
+const float ceiling = 18446744073709551616.0f;  // 2^64: what the contrast pass hands on is capped there (pt_post.h kPostCeiling), so that overbright is white, not NaN
+inline float3 exp2v(float3 v) { return {exp2g(v.x), exp2g(v.y), exp2g(v.z)}; }
 inline float3 sat3(float3 v) { return {saturate(v.x), saturate(v.y), saturate(v.z)}; }
 inline float3 vmul(float3 v, const Mat3& m) { return {dot(v, m.c0), dot(v, m.c1), dot(v, m.c2)}; }  // v * M
 
@@ -57,7 +61,7 @@ float3 apply(float3 val, const pt_tonemap_options& o) {
   val = start(val);
   float l = luma(val);
   float3 t = val * f3(o.agx_slope[0], o.agx_slope[1], o.agx_slope[2]) + f3(o.agx_offset[0], o.agx_offset[1], o.agx_offset[2]);
-  t = f3(powr_det(t.x, o.agx_power[0]), powr_det(t.y, o.agx_power[1]), powr_det(t.z, o.agx_power[2]));
+  t = f3(powrg(t.x, o.agx_power[0]), powrg(t.y, o.agx_power[1]), powrg(t.z, o.agx_power[2]));
   val = mix3(f3(l), t, o.agx_saturation);
   return end(val);
 }
@@ -133,10 +137,10 @@ float superSigmoid(float x, float2 toe, float2 shoulder) {
   toe = {saturate(toe.x), saturate(toe.y)};
   shoulder = {saturate(shoulder.x), saturate(shoulder.y)};
   float slope = (shoulder.y - toe.y) / (shoulder.x - toe.x);
-  if (x < toe.x) return toe.y * powr_det(x / toe.x, slope * toe.x / toe.y);
+  if (x < toe.x) return toe.y * powrg(x / toe.x, slope * toe.x / toe.y);
   if (x < shoulder.x) return slope * x + toe.y - (slope * toe.x);
-  float shoulderPow = -slope / ((shoulder.x - 1.0f) / powr_det(1.0f - shoulder.x, 2.0f) * (1.0f - shoulder.y));
-  return (1.0f - powr_det(1.0f - (x - shoulder.x) / (1.0f - shoulder.x), shoulderPow)) * (1.0f - shoulder.y) + shoulder.y;
+  float shoulderPow = -slope / ((shoulder.x - 1.0f) / powrg(1.0f - shoulder.x, 2.0f) * (1.0f - shoulder.y));
+  return (1.0f - powrg(1.0f - (x - shoulder.x) / (1.0f - shoulder.x), shoulderPow)) * (1.0f - shoulder.y) + shoulder.y;
 }
 float dyeMixFactor(float mono, float maxDensity, const pt_tonemap_options& o) {
   float offset = exp2s(o.flim_sigmoid_log2_min);
@@ -221,7 +225,7 @@ float sampleExposed(const float* acc, uint32_t W, uint32_t H, float expScale, fl
   return a + (b - a) * wy;
 }
 
-inline float sRGB_channel(float c) { return c < 0.0031308f ? 12.92f * c : 1.055f * powr_det(c, 1.0f / 2.4f) - 0.055f; }  // :29-32
+inline float sRGB_channel(float c) { return c < 0.0031308f ? 12.92f * c : 1.055f * powrg(c, 1.0f / 2.4f) - 0.055f; }  // :29-32
 
 // exposure -> chromaticAberration -> contrastSaturation -> toneCurve -> vignette -> tonemap for one pixel
 float3 pixel(const float* acc, uint32_t W, uint32_t H, uint32_t px, uint32_t py, const pt_post_options& o, const pt_tonemap_options& t,
@@ -247,7 +251,7 @@ float3 pixel(const float* acc, uint32_t W, uint32_t H, uint32_t px, uint32_t py,
     float3 logColor = log2v(color + f3(eps));
     float3 adj = mix3(f3(0.18f), logColor, 1.0f + o.contrast * 0.01f);
     float3 e = exp2v(adj) - f3(eps);
-    color = f3(fmaxf(0.0f, e.x), fmaxf(0.0f, e.y), fmaxf(0.0f, e.z));
+    color = f3(fminf(fmaxf(e.x, 0.0f), ceiling), fminf(fmaxf(e.y, 0.0f), ceiling), fminf(fmaxf(e.z, 0.0f), ceiling));
     float3 gray = f3(luma(color));
     color = mix3(gray, color, 1.0f + o.saturation * 0.01f);
   }
@@ -271,11 +275,11 @@ float3 pixel(const float* acc, uint32_t W, uint32_t H, uint32_t px, uint32_t py,
     float start = end * (1.0f - o.vig_feather * 0.01f);
     float power = o.vig_power * 0.05f;
     float d = invLerp(distanceNorm, start, end);
-    float vignetting = (d == 0.0f ? 0.0f : powr_det(d, power)) * smoothstep(start, end, distanceNorm);
+    float vignetting = (d == 0.0f ? 0.0f : powrg(d, power)) * smoothstep(start, end, distanceNorm);
     color *= exp2s(o.vig_amount * vignetting);
   }
   switch (t.tonemapper) {  // tonemap, :553-600
-    case 1: { float3 c = agx::apply(color, t); color = f3(powr_det(c.x, 2.2f), powr_det(c.y, 2.2f), powr_det(c.z, 2.2f)); break; }
+    case 1: { float3 c = agx::apply(color, t); color = f3(powrg(c.x, 2.2f), powrg(c.y, 2.2f), powrg(c.z, 2.2f)); break; }
     case 2: color = khronos_apply(color, t); break;
     case 3: color = flim::apply(color, t); break;
     default: break;
@@ -290,7 +294,7 @@ float3 pixel(const float* acc, uint32_t W, uint32_t H, uint32_t px, uint32_t py,
   float3 gain = (f3(1.0f) + gainColor) + f3(t.highlight_offset * 0.01f);
   float3 midGray = (f3(0.5f) + gammaColor) + f3(t.midtone_offset * 0.01f);
   float3 gamma = log2v((f3(0.5f) - lift) / (gain - lift)) / log2v(midGray);  // log10 ratio == log2 ratio
-  float3 tt = sat3(f3(powr_det(color.x, 1.0f / gamma.x), powr_det(color.y, 1.0f / gamma.y), powr_det(color.z, 1.0f / gamma.z)));
+  float3 tt = sat3(f3(powrg(color.x, 1.0f / gamma.x), powrg(color.y, 1.0f / gamma.y), powrg(color.z, 1.0f / gamma.z)));
   color = lift + (gain - lift) * tt;
   color = mul(odt, color);
   return f3(sRGB_channel(color.x), sRGB_channel(color.y), sRGB_channel(color.z));

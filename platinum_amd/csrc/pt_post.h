@@ -26,8 +26,17 @@ PT_HD float pp_smoothstep(float e0, float e1, float x) {
 PT_HD vec3 pp_mix3(vec3 a, vec3 b, float t) { return a + (b - a) * t; }
 PT_HD float pp_log2(float x) { return x > 0.0f ? log2_det(x) : -kInf; }
 PT_HD vec3 pp_log2v(vec3 v) { return {pp_log2(v.x), pp_log2(v.y), pp_log2(v.z)}; }
-PT_HD vec3 pp_exp2v(vec3 v) { return {exp2_det(v.x), exp2_det(v.y), exp2_det(v.z)}; }
-PT_HD vec3 pp_powrv(vec3 v, float p) { return {powr_det(v.x, p), powr_det(v.y, p), powr_det(v.z, p)}; }
+// exp2_det / powr_det over the whole float range: exp2_det builds 2^n as (n + 127) << 23, which is a float only for n in [-127, 128]
+// (n = 128 is already +inf, n = -127 already 0).  Past that the bits run into the sign (x >= 128.5 gave -0) or the cast of a huge
+// float is undefined, where MSL's exp2 / powr overflow to +inf and underflow to 0.  No argument inside the range changes by a bit.
+PT_HD float pp_exp2(float x) { return x >= 128.0f ? kInf : (x < -127.0f ? 0.0f : exp2_det(x)); }
+PT_HD float pp_powr(float x, float y) { return x <= 0.0f ? 0.0f : pp_exp2(y * log2_det(x)); }
+// What the contrast pass hands on is capped at 2^64: an overbright pixel (exp2 above the range, or inf in the accumulator) stays a finite
+// "far above white" instead of +inf, which the blends after it (gray + (color - gray) * t, newPeak / peak, 0 * inf in a dot product) would
+// turn into NaN and the NaN into black.  No later pass can bring 2^64 back below display white with options anywhere near their ranges.
+constexpr float kPostCeiling = 18446744073709551616.0f;
+PT_HD vec3 pp_exp2v(vec3 v) { return {pp_exp2(v.x), pp_exp2(v.y), pp_exp2(v.z)}; }
+PT_HD vec3 pp_powrv(vec3 v, float p) { return {pp_powr(v.x, p), pp_powr(v.y, p), pp_powr(v.z, p)}; }
 PT_HD vec3 pp_saturate3(vec3 v) { return {saturate(v.x), saturate(v.y), saturate(v.z)}; }
 PT_HD vec3 pp_clamp3(vec3 v, float lo, float hi) { return {fminf(fmaxf(v.x, lo), hi), fminf(fmaxf(v.y, lo), hi), fminf(fmaxf(v.z, lo), hi)}; }
 PT_HD float pp_exp2s(float x) { return x < -125.0f ? 0.0f : (x > 125.0f ? kInf : exp2_det(x)); }  // range guard around exp2_det
@@ -77,7 +86,7 @@ PT_HD vec3 agx_apply(vec3 val, const pt_tonemap_options& o) {
   val = agx_start(val);
   const float luma = pp_luma(val);  // applyLook, :131-136
   vec3 t = val * v3(o.agx_slope[0], o.agx_slope[1], o.agx_slope[2]) + v3(o.agx_offset[0], o.agx_offset[1], o.agx_offset[2]);
-  t = v3(powr_det(t.x, o.agx_power[0]), powr_det(t.y, o.agx_power[1]), powr_det(t.z, o.agx_power[2]));
+  t = v3(pp_powr(t.x, o.agx_power[0]), pp_powr(t.y, o.agx_power[1]), pp_powr(t.z, o.agx_power[2]));
   val = pp_mix3(v3(luma), t, o.agx_saturation);
   return agx_end(val);
 }
@@ -154,10 +163,10 @@ PT_HD float flim_superSigmoid(float x, vec2 toe, vec2 shoulder) {
   toe = {saturate(toe.x), saturate(toe.y)};
   shoulder = {saturate(shoulder.x), saturate(shoulder.y)};
   const float slope = (shoulder.y - toe.y) / (shoulder.x - toe.x);
-  if (x < toe.x) return toe.y * powr_det(x / toe.x, slope * toe.x / toe.y);
+  if (x < toe.x) return toe.y * pp_powr(x / toe.x, slope * toe.x / toe.y);
   if (x < shoulder.x) return slope * x + toe.y - (slope * toe.x);
-  const float shoulderPow = -slope / ((shoulder.x - 1.0f) / powr_det(1.0f - shoulder.x, 2.0f) * (1.0f - shoulder.y));
-  return (1.0f - powr_det(1.0f - (x - shoulder.x) / (1.0f - shoulder.x), shoulderPow)) * (1.0f - shoulder.y) + shoulder.y;
+  const float shoulderPow = -slope / ((shoulder.x - 1.0f) / pp_powr(1.0f - shoulder.x, 2.0f) * (1.0f - shoulder.y));
+  return (1.0f - pp_powr(1.0f - (x - shoulder.x) / (1.0f - shoulder.x), shoulderPow)) * (1.0f - shoulder.y) + shoulder.y;
 }
 PT_HD float flim_dyeMixFactor(float mono, float maxDensity, const pt_tonemap_options& o) {
   const float offset = pp_exp2s(o.flim_sigmoid_log2_min);
@@ -277,7 +286,7 @@ PT_HD vec3 postprocess_pixel(const vec4* __restrict__ acc, uint32_t W, uint32_t 
     const vec3 logColor = pp_log2v(color + v3(eps));
     const vec3 adj = pp_mix3(v3(0.18f), logColor, 1.0f + o.contrast * 0.01f);
     const vec3 e = pp_exp2v(adj) - v3(eps);
-    color = v3(fmaxf(0.0f, e.x), fmaxf(0.0f, e.y), fmaxf(0.0f, e.z));
+    color = pp_clamp3(e, 0.0f, kPostCeiling);
     const vec3 gray = v3(pp_luma(color));
     color = pp_mix3(gray, color, 1.0f + o.saturation * 0.01f);
   }
@@ -301,7 +310,7 @@ PT_HD vec3 postprocess_pixel(const vec4* __restrict__ acc, uint32_t W, uint32_t 
     const float start = end * (1.0f - o.vig_feather * 0.01f);
     const float power = o.vig_power * 0.05f;
     const float d = pp_invLerp(distanceNorm, start, end);
-    const float vignetting = (d == 0.0f ? 0.0f : powr_det(d, power)) * pp_smoothstep(start, end, distanceNorm);
+    const float vignetting = (d == 0.0f ? 0.0f : pp_powr(d, power)) * pp_smoothstep(start, end, distanceNorm);
     color = color * pp_exp2s(o.vig_amount * vignetting);
   }
   // tonemap, :553-600
@@ -324,10 +333,10 @@ PT_HD vec3 postprocess_pixel(const vec4* __restrict__ acc, uint32_t W, uint32_t 
   const vec3 num = pp_log2v((v3(0.5f) - lift) / (gain - lift));  // log10(a) / log10(b) == log2(a) / log2(b)
   const vec3 den = pp_log2v(midGray);
   const vec3 gamma = num / den;
-  const vec3 tt = pp_saturate3(v3(powr_det(color.x, 1.0f / gamma.x), powr_det(color.y, 1.0f / gamma.y), powr_det(color.z, 1.0f / gamma.z)));
+  const vec3 tt = pp_saturate3(v3(pp_powr(color.x, 1.0f / gamma.x), pp_powr(color.y, 1.0f / gamma.y), pp_powr(color.z, 1.0f / gamma.z)));
   color = lift + (gain - lift) * tt;  // mix(lift, gain, t)
   color = pp_mul(pc.odt, color);
-  auto srgb = [](float c) { return c < 0.0031308f ? 12.92f * c : 1.055f * powr_det(c, 1.0f / 2.4f) - 0.055f; };  // :29-36
+  auto srgb = [](float c) { return c < 0.0031308f ? 12.92f * c : 1.055f * pp_powr(c, 1.0f / 2.4f) - 0.055f; };  // :29-36
   return v3(srgb(color.x), srgb(color.y), srgb(color.z));
 }
 

@@ -1012,6 +1012,9 @@ int dev_read_render_target(pt_renderer* r, uint8_t* rgba8_out) {
 
 int dev_set_gmon_options(pt_renderer* r, const pt_gmon_options* o) {
   if (!r || !o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  // G never exceeds 1, so a larger cap only acts on the NaN of an all-black pixel: min(NaN, cap) = cap, and int(cap * (n / 2)) of a
+  // huge or infinite cap is undefined in k_gmon (a trim count past the bucket array in the oracle).  NaN is refused by the same test.
+  if (!(o->cap >= 0.0f && o->cap <= 1.0f)) return fail(PT_ERR_INVALID_ARGUMENT, "gmon cap must lie in [0, 1]");
   r->gmon_cap = o->cap;
   return PT_OK;
 }

@@ -52,7 +52,7 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    srcs = [os.path.join(ORACLE_DIR, f) for f in ("pt_oracle.cpp", "pt_oracle.h", "oracle_math.h")]
+    srcs = [os.path.join(ORACLE_DIR, f) for f in ("pt_oracle.cpp", "post_oracle.inc", "pt_oracle.h", "oracle_math.h")]
     if not os.path.exists(ORACLE_LIB) or any(os.path.getmtime(s) > os.path.getmtime(ORACLE_LIB) for s in srcs):
         build()
     L = C.CDLL(ORACLE_LIB)

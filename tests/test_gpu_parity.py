@@ -314,11 +314,15 @@ def test_odd_image_size_and_many_batches(gpu_renderer):
     assert np.array_equal(acc.view(np.uint32), ref.view(np.uint32))
 
 
-@pytest.mark.parametrize("spp,buckets,sif", [(30, 15, 8), (17, 5, 3)])
+# at 33x17: one bucket, two, the most there can be, one sample past that, fewer full buckets than allocated (spp < buckets), a ragged last bucket
+GMON_EDGE_PAIRS = [(1, 1), (2, 2), (32, 32), (33, 32), (5, 8), (31, 3)]
+
+
+@pytest.mark.parametrize("spp,buckets,sif", [(30, 15, 8), (17, 5, 3)] + [(s, b, 4) for s, b in GMON_EDGE_PAIRS])
 def test_gmon_matches_oracle(gpu_renderer, spp, buckets, sif):
     """bucketed accumulation + Gini-weighted median of means, bit-identical to the oracle."""
     sc = _scene("cornell_sphere")
-    w, h, bounces = 96, 64, 5
+    (w, h), bounces = ((33, 17) if (spp, buckets) in GMON_EDGE_PAIRS else (96, 64)), 5
     flags = abi.FLAG_MULTISCATTER_GGX | abi.FLAG_GMON
     gpu_renderer.selectKernel(abi.INTEGRATOR_MIS)
     gpu_renderer.startRender(sc, (w, h), spp, gmonBuckets=buckets, flags=flags, max_bounces=bounces, samples_in_flight=sif)
