@@ -1,4 +1,4 @@
-"""Host side of the adaptive-sampling tests: the ctypes loader of tests/_build/libadaptive_emu.so (the host build of
+"""Host side of the adaptive-sampling tests: the ctypes wrapper of the ad_* functions of the host harness (tests/host_build.py; the host build of
 platinum_amd/csrc/pt_adaptive.h and of the denoiser's per-pixel-N prep, tests/emu/adaptive_emu.cpp) and a float64 numpy restatement of
 the criterion as DESIGN.md §3b states it; reference_render, a whole adaptive render on the host (denoise_lib.HostScene + the host
 criterion), and the configurations tests/test_adaptive_reference.py and tests/test_gpu_adaptive_matrix.py share.  TEST HARNESS, never
@@ -6,7 +6,6 @@ imported by platinum_amd."""
 import ctypes as C
 import functools
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,31 +14,18 @@ _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
-SRC = os.path.join(_ROOT, "tests", "emu", "adaptive_emu.cpp")
-LIB = os.path.join(_ROOT, "tests", "_build", "libadaptive_emu.so")
+import host_build  # noqa: E402
+
 LUM_FLOOR = 1e-3
-_lib = None
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    csrc = os.path.join(_ROOT, "platinum_amd", "csrc")
-    emu = os.path.join(_ROOT, "tests", "emu")
-    deps = [os.path.join(emu, f) for f in os.listdir(emu)] + [os.path.join(_ROOT, "include", "ptamd.h")]
-    deps += [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread", "-shared", "-o", tmp, SRC])
-        os.replace(tmp, LIB)
-    L = C.CDLL(LIB)
+    L = host_build.load()
     L.ad_host_error.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
     L.ad_host_tiles.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]
     L.ad_host_filter_counts.argtypes = [C.c_void_p] * 4 + [C.c_uint32] * 2 + [C.c_void_p, C.c_uint32] + [C.c_float] * 3 + [C.c_void_p]
     L.ad_host_options_layout.argtypes = [C.POINTER(C.c_uint32 * 5)]
-    _lib = L
     return L
 
 

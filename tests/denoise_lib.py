@@ -1,9 +1,9 @@
-"""Host side of the denoiser tests: the ctypes loader of tests/_build/libdenoise_emu.so (the host build of
+"""Host side of the denoiser tests: the ctypes wrapper of the dn_* functions of the host harness (tests/host_build.py; the host build of
 platinum_amd/csrc/pt_denoise.h, tests/emu/denoise_emu.cpp) and a float64 numpy restatement of the filter as DESIGN.md §3 states it.
 TEST HARNESS, never imported by platinum_amd."""
 import ctypes as C
+import functools
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,36 +13,20 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 from platinum_amd import abi  # noqa: E402
 
-SRC = os.path.join(_ROOT, "tests", "emu", "denoise_emu.cpp")
-LIB = os.path.join(_ROOT, "tests", "_build", "libdenoise_emu.so")
-_lib = None
+import emu_lib  # noqa: E402
 
 DEFAULTS = dict(iterations=5, sigma_l=4.0, sigma_n=128.0, sigma_z=1.0)
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    csrc = os.path.join(_ROOT, "platinum_amd", "csrc")
-    deps = [SRC, os.path.join(_ROOT, "tests", "emu", "wavefront_emu.cpp"), os.path.join(_ROOT, "include", "ptamd.h")]
-    deps += [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread", "-shared", "-o", tmp, SRC])
-        os.replace(tmp, LIB)
-    L = C.CDLL(LIB)
-    L.emu_create.restype = C.c_void_p
-    L.emu_create.argtypes = [C.POINTER(abi.SceneSnapshot), C.POINTER(abi.RenderParams), C.c_void_p, C.c_uint64]
-    L.emu_destroy.argtypes = [C.c_void_p]
+    L = emu_lib.lib()   # (HostScene creates its scene with emu_create)
     L.dn_host_filter.argtypes = [C.c_void_p] * 4 + [C.c_uint32] * 4 + [C.c_float] * 3 + [C.c_void_p]
     L.dn_host_stage_aov.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dn_host_lum.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.dn_host_render.restype = C.c_uint64
     L.dn_host_render.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5
     L.dn_host_options_layout.argtypes = [C.POINTER(C.c_uint32 * 7)]
-    _lib = L
     return L
 
 

@@ -1,7 +1,9 @@
 // TEST HARNESS ONLY (tests/emu) — the host build of the adaptive-sampling criterion (platinum_amd/csrc/pt_adaptive.h) and of the
 // denoiser's prep with per-pixel sample counts (pt_denoise.h dn_prep_pixel_counts), for tests/test_adaptive_host.py and
-// tests/test_gpu_adaptive.py.  It reuses denoise_emu.cpp.  Not part of libptamd.so, never loaded by platinum_amd, not a fallback.
-#include "denoise_emu.cpp"
+// tests/test_gpu_adaptive.py.  Not part of libptamd.so, never loaded by platinum_amd, not a fallback.
+// Third part of tests/emu/host_harness.cpp, after denoise_emu.cpp; not compiled alone.
+#ifndef PTAMD_TESTS_EMU_ADAPTIVE_EMU
+#define PTAMD_TESTS_EMU_ADAPTIVE_EMU
 #include "../../platinum_amd/csrc/pt_adaptive.h"
 
 extern "C" {
@@ -65,3 +67,5 @@ void ad_host_options_layout(uint32_t out[5]) {
 }
 
 }  // extern "C"
+
+#endif  // PTAMD_TESTS_EMU_ADAPTIVE_EMU

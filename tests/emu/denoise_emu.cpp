@@ -1,7 +1,9 @@
 // TEST HARNESS ONLY (tests/emu) — the host build of the denoiser's arithmetic and of the first-hit AOV stage
-// (platinum_amd/csrc/pt_denoise.h), for tests/test_denoise_host.py and tests/test_gpu_denoise.py.  It reuses the host scene of
-// wavefront_emu.cpp.  Not part of libptamd.so, never loaded by platinum_amd, not a fallback.
-#include "wavefront_emu.cpp"
+// (platinum_amd/csrc/pt_denoise.h), for tests/test_denoise_host.py and tests/test_gpu_denoise.py.  It reuses the host scene (Emu) and
+// the per-path function (emu_path) of wavefront_emu.cpp.  Not part of libptamd.so, never loaded by platinum_amd, not a fallback.
+// Second part of tests/emu/host_harness.cpp, which includes wavefront_emu.cpp before it; not compiled alone.
+#ifndef PTAMD_TESTS_EMU_DENOISE_EMU
+#define PTAMD_TESTS_EMU_DENOISE_EMU
 #include "../../platinum_amd/csrc/pt_denoise.h"
 
 extern "C" {
@@ -85,7 +87,7 @@ uint64_t dn_host_render(void* h, uint32_t first, uint32_t ns, uint32_t n0, float
   const uint32_t W = S.width, H = S.height;
   std::vector<pt_hit_record> hits((size_t)W * H);
   std::vector<float> ab((size_t)W * H * 4), nb((size_t)W * H * 4);
-  std::vector<uint32_t> lds(std::max(kLdsStack, kLdsStack6) + 1), spill(kSpillStack), pend(std::max(kPendLeaves, kPendLeaves6) + 1);
+  TravScratch scratch;
   const bool zero = e->params.nonfinite_policy == PT_NONFINITE_ZERO;
   uint64_t nonfinite = 0;
   for (uint32_t s = 0; s < ns; s++) {
@@ -95,7 +97,7 @@ uint64_t dn_host_render(void* h, uint32_t first, uint32_t ns, uint32_t n0, float
     for (uint32_t y = 0; y < H; y++)
       for (uint32_t x = 0; x < W; x++) {
         const size_t p = (size_t)y * W + x;
-        vec3 L = emu_path(e, x, y, first + s, lds.data(), spill.data(), pend.data());
+        vec3 L = emu_path<false>(e, x, y, first + s, scratch);
         if (!(fabsf(L.x) <= 3.0e38f && fabsf(L.y) <= 3.0e38f && fabsf(L.z) <= 3.0e38f)) {  // NaN or inf
           nonfinite++;
           if (nonfinite_px) nonfinite_px[p]++;
@@ -131,3 +133,5 @@ void dn_host_options_layout(uint32_t out[7]) {
 }
 
 }  // extern "C"
+
+#endif  // PTAMD_TESTS_EMU_DENOISE_EMU

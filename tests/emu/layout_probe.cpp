@@ -1,5 +1,8 @@
 // TEST HARNESS ONLY (tests/emu) — the host build of the index maps of platinum_amd/csrc/pt_layout.h and of plan_queues (queue_plan.h), one
 // table per map, for tests/test_layout_host.py.  Not part of libptamd.so, never loaded by platinum_amd, not a fallback.
+// Fifth part of tests/emu/host_harness.cpp; not compiled alone.
+#ifndef PTAMD_TESTS_EMU_LAYOUT_PROBE
+#define PTAMD_TESTS_EMU_LAYOUT_PROBE
 #include "../../platinum_amd/csrc/pt_device.h"
 #include "../../platinum_amd/csrc/pt_layout.h"
 #include "../../platinum_amd/csrc/queue_plan.h"
@@ -59,3 +62,5 @@ void lp_tile_pixels(uint32_t W, uint32_t H, uint32_t* xy) {
 }
 
 }  // extern "C"
+
+#endif  // PTAMD_TESTS_EMU_LAYOUT_PROBE

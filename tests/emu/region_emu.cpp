@@ -1,5 +1,8 @@
 // TEST HARNESS ONLY (tests/emu) — how this compiler lays out pt_render_region (include/ptamd.h), and the host build of the rectangle
 // arithmetic of platinum_amd/csrc/pt_layout.h, for tests/test_region_host.py.  Not part of libptamd.so, never loaded by platinum_amd.
+// Fourth part of tests/emu/host_harness.cpp; not compiled alone.
+#ifndef PTAMD_TESTS_EMU_REGION_EMU
+#define PTAMD_TESTS_EMU_REGION_EMU
 #include <cstddef>
 #include <cstdint>
 
@@ -26,3 +29,5 @@ void rg_host_mask(uint32_t W, uint32_t H, uint32_t x0, uint32_t y0, uint32_t x1,
 }
 
 }  // extern "C"
+
+#endif  // PTAMD_TESTS_EMU_REGION_EMU

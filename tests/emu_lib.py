@@ -1,8 +1,9 @@
-"""ctypes loader for tests/_build/libwavefront_emu.so — the host build of the product's per-path stage functions
-(TEST HARNESS, see tests/emu/wavefront_emu.cpp). Never imported by platinum_amd."""
+"""ctypes wrapper of the emu_* functions of the host harness (tests/host_build.py: tests/_build/libptamd_host.so) — the host build of
+the product's per-path stage functions (TEST HARNESS, see tests/emu/wavefront_emu.cpp).  bench.py's cpu_baseline renders through
+EmuScene.render.  Never imported by platinum_amd."""
 import ctypes as C
+import functools
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,21 +13,11 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 from platinum_amd import abi  # noqa: E402
 
-SRC = os.path.join(_ROOT, "tests", "emu", "wavefront_emu.cpp")
-LIB = os.path.join(_ROOT, "tests", "_build", "libwavefront_emu.so")
-_lib = None
+import host_build  # noqa: E402
 
 
-def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    csrc = os.path.join(_ROOT, "platinum_amd", "csrc")
-    deps = [SRC] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread", "-shared", "-o", LIB, SRC])
-    L = C.CDLL(LIB)
+def bind(L):
+    """The argtypes of the emu_* functions on L, a library that holds the harness (host_build.load of it, or of a unit that includes it)."""
     L.emu_create.restype = C.c_void_p
     L.emu_create.argtypes = [C.POINTER(abi.SceneSnapshot), C.POINTER(abi.RenderParams), C.c_void_p, C.c_uint64]
     L.emu_destroy.argtypes = [C.c_void_p]
@@ -38,13 +29,17 @@ def lib():
     L.emu_render.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]
     L.emu_halton.restype = C.c_float
     L.emu_halton.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-    _lib = L
     return L
 
 
+@functools.lru_cache(maxsize=None)
+def lib():
+    return bind(host_build.load())
+
+
 class EmuScene:
-    def __init__(self, scene, params):
-        self.L = lib()
+    def __init__(self, scene, params, L=None):
+        self.L = lib() if L is None else L
         self.params = params
         self.snapshot = scene.snapshot()
         blob = open(abi.LUT_PATH, "rb").read()

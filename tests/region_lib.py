@@ -1,10 +1,10 @@
 """Host side of the render-region tests: reference_region_render, a whole region render on the host, adaptive or
 uniform, built from what exists (denoise_lib.HostScene renders, adaptive_lib.host_error judges), and the numpy enumeration of the
-tiles a rectangle touches.  No GPU in the loop.  TEST HARNESS, never imported by platinum_amd."""
+tiles a rectangle touches; the ctypes wrapper of the rg_* functions of the host harness (tests/host_build.py,
+tests/emu/region_emu.cpp).  No GPU in the loop.  TEST HARNESS, never imported by platinum_amd."""
 import ctypes as C
 import functools
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,28 +14,15 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 import adaptive_lib as al  # noqa: E402
-
-SRC = os.path.join(_ROOT, "tests", "emu", "region_emu.cpp")
-LIB = os.path.join(_ROOT, "tests", "_build", "libregion_emu.so")
-_lib = None
+import host_build  # noqa: E402
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    """tests/emu/region_emu.cpp built for the host."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    deps = [SRC, os.path.join(_ROOT, "include", "ptamd.h"), os.path.join(_ROOT, "platinum_amd", "csrc", "pt_layout.h"),
-            os.path.join(_ROOT, "platinum_amd", "csrc", "pt_math.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", tmp, SRC])
-        os.replace(tmp, LIB)
-    L = C.CDLL(LIB)
+    """tests/emu/region_emu.cpp built for the host (part of the one harness library)."""
+    L = host_build.load()
     L.rg_host_region_layout.argtypes = [C.POINTER(C.c_uint32 * 6)]
     L.rg_host_mask.argtypes = [C.c_uint32] * 6 + [C.c_void_p]
-    _lib = L
     return L
 
 

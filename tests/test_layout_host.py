@@ -1,19 +1,15 @@
 """CPU: the tile, queue-segment and radiance-buffer index maps (platinum_amd/csrc/pt_layout.h, built for the host by
-tests/emu/layout_probe.cpp) against the properties every kernel relies on, enumerated exhaustively over small queue plans
+tests/emu/layout_probe.cpp, a part of the host harness of tests/host_build.py) against the properties every kernel relies on, enumerated exhaustively over small queue plans
 (platinum_amd/csrc/queue_plan.h plan_queues): images with partial tiles on both edges, sample counts that are no multiple of the
 eight-sample staging round, one and several tiles per segment, one and several bands."""
 import ctypes as C
 import functools
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(_ROOT, "tests", "emu", "layout_probe.cpp")
-LIB = os.path.join(_ROOT, "tests", "_build", "liblayout_probe.so")
+import host_build
 
 
 class Plan(C.Structure):  # include/ptamd.h pt_queue_plan
@@ -23,14 +19,7 @@ class Plan(C.Structure):  # include/ptamd.h pt_queue_plan
 
 @functools.lru_cache(maxsize=None)
 def lib():
-    csrc = os.path.join(_ROOT, "platinum_amd", "csrc")
-    deps = [SRC, os.path.join(_ROOT, "include", "ptamd.h")] + [os.path.join(csrc, f) for f in ("pt_layout.h", "pt_math.h", "pt_device.h", "queue_plan.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread", "-shared", "-o", tmp, SRC])
-        os.replace(tmp, LIB)
-    L = C.CDLL(LIB)
+    L = host_build.load()
     L.lp_plan.argtypes = [C.c_uint32] * 5 + [C.POINTER(Plan)]
     L.lp_tile_count.argtypes = [C.c_uint32] * 2
     L.lp_tile_count.restype = C.c_uint32

@@ -1,17 +1,18 @@
 #!/usr/bin/env python3
-"""Host probe (tests/emu emu_l2_probe): predicted L2 misses per closest-hit ray of C3's bounce-b rays under today's chunk order
+"""ARCHIVED (experiment closed: DESIGN.md section 6, profiles/r06_experiments.md section 1).  Host probe (tools/archive/emu_probes.cpp emu_l2_probe): predicted L2 misses per closest-hit ray of C3's bounce-b rays under today's chunk order
 against SCENE-SPACE ray queues (rays sorted by the Morton cell of their origin, 8 contiguous cell ranges -> 8 XCDs), by replaying the 64-byte lines
 the rays fetch through eight 4 MB 16-way LRU caches fed by 768 resident waves each.  Go / no-go rule: build the scheduler only if <= 1.2 (today's counters: 1.93).
-    python tools/l2_probe.py [c3] [bounces=1,2,3] [T=tiles per band in the window] [s0=first tile index inside each band]"""
+    python tools/archive/l2_probe.py [c3] [bounces=1,2,3] [T=tiles per band in the window] [s0=first tile index inside each band] [samples=128]"""
 import ctypes as C
 import os
 import sys
 import time
 
-ROOT = os.environ.get("GRAFT_REPO_ROOT") or os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 os.environ.update(EMU_MORTON="1", EMU_PLOC="8", EMU_WIDE6="1", EMU_PAIRS="1")
 import emu_lib  # noqa: E402
+import host_build  # noqa: E402
 from platinum_amd import scenes  # noqa: E402
 from platinum_amd.renderer import make_params  # noqa: E402
 
@@ -19,9 +20,11 @@ wl = sys.argv[1] if len(sys.argv) > 1 else "c3"
 bounces = [int(x) for x in (sys.argv[2] if len(sys.argv) > 2 else "1,2,3").split(",")]
 T = int(sys.argv[3]) if len(sys.argv) > 3 else 0
 s0 = int(sys.argv[4]) if len(sys.argv) > 4 else 4000
-ns = 128
+ns = int(sys.argv[5]) if len(sys.argv) > 5 else 128
 factory, W, H, spp, B = scenes.CONFIGS[wl]
-e = emu_lib.EmuScene(factory(), make_params(W, H, ns, B))
+# the probes' own library: the test harness plus tools/archive/emu_probes.cpp
+PROBES = emu_lib.bind(host_build.load(os.path.join(ROOT, "tools", "archive", "emu_probes.cpp"), os.path.join(ROOT, "tools", "_build", "libemu_probes.so")))
+e = emu_lib.EmuScene(factory(), make_params(W, H, ns, B), L=PROBES)
 e.L.emu_l2_probe.argtypes = [C.c_void_p] + [C.c_uint32] * 8 + [C.c_double * 18]
 threads = len(os.sched_getaffinity(0))
 names = ("today (segment order, one cursor)", "origin cells, 8 ranges -> 8 XCDs", "origin-sorted, one cursor")

@@ -1,22 +1,25 @@
 #!/usr/bin/env python3
-"""Host probe (tests/emu emu_origin_sort_probe): distinct 64-byte lines (6-wide nodes + leaf slots) the 64-ray chunks of a segment's SECONDARY rays
+"""ARCHIVED (experiment closed: DESIGN.md section 6, profiles/r05_experiments.md).  Host probe (tools/archive/emu_probes.cpp emu_origin_sort_probe): distinct 64-byte lines (6-wide nodes + leaf slots) the 64-ray chunks of a segment's SECONDARY rays
 fetch, in the order the shading stage leaves them against sorted by the cell of their origin.
-    python tools/origin_sort_probe.py c3 [samples=128]"""
+    python tools/archive/origin_sort_probe.py c3 [samples=128]"""
 import ctypes as C
 import os
 import sys
 
-ROOT = os.environ.get("GRAFT_REPO_ROOT") or os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 os.environ.update(EMU_MORTON="1", EMU_PLOC="8", EMU_WIDE6="1", EMU_PAIRS="1")
 import emu_lib  # noqa: E402
+import host_build  # noqa: E402
 from platinum_amd import scenes  # noqa: E402
 from platinum_amd.renderer import make_params  # noqa: E402
 
 wl = sys.argv[1] if len(sys.argv) > 1 else "c3"
 ns = int(sys.argv[2]) if len(sys.argv) > 2 else 128
 factory, W, H, spp, B = scenes.CONFIGS[wl]
-e = emu_lib.EmuScene(factory(), make_params(W, H, ns, B))
+# the probes' own library: the test harness plus tools/archive/emu_probes.cpp
+PROBES = emu_lib.bind(host_build.load(os.path.join(ROOT, "tools", "archive", "emu_probes.cpp"), os.path.join(ROOT, "tools", "_build", "libemu_probes.so")))
+e = emu_lib.EmuScene(factory(), make_params(W, H, ns, B), L=PROBES)
 e.L.emu_origin_sort_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double * 5]
 tiles = [(tx, ty) for ty in range(8, H // 8, 25) for tx in range(10, W // 8, 45)]
 for b in (1, 2, 3, 5):
