@@ -6,9 +6,12 @@
 //   k_bounds    scene centroid bounds (wave reduce + ordered-int atomics)
 //   k_morton    63-bit Morton code of the AABB centre (21 bits / axis, cubic cells)
 //   radix sort  rocPRIM (hipcub::DeviceRadixSort::SortPairs, 64-bit keys)
-//   k_karras    Karras 2012 radix tree: one thread per internal node, duplicate codes split by position
-//   k_refit     bottom-up AABB union, second arrival at a node proceeds (agent-scope fences around the counter)
-//   k_emit      collapse to 4-wide 64-byte nodes (8-bit quantised, inflated child boxes) + triangles in leaf order
+//   k_ploc_*    the binary tree by PLOC over the Morton order (ploc_dev: passes and a single-block tail launched back to back)
+//   k_karras    ... or the Karras 2012 radix tree ($PTAMD_RADIX_TREE, or PLOC gave up): one thread per internal node, duplicate codes split by position
+//   k_refit     its bottom-up AABB union, second arrival at a node proceeds (agent-scope fences around the counter)
+//   k_emit_sah_head, k_emit_sah_dev   surface-area-guided collapse of either binary tree to 6- or 4-wide 64-byte nodes (8-bit quantised,
+//               inflated child boxes), dense in BFS order (collapse_dev) + triangles in leaf order
+//   k_emit      the even-depth 4-wide collapse: only for a radix tree whose guided collapse is deeper than the traversal stack
 //
 // Not on the per-sample hot path: runs once per pt_start_render; timed separately (pt_stats.bvh_build_ms).
 #include <hip/hip_runtime.h>
@@ -274,9 +277,38 @@ __global__ void __launch_bounds__(256) k_emit(int n, const uint2* __restrict__ c
   atomicAdd(emitted, 1u);
 }
 
-// Surface-area-guided collapse, one tree level per launch: the 4-wide node rooted at binary node i starts from i's two
+// The children of the W-wide node rooted at binary node i: i's two children, then the internal child with the largest surface area is
+// opened (it keeps its slot for its left child, the right child takes the next free slot) until W slots are used or only leaves are left.
+// A strict `>`: of children with equal areas the first one is opened.  Returns the number of slots used; refs[] are binary refs.
+template <int W>
+__device__ __forceinline__ int open_by_area(uint32_t i, const uint2* __restrict__ children, const Box* __restrict__ leaf_boxes,
+                                            const uint32_t* __restrict__ order, const Box* __restrict__ node_boxes, uint32_t (&refs)[W], Box (&bx)[W]) {
+  auto box_of = [&](uint32_t ref) { return (ref & kLeafBit) ? leaf_boxes[order[ref & ~kLeafBit]] : node_boxes[ref]; };
+  auto half_area = [](const Box& b) {
+    const float x = b.hi[0] - b.lo[0], y = b.hi[1] - b.lo[1], z = b.hi[2] - b.lo[2];
+    return x * y + y * z + z * x;
+  };
+  const uint2 ch = children[i];
+  refs[0] = ch.x; bx[0] = box_of(ch.x);
+  refs[1] = ch.y; bx[1] = box_of(ch.y);
+  int count = 2;
+  while (count < W) {
+    int best = -1;
+    float best_area = -1.0f;
+    for (int k = 0; k < count; k++)
+      if (!(refs[k] & kLeafBit)) { const float a = half_area(bx[k]); if (a > best_area) { best_area = a; best = k; } }
+    if (best < 0) break;
+    const uint2 g = children[refs[best]];
+    refs[best] = g.x; bx[best] = box_of(g.x);
+    refs[count] = g.y; bx[count] = box_of(g.y);
+    count++;
+  }
+  return count;
+}
+
+// Surface-area-guided collapse, level by level (k_emit_sah_head / k_emit_sah_dev): the 4-wide node rooted at binary node i starts from i's two
 // children and keeps opening the internal child with the largest surface area until four slots are used (the even-depth
-// rule above opens both children blindly).  On Morton trees this visits 5-13 % fewer nodes per ray (measured with the host
+// rule of k_emit opens both children blindly).  On Morton trees this visits 5-13 % fewer nodes per ray (measured with the host
 // build of the same traversal: C2 7.73 -> 7.37, a 259 k triangle field 11.3 -> 10.5, the atrium 17.0 -> 14.8).
 // Nodes are written DENSELY, level by level: the level's queue holds (binary node, dense index) pairs; an internal child gets
 // the dense index next_base + its position in the next level's queue.  The 4-wide tree therefore occupies node_count
@@ -288,27 +320,9 @@ __device__ __forceinline__ void emit_sah_node(uint32_t t, const uint2* __restric
                                               const uint32_t* __restrict__ order, const Box* __restrict__ node_boxes,
                                               BvhNode* __restrict__ nodes) {
   const uint32_t i = q_in[t].x, dense = q_in[t].y;
-  auto box_of = [&](uint32_t ref) { return (ref & kLeafBit) ? leaf_boxes[order[ref & ~kLeafBit]] : node_boxes[ref]; };
-  auto half_area = [](const Box& b) {
-    const float x = b.hi[0] - b.lo[0], y = b.hi[1] - b.lo[1], z = b.hi[2] - b.lo[2];
-    return x * y + y * z + z * x;
-  };
-  const uint2 ch = children[i];
-  uint32_t refs[4] = {ch.x, ch.y, kInvalidRef, kInvalidRef};
+  uint32_t refs[4];
   Box bx[4];
-  bx[0] = box_of(refs[0]); bx[1] = box_of(refs[1]);
-  int count = 2;
-  while (count < 4) {
-    int best = -1;
-    float best_area = -1.0f;
-    for (int k = 0; k < count; k++)
-      if (!(refs[k] & kLeafBit)) { const float a = half_area(bx[k]); if (a > best_area) { best_area = a; best = k; } }
-    if (best < 0) break;
-    const uint2 g = children[refs[best]];
-    refs[best] = g.x; bx[best] = box_of(g.x);
-    refs[count] = g.y; bx[count] = box_of(g.y);
-    count++;
-  }
+  const int count = open_by_area<4>(i, children, leaf_boxes, order, node_boxes, refs, bx);
   Box3 boxes[4];
   // the internal children of one node get CONSECUTIVE records (one reservation): siblings share 128-byte lines, and a ray that
   // visits two children of a node finds the second one in the line the first one brought in
@@ -339,27 +353,9 @@ __device__ __forceinline__ void emit_sah_node6(uint32_t t, const uint2* __restri
                                                const uint32_t* __restrict__ order, const Box* __restrict__ node_boxes, uint32_t* __restrict__ tri_perm,
                                                BvhNode* __restrict__ nodes) {
   const uint32_t i = q_in[t].x, dense = q_in[t].y;
-  auto box_of = [&](uint32_t ref) { return (ref & kLeafBit) ? leaf_boxes[order[ref & ~kLeafBit]] : node_boxes[ref]; };
-  auto half_area = [](const Box& b) {
-    const float x = b.hi[0] - b.lo[0], y = b.hi[1] - b.lo[1], z = b.hi[2] - b.lo[2];
-    return x * y + y * z + z * x;
-  };
-  const uint2 ch = children[i];
-  uint32_t refs[6] = {ch.x, ch.y, kInvalidRef, kInvalidRef, kInvalidRef, kInvalidRef};
+  uint32_t refs[6];
   Box bx[6];
-  bx[0] = box_of(refs[0]); bx[1] = box_of(refs[1]);
-  int count = 2;
-  while (count < 6) {
-    int best = -1;
-    float best_area = -1.0f;
-    for (int k = 0; k < count; k++)
-      if (!(refs[k] & kLeafBit)) { const float a = half_area(bx[k]); if (a > best_area) { best_area = a; best = k; } }
-    if (best < 0) break;
-    const uint2 g = children[refs[best]];
-    refs[best] = g.x; bx[best] = box_of(g.x);
-    refs[count] = g.y; bx[count] = box_of(g.y);
-    count++;
-  }
+  const int count = open_by_area<6>(i, children, leaf_boxes, order, node_boxes, refs, bx);
   uint32_t n_int = 0;
   for (int k = 0; k < count; k++) n_int += (refs[k] & kLeafBit) ? 0u : 1u;
   const uint32_t n_leaf = (uint32_t)count - n_int;
@@ -382,39 +378,37 @@ __device__ __forceinline__ void emit_sah_node6(uint32_t t, const uint2* __restri
   }
   reinterpret_cast<BvhNode6*>(nodes)[dense] = quantize_node6(boxes, (int)n_int, (int)n_leaf, next_base + p_node, p_leaf);
 }
-__global__ void __launch_bounds__(256) k_emit_sah(uint32_t n_in, const uint2* __restrict__ q_in, uint2* __restrict__ q_out,
-                                                   uint32_t* __restrict__ n_out, uint32_t next_base, uint32_t ref_base, uint32_t leaf_tag,
-                                                   uint32_t remap, const uint2* __restrict__ children, const Box* __restrict__ leaf_boxes,
-                                                   const uint32_t* __restrict__ order, const Box* __restrict__ node_boxes,
-                                                   BvhNode* __restrict__ nodes) {
-  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= n_in) return;
-  emit_sah_node(t, q_in, q_out, n_out, next_base, ref_base, leaf_tag, remap, children, leaf_boxes, order, node_boxes, nodes);
-}
 
 // ---- the builder's device-resident state: PLOC passes and collapse levels are launched back to back, each kernel reads what the one
-// before it left here, and the host looks in only every few passes / levels (it used to wait for a read-back after EVERY pass and level:
-// 46 round trips of ~25 us on C3, a third of the build).  Grids are sized from the last count the host saw (counts only shrink during
-// PLOC; a collapse level is at most 4x the one before); threads beyond the real count leave at once.
+// before it left here, and the host looks in only every few passes / levels (a read-back after EVERY pass and level was 46 round trips
+// of ~25 us on C3, a third of the build).  Grids are sized from the last count the host saw (counts only shrink during PLOC; a collapse
+// level is at most `width` times the one before); threads beyond the real count leave at once.  The kernels and host functions that work
+// this way carry the suffix _dev.
 // (Measured and dropped, r3: the same loops as two COOPERATIVE kernels with grid barriers — correct, and 3.5x slower: a grid-wide
 // barrier costs ~100 us on this part, it has to write back and invalidate eight XCD-private L2s; tools/experiments/r03_bvh_cooperative_build.patch.)
 constexpr uint32_t kMaxLevels = 128;  // 4-wide levels (the traversal stack bounds them far lower: 3 entries per level)
 struct PlocSlot { uint32_t cur, base, buf, ok; };  // clusters left, binary nodes created, which cluster buffer holds them, 0 = gave up
 struct BuildState {
   PlocSlot ploc[2];                  // pass p reads slot p & 1 and writes slot (p + 1) & 1
-  uint32_t level_count[kMaxLevels];  // collapse: nodes queued for level l + 1 by level l (zeroed before the first level)
+  uint32_t tree_ok;                  // children[] / node_boxes[] hold a whole binary tree (k_ploc_tail_dev's verdict; 1 for a radix tree): the collapse runs
+  uint32_t level_count[kMaxLevels];  // collapse: nodes queued for level l + 1 by level l (zeroed by k_seed_queue)
   uint32_t leaf_count;               // 6-wide collapse: triangle slots handed out so far
 };
+__global__ void k_state_init(BuildState* st, uint32_t n, uint32_t tree_ok) {
+  st->ploc[0] = PlocSlot{n, 0u, 0u, 1u};
+  st->ploc[1] = PlocSlot{n, 0u, 0u, 1u};
+  st->tree_ok = tree_ok;
+}
 
 // The first kHeadLevels collapse levels (level l holds at most 4^l nodes: <= 1 024 up to level 5) in one single-block launch, block barriers
 // between the levels: a level is a chain of ~6 dependent loads whatever its size, so a launch per tiny level cost ~27 us each.
 constexpr uint32_t kHeadLevels = 6;
 template <bool W6>
-__global__ void __launch_bounds__(1024) k_emit_sah_head(BuildState* st, uint32_t ploc_slot, uint32_t levels, uint2* q0, uint2* q1, uint32_t* level_count,
+__global__ void __launch_bounds__(1024) k_emit_sah_head(BuildState* st, uint32_t levels, uint2* q0, uint2* q1, uint32_t* level_count,
                                                          uint32_t ref_base, uint32_t leaf_tag, uint32_t remap, const uint2* __restrict__ children,
                                                          const Box* __restrict__ leaf_boxes, const uint32_t* __restrict__ order,
                                                          const Box* __restrict__ node_boxes, uint32_t* __restrict__ tri_perm, BvhNode* __restrict__ nodes) {
-  if (st->ploc[ploc_slot].ok == 0) return;
+  if (st->tree_ok == 0) return;
   uint32_t n_in = 1, before = 0;
   for (uint32_t level = 0; level < levels; level++) {
     if (threadIdx.x < n_in) {
@@ -433,12 +427,12 @@ __global__ void __launch_bounds__(1024) k_emit_sah_head(BuildState* st, uint32_t
 
 // One collapse level, its size and numbering base read from the counts the levels before it left (level 0: the root alone).
 template <bool W6>
-__global__ void __launch_bounds__(256) k_emit_sah_dev(BuildState* st, uint32_t ploc_slot, uint32_t level, const uint2* __restrict__ q_in,
+__global__ void __launch_bounds__(256) k_emit_sah_dev(BuildState* st, uint32_t level, const uint2* __restrict__ q_in,
                                                        uint2* __restrict__ q_out, uint32_t* level_count, uint32_t ref_base, uint32_t leaf_tag,
                                                        uint32_t remap, const uint2* __restrict__ children, const Box* __restrict__ leaf_boxes,
                                                        const uint32_t* __restrict__ order, const Box* __restrict__ node_boxes, uint32_t* __restrict__ tri_perm,
                                                        BvhNode* __restrict__ nodes) {
-  if (st->ploc[ploc_slot].ok == 0) return;  // PLOC gave up: the host falls back to the radix tree
+  if (st->tree_ok == 0) return;  // PLOC gave up: the host falls back to the radix tree
   uint32_t n_in = 1, before = 0;            // nodes of this level, nodes of all levels before it
   for (uint32_t l = 0; l < level; l++) { before += n_in; n_in = st->level_count[l]; }
   const uint32_t t = blockIdx.x * 256 + threadIdx.x;
@@ -457,7 +451,11 @@ __global__ void __launch_bounds__(256) k_reorder_tris(int n, const uint32_t* __r
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) tris_out[i] = tris_in[order[i]];
 }
-__global__ void k_seed_queue(uint2* q, uint32_t* counters, uint32_t root) { q[0] = make_uint2(root, 0u); counters[0] = 0u; counters[1] = 0u; }
+// before a collapse: nothing queued for any level, no triangle slot handed out, the root (dense node 0) alone in the first queue
+__global__ void __launch_bounds__(kMaxLevels) k_seed_queue(BuildState* st, uint2* q, uint32_t root) {
+  st->level_count[threadIdx.x] = 0u;
+  if (threadIdx.x == 0) { st->leaf_count = 0u; q[0] = make_uint2(root, 0u); }
+}
 
 // ---- PLOC: parallel locally-ordered clustering (Meister & Bittner 2018) over the Morton order -----------------------------
 // Every cluster looks +-kPlocRadius positions around itself for the neighbour whose union with it has the smallest surface
@@ -469,7 +467,7 @@ __global__ void k_seed_queue(uint2* q, uint32_t* counters, uint32_t root) { q[0]
 #define PT_PLOC_RADIUS 8
 #endif
 constexpr int kPlocRadius = PT_PLOC_RADIUS;
-constexpr uint32_t kPlocTail = 1024;  // clusters the single-block tail takes over at (k_ploc_tail)
+constexpr uint32_t kPlocTail = 1024;  // clusters the single-block tail takes over at (k_ploc_tail_dev)
 __device__ __forceinline__ float merged_half_area(const Box& a, const Box& b) {
   const float x = fmaxf(a.hi[0], b.hi[0]) - fminf(a.lo[0], b.lo[0]);
   const float y = fmaxf(a.hi[1], b.hi[1]) - fminf(a.lo[1], b.lo[1]);
@@ -483,63 +481,18 @@ __global__ void __launch_bounds__(256) k_ploc_init(uint32_t n, const Box* __rest
   cl_ref[i] = kLeafBit | i;
   cl_box[i] = leaf_boxes[order[i]];
 }
-__global__ void __launch_bounds__(256) k_ploc_nn(uint32_t n, const Box* __restrict__ cl_box, uint32_t* __restrict__ nn) {
-  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-  if (i >= (int)n) return;
-  const Box me = cl_box[i];
-  float best = kInf;
-  int bj = i;
-  // candidate order: the pairing partner i ^ 1 first, then by distance (left before right); a strict `<` keeps the first
-  // of equal candidates, so a run of identical boxes pairs up as (0,1)(2,3)... instead of one merge per pass
-  auto consider = [&](int j) {
-    if (j < 0 || j >= (int)n || j == i) return;
-    const float a = merged_half_area(me, cl_box[j]);
-    if (a < best) { best = a; bj = j; }
-  };
-  consider(i ^ 1);
-  for (int d = 1; d <= kPlocRadius; d++) { consider(i - d); consider(i + d); }
-  nn[i] = (uint32_t)bj;
-}
-__global__ void __launch_bounds__(256) k_ploc_flags(uint32_t n, const uint32_t* __restrict__ nn, uint32_t* __restrict__ merge_flag,
-                                                     uint32_t* __restrict__ keep_flag) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t j = nn[i];
-  const bool mutual = j != i && nn[j] == i;
-  merge_flag[i] = (mutual && i < j) ? 1u : 0u;
-  keep_flag[i] = (mutual && i > j) ? 0u : 1u;
-}
-__global__ void __launch_bounds__(256) k_ploc_apply(uint32_t n, const uint32_t* __restrict__ nn, const uint32_t* __restrict__ merge_flag,
-                                                     const uint32_t* __restrict__ keep_flag, const uint32_t* __restrict__ node_off,
-                                                     const uint32_t* __restrict__ pos, uint32_t base, const uint32_t* __restrict__ cl_ref,
-                                                     const Box* __restrict__ cl_box, uint32_t* __restrict__ out_ref, Box* __restrict__ out_box,
-                                                     uint2* __restrict__ children, Box* __restrict__ node_boxes, uint32_t* __restrict__ counts) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  if (i == n - 1) { counts[0] = node_off[i] + merge_flag[i]; counts[1] = pos[i] + keep_flag[i]; }
-  if (!keep_flag[i]) return;
-  const uint32_t p = pos[i];
-  if (merge_flag[i]) {
-    const uint32_t j = nn[i], idx = base + node_off[i];
-    const Box a = cl_box[i], b = cl_box[j];
-    Box m;
-    for (int k = 0; k < 3; k++) { m.lo[k] = fminf(a.lo[k], b.lo[k]); m.hi[k] = fmaxf(a.hi[k], b.hi[k]); }
-    children[idx] = make_uint2(cl_ref[i], cl_ref[j]);
-    node_boxes[idx] = m;
-    out_ref[p] = idx;
-    out_box[p] = m;
-  } else {
-    out_ref[p] = cl_ref[i];
-    out_box[p] = cl_box[i];
-  }
-}
 
 // One PLOC pass as three launches that take the cluster count from device memory: (A) nearest-neighbour search; (B) every block counts the
 // merges / survivors of its contiguous tile of the cluster array; (C) every block sums the counts of the blocks before it (its output
 // offsets), recomputes its tile's flags, numbers them with ballots, writes the merged / kept clusters, and block 0 leaves the next pass its
-// state.  Same candidate order, same mutual-pair rule, same numbering (positions and node indices in cluster order) as k_ploc_nn / _flags /
-// two device-wide prefix sums / _apply: the tree is the same; a pass is 3 launches instead of 7 + a read-back.  Passes launched after the
-// cluster count has fallen to kPlocTail (the host's count is a few passes old) do nothing but hand the state on.
+// state.  The rules, which k_ploc_tail_dev repeats in LDS:
+//   candidate order   the pairing partner i ^ 1 first, then by distance d = 1 ... kPlocRadius, i - d before i + d; a strict `<` keeps the
+//                     first of equal candidates, so a run of identical boxes pairs up as (0,1)(2,3)... instead of one merge per pass
+//   mutual pairs      i and j merge when nn[i] == j and nn[j] == i; the lower position of the two carries the merged cluster (merge
+//                     flag), the higher one is dropped, everything else is kept as it is (keep flag)
+//   numbering         in cluster order: the m-th merge of a pass becomes binary node base + m, the k-th kept cluster moves to position k
+//                     (exclusive prefix sums of the two flags), so the tree is the same on every run
+// Passes launched after the cluster count has fallen to kPlocTail (the host's count is a few passes old) do nothing but hand the state on.
 __device__ __forceinline__ void ploc_flags(uint32_t i, uint32_t cur, const uint32_t* __restrict__ nn, uint32_t& j, bool& mf, bool& kf) {
   j = i; mf = false; kf = false;
   if (i < cur) {
@@ -550,10 +503,6 @@ __device__ __forceinline__ void ploc_flags(uint32_t i, uint32_t cur, const uint3
   }
 }
 __device__ __forceinline__ bool ploc_active(const PlocSlot& ps) { return ps.ok != 0 && ps.cur > kPlocTail; }
-__global__ void k_ploc_state_init(BuildState* st, uint32_t n) {
-  st->ploc[0] = PlocSlot{n, 0u, 0u, 1u};
-  st->ploc[1] = PlocSlot{n, 0u, 0u, 1u};
-}
 __global__ void __launch_bounds__(256) k_ploc_nn_dev(const BuildState* __restrict__ st, uint32_t pass, const Box* __restrict__ box0, const Box* __restrict__ box1,
                                                       uint32_t* __restrict__ nn) {
   const PlocSlot ps = st->ploc[pass & 1u];
@@ -675,22 +624,27 @@ __global__ void __launch_bounds__(256) k_ploc_apply_dev(BuildState* __restrict__
 
 // The LAST passes of PLOC in one launch: once at most kPlocTail clusters are left, one 1024-thread block keeps them in LDS and
 // runs nearest-neighbour search, mutual-pair test, the two prefix sums and the merge for every remaining pass between block
-// barriers.  Same arithmetic, same candidate order, same node numbering as the multi-kernel passes (k_ploc_nn / _flags / _apply):
-// the tree does not change; what goes away is ~25 of the ~40 passes' worth of tiny dependent launches and host round trips
-// (C3: BVH build 4.4 -> 3.x ms).  counts[0] = nodes created in all (base), counts[1] = clusters left (1 on success).
-__device__ __forceinline__ void ploc_tail_body(uint32_t n0, uint32_t base0, const uint32_t* __restrict__ ref_in, const Box* __restrict__ box_in,
-                                               uint2* __restrict__ children, Box* __restrict__ node_boxes, uint32_t* __restrict__ counts) {
+// barriers.  Same arithmetic and rules as the three-launch passes above: what goes away is ~25 of the ~40 passes' worth of tiny
+// dependent launches (C3: BVH build 4.4 -> 3.x ms).  Cluster count, node base and buffer come from the state slot; the verdict goes
+// to BuildState::tree_ok: one cluster is left and the root is the last node created, n - 2.
+__global__ void __launch_bounds__(1024) k_ploc_tail_dev(BuildState* __restrict__ st, uint32_t slot, uint32_t n, const uint32_t* __restrict__ ref0,
+                                                         const uint32_t* __restrict__ ref1, const Box* __restrict__ box0, const Box* __restrict__ box1,
+                                                         uint2* __restrict__ children, Box* __restrict__ node_boxes) {
   __shared__ Box s_box[2][kPlocTail];
   __shared__ uint32_t s_ref[2][kPlocTail];
   __shared__ uint32_t s_nn[kPlocTail];
   __shared__ uint32_t s_merge[kPlocTail], s_keep[kPlocTail];   // inclusive prefix sums of the pass's flags
+  const PlocSlot ps = st->ploc[slot];
+  if (ps.ok == 0 || ps.cur > kPlocTail) return;  // the passes gave up, or left more than a block holds: tree_ok stays 0
+  const uint32_t* ref_in = ps.buf ? ref1 : ref0;
+  const Box* box_in = ps.buf ? box1 : box0;
   const uint32_t i = threadIdx.x;
-  if (i < n0) { s_box[0][i] = box_in[i]; s_ref[0][i] = ref_in[i]; }
+  if (i < ps.cur) { s_box[0][i] = box_in[i]; s_ref[0][i] = ref_in[i]; }
   __syncthreads();
-  uint32_t cur = n0, base = base0;
+  uint32_t cur = ps.cur, base = ps.base;
   int a = 0;
   for (uint32_t pass = 0; cur > 1 && pass < 4 * kPlocTail; pass++) {
-    // nearest neighbour within +-kPlocRadius (k_ploc_nn)
+    // nearest neighbour within +-kPlocRadius (as k_ploc_nn_dev)
     if (i < cur) {
       const Box me = s_box[a][i];
       float best = kInf;
@@ -705,7 +659,7 @@ __device__ __forceinline__ void ploc_tail_body(uint32_t n0, uint32_t base0, cons
       s_nn[i] = (uint32_t)bj;
     }
     __syncthreads();
-    // mutual pairs (k_ploc_flags) and their inclusive prefix sums (Hillis-Steele over the block)
+    // mutual pairs (as ploc_flags) and their inclusive prefix sums (Hillis-Steele over the block)
     uint32_t j = 0, mf = 0, kf = 0;
     if (i < cur) {
       j = s_nn[i];
@@ -722,7 +676,7 @@ __device__ __forceinline__ void ploc_tail_body(uint32_t n0, uint32_t base0, cons
       __syncthreads();
     }
     const uint32_t n_merge = s_merge[kPlocTail - 1], n_keep = s_keep[kPlocTail - 1];
-    // merge / copy into the other buffer (k_ploc_apply)
+    // merge / copy into the other buffer (as k_ploc_apply_dev)
     if (i < cur && kf) {
       const uint32_t pos = s_keep[i] - 1u;
       if (mf) {
@@ -746,23 +700,7 @@ __device__ __forceinline__ void ploc_tail_body(uint32_t n0, uint32_t base0, cons
     cur = n_keep;
     a ^= 1;
   }
-  if (i == 0) { counts[0] = base; counts[1] = cur; }
-}
-__global__ void __launch_bounds__(1024) k_ploc_tail(uint32_t n0, uint32_t base0, const uint32_t* __restrict__ ref_in, const Box* __restrict__ box_in,
-                                                     uint2* __restrict__ children, Box* __restrict__ node_boxes, uint32_t* __restrict__ counts) {
-  ploc_tail_body(n0, base0, ref_in, box_in, children, node_boxes, counts);
-}
-// ... the same, entered from the device-driven passes: cluster count, node base and buffer come from the state slot; it leaves its
-// verdict there (ok = the root is the last node created, n - 2, and one cluster is left)
-__global__ void __launch_bounds__(1024) k_ploc_tail_dev(BuildState* __restrict__ st, uint32_t slot, uint32_t n, const uint32_t* __restrict__ ref0,
-                                                         const uint32_t* __restrict__ ref1, const Box* __restrict__ box0, const Box* __restrict__ box1,
-                                                         uint2* __restrict__ children, Box* __restrict__ node_boxes, uint32_t* __restrict__ counts) {
-  const PlocSlot ps = st->ploc[slot];
-  if (ps.ok == 0) return;
-  if (ps.cur > kPlocTail) { if (threadIdx.x == 0) st->ploc[slot].ok = 0; return; }
-  ploc_tail_body(ps.cur, ps.base, ps.buf ? ref1 : ref0, ps.buf ? box1 : box0, children, node_boxes, counts);
-  __syncthreads();
-  if (threadIdx.x == 0) st->ploc[slot] = PlocSlot{counts[1], counts[0], ps.buf, (counts[0] == n - 1 && counts[1] == 1) ? 1u : 0u};
+  if (i == 0) st->tree_ok = (base == n - 1 && cur == 1) ? 1u : 0u;
 }
 
 #define LB_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = e_; goto done; } } while (0)
@@ -780,98 +718,32 @@ struct Arena {
   }
 };
 
-// Builds the binary tree by PLOC over the Morton order `order` (n >= 2).  Fills children[] / node_boxes[] (n - 1 slots, the
-// root is the last node created) and *root.  *ok = false when the pass limit is hit (the caller falls back to the radix tree).
-static size_t ploc_scratch_bytes(uint32_t n, size_t* scan_bytes_out) {
-  size_t scan_bytes = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0);
-  *scan_bytes_out = scan_bytes;
-  return 2 * (Arena::pad(sizeof(uint32_t) * (size_t)n) + Arena::pad(sizeof(Box) * (size_t)n)) + 5 * Arena::pad(sizeof(uint32_t) * (size_t)n) +
-         Arena::pad(2 * sizeof(uint32_t)) + Arena::pad(scan_bytes);
-}
-static hipError_t ploc_build(hipStream_t s, uint32_t n, const Box* leaf_boxes, const uint32_t* order, uint2* children, Box* node_boxes,
-                             uint32_t* root, bool* ok, Arena& arena, size_t scan_bytes) {
-  hipError_t err = hipSuccess;
-  *ok = false;
-  uint32_t* cl_ref[2] = {nullptr, nullptr}; Box* cl_box[2] = {nullptr, nullptr};
-  uint32_t *nn = nullptr, *merge_flag = nullptr, *keep_flag = nullptr, *node_off = nullptr, *pos = nullptr, *counts = nullptr;
-  void* scan_tmp = nullptr;
-  uint32_t cur = n, base = 0, passes = 0;
-  int a = 0;
-  const size_t mark = arena.off;  // (the radix-tree fallback reuses the arena: everything taken here is handed back on return)
-  for (int k = 0; k < 2; k++) { cl_ref[k] = arena.take<uint32_t>(n); cl_box[k] = arena.take<Box>(n); }
-  nn = arena.take<uint32_t>(n); merge_flag = arena.take<uint32_t>(n); keep_flag = arena.take<uint32_t>(n); node_off = arena.take<uint32_t>(n);
-  pos = arena.take<uint32_t>(n); counts = arena.take<uint32_t>(2);
-  scan_tmp = arena.take<char>(scan_bytes);
-  if (!scan_tmp && scan_bytes) { arena.off = mark; return hipErrorOutOfMemory; }
-  hipLaunchKernelGGL(k_ploc_init, dim3((n + 255) / 256), dim3(256), 0, s, n, leaf_boxes, order, cl_ref[0], cl_box[0]);
-  while (cur > 1) {
-    if (cur <= kPlocTail) {  // the rest in one launch
-      hipLaunchKernelGGL(k_ploc_tail, dim3(1), dim3(1024), 0, s, cur, base, cl_ref[a], cl_box[a], children, node_boxes, counts);
-      uint32_t h[2];
-      LB_CHECK(hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, s));
-      LB_CHECK(hipStreamSynchronize(s));
-      if (h[1] != 1 || h[0] > n - 1) goto done;
-      base = h[0];
-      cur = 1;
-      break;
-    }
-    if (++passes > 256) goto done;  // >= 1 merge per pass is guaranteed, ~30 % per pass is typical: this is a degenerate input
-    const uint32_t blocks = (cur + 255) / 256;
-    hipLaunchKernelGGL(k_ploc_nn, dim3(blocks), dim3(256), 0, s, cur, cl_box[a], nn);
-    hipLaunchKernelGGL(k_ploc_flags, dim3(blocks), dim3(256), 0, s, cur, nn, merge_flag, keep_flag);
-    LB_CHECK(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, merge_flag, node_off, (int)cur, s));
-    LB_CHECK(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, keep_flag, pos, (int)cur, s));
-    hipLaunchKernelGGL(k_ploc_apply, dim3(blocks), dim3(256), 0, s, cur, nn, merge_flag, keep_flag, node_off, pos, base, cl_ref[a], cl_box[a],
-                       cl_ref[a ^ 1], cl_box[a ^ 1], children, node_boxes, counts);
-    uint32_t h[2];
-    LB_CHECK(hipMemcpyAsync(h, counts, sizeof(h), hipMemcpyDeviceToHost, s));
-    LB_CHECK(hipStreamSynchronize(s));
-    if (h[0] == 0 || h[1] != cur - h[0] || base + h[0] > n - 1) goto done;  // no progress / inconsistent: fall back
-    base += h[0];
-    cur = h[1];
-    a ^= 1;
-  }
-  if (base == n - 1) {
-    *root = n - 2;  // the last node created
-    *ok = true;
-  }
-done:
-  arena.off = mark;
-  return err;
-}
-
-
-// The device-driven build: PLOC passes, PLOC tail and collapse levels launched back to back (kernels above); the host reads the state
-// after each batch of passes / levels (2 + 1-2 read-backs on C3 where there were 46).  PTAMD_BVH_LEGACY=1 selects the per-pass / per-level launches (the fallback, kept for A/B).
 constexpr uint32_t kPlocBlocks = 1024;
-static bool device_driven_build() { static const bool on = getenv("PTAMD_BVH_LEGACY") == nullptr; return on; }
-static size_t dev_scratch_bytes(uint32_t n) {
+static size_t dev_scratch_bytes(uint32_t n) {  // ploc_dev's cluster buffers, and the BuildState both halves of the build share
   return 2 * (Arena::pad(sizeof(uint32_t) * (size_t)n) + Arena::pad(sizeof(Box) * (size_t)n)) + Arena::pad(sizeof(uint32_t) * (size_t)n) +
-         Arena::pad(sizeof(uint2) * (size_t)kPlocBlocks) + Arena::pad(2 * sizeof(uint32_t)) + Arena::pad(sizeof(BuildState));
+         Arena::pad(sizeof(uint2) * (size_t)kPlocBlocks) + Arena::pad(sizeof(BuildState));
 }
-// children[] / node_boxes[] / nodes_out are filled on success (*ok): *emitted 4-wide nodes in *levels levels, root = dense node 0.
-static hipError_t build_dev(hipStream_t s, uint32_t n, const Box* leaf_boxes, const uint32_t* order, uint32_t stack_capacity, uint2* children,
-                            Box* node_boxes, uint2* q0, uint2* q1, uint32_t ref_base, uint32_t leaf_tag, uint32_t remap, BvhNode* nodes_out,
-                            bool wide6, uint32_t* tri_perm, Arena& arena, bool* ok, uint32_t* emitted, uint32_t* levels) {
+
+// The binary tree by PLOC over the Morton order `order` (n >= 2): fills children[] / node_boxes[] (n - 1 slots; the root is the last node
+// created, n - 2).  The host reads the state after each batch of passes (2 read-backs on C3).  *ok = false when it gave up there
+// (PlocSlot::ok, the pass limit); what the tail decides stays on the device (BuildState::tree_ok) and reaches the host with the collapse's
+// first read-back.
+static hipError_t ploc_dev(hipStream_t s, uint32_t n, const Box* leaf_boxes, const uint32_t* order, uint2* children, Box* node_boxes, BuildState* st,
+                           Arena& arena, bool* ok) {
   hipError_t err = hipSuccess;
   *ok = false;
-  const size_t mark = arena.off;
+  const size_t mark = arena.off;  // (everything taken here is handed back on return)
   uint32_t* ref0 = arena.take<uint32_t>(n); Box* box0 = arena.take<Box>(n);
   uint32_t* ref1 = arena.take<uint32_t>(n); Box* box1 = arena.take<Box>(n);
   uint32_t* nn = arena.take<uint32_t>(n);
   uint2* block_counts = arena.take<uint2>(kPlocBlocks);
-  uint32_t* counts = arena.take<uint32_t>(2);
-  BuildState* st = arena.take<BuildState>(1);
-  BuildState h;
-  uint32_t pass = 0, bound = n, level = 0, level_bound = 1, done_levels = 0, total = 0;
-  bool finished = false;
-  if (!st) { arena.off = mark; return hipErrorOutOfMemory; }
-  LB_CHECK(hipMemsetAsync(st, 0, sizeof(BuildState), s));
-  hipLaunchKernelGGL(k_ploc_state_init, dim3(1), dim3(1), 0, s, st, n);
+  PlocSlot h;
+  uint32_t pass = 0, bound = n;
+  if (!block_counts) { arena.off = mark; return hipErrorOutOfMemory; }
+  hipLaunchKernelGGL(k_state_init, dim3(1), dim3(1), 0, s, st, n, 0u);
   hipLaunchKernelGGL(k_ploc_init, dim3((n + 255) / 256), dim3(256), 0, s, n, leaf_boxes, order, ref0, box0);
-  // ---- PLOC passes down to kPlocTail clusters: as many as the count the host last saw should need (a pass keeps <~ 80 % of the clusters);
-  //      passes that turn out to be one too many do nothing ----
+  // passes down to kPlocTail clusters: as many as the count the host last saw should need (a pass keeps <~ 80 % of the clusters); passes
+  // that turn out to be one too many do nothing
   while (bound > kPlocTail) {
     if (pass > 256) goto done;  // >= 1 merge per pass is guaranteed, ~25 % per pass is typical: a degenerate input (-> radix tree)
     const uint32_t blocks = (bound + 255) / 256;
@@ -883,104 +755,132 @@ static hipError_t build_dev(hipStream_t s, uint32_t n, const Box* leaf_boxes, co
       hipLaunchKernelGGL(k_ploc_count_dev, dim3(tiles), dim3(256), 0, s, st, pass, nn, block_counts);
       hipLaunchKernelGGL(k_ploc_apply_dev, dim3(tiles), dim3(256), 0, s, st, pass, n, nn, block_counts, ref0, ref1, box0, box1, children, node_boxes);
     }
-    LB_CHECK(hipMemcpyAsync(&h.ploc[0], &st->ploc[pass & 1u], sizeof(PlocSlot), hipMemcpyDeviceToHost, s));
+    LB_CHECK(hipMemcpyAsync(&h, &st->ploc[pass & 1u], sizeof(PlocSlot), hipMemcpyDeviceToHost, s));
     LB_CHECK(hipStreamSynchronize(s));
-    if (!h.ploc[0].ok || h.ploc[0].cur > bound) goto done;
-    bound = h.ploc[0].cur;
+    if (!h.ok || h.cur > bound) goto done;
+    bound = h.cur;
   }
-  hipLaunchKernelGGL(k_ploc_tail_dev, dim3(1), dim3(1024), 0, s, st, pass & 1u, n, ref0, ref1, box0, box1, children, node_boxes, counts);
-  // ---- level-synchronous SAH collapse; the root is the last binary node created.  First batch: the levels a balanced tree has and
-  //      eight more; further batches of six while the last level still queued something ----
-  hipLaunchKernelGGL(k_seed_queue, dim3(1), dim3(1), 0, s, q0, counts, n - 2);
-  {
-    const uint32_t width = wide6 ? 6u : 4u;
-    uint32_t allowed = std::min<uint32_t>(stack_capacity / (width - 1), kMaxLevels - 1);  // levels the traversal stack can hold (width - 1 pushes per level)
-    if (wide6) if (const char* e = getenv("PTAMD_TEST_W6_LEVELS")) allowed = std::min<uint32_t>(allowed, (uint32_t)std::max(1, atoi(e)));  // test hook: makes the 6-wide
-                                                                                         // form "too deep" so that the retry in the 4-wide form runs (tests/test_gpu_parity.py)
-    const uint32_t head = std::min(wide6 ? 4u : kHeadLevels, allowed);                          // width^(head - 1) <= 1 024
-    auto grow = [&](uint32_t b) { return b > n / width ? n : b * width; };
-    if (head) {
-      if (wide6) hipLaunchKernelGGL(k_emit_sah_head<true>, dim3(1), dim3(1024), 0, s, st, pass & 1u, head, q0, q1, st->level_count, ref_base, leaf_tag, remap, children,
-                                    leaf_boxes, order, node_boxes, tri_perm, nodes_out);
-      else hipLaunchKernelGGL(k_emit_sah_head<false>, dim3(1), dim3(1024), 0, s, st, pass & 1u, head, q0, q1, st->level_count, ref_base, leaf_tag, remap, children,
-                              leaf_boxes, order, node_boxes, tri_perm, nodes_out);
+  hipLaunchKernelGGL(k_ploc_tail_dev, dim3(1), dim3(1024), 0, s, st, pass & 1u, n, ref0, ref1, box0, box1, children, node_boxes);
+  *ok = true;
+done:
+  arena.off = mark;
+  return err;
+}
+
+// The Karras radix tree over the sorted keys: fills children[] / node_boxes[] (root 0) and, for k_emit, parent_int[] and depth[0] = the
+// deepest leaf's binary depth.
+static hipError_t radix_tree(hipStream_t s, uint32_t n, const uint64_t* keys, const Box* leaf_boxes, const uint32_t* order, uint2* children,
+                             uint32_t* parent_int, uint32_t* parent_leaf, Box* node_boxes, uint32_t* flags, uint32_t* depth, BuildState* st) {
+  const uint32_t blocks = (n + 255) / 256;
+  hipError_t e = hipMemsetAsync(flags, 0, sizeof(uint32_t) * (size_t)(n - 1), s);
+  if (e == hipSuccess) e = hipMemsetAsync(depth, 0, 2 * sizeof(uint32_t), s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_state_init, dim3(1), dim3(1), 0, s, st, n, 1u);
+  hipLaunchKernelGGL(k_karras, dim3(blocks), dim3(256), 0, s, keys, (int)n, children, parent_int, parent_leaf);
+  hipLaunchKernelGGL(k_refit, dim3(blocks), dim3(256), 0, s, (int)n, children, parent_int, parent_leaf, leaf_boxes, order, node_boxes, flags, depth);
+  return hipSuccess;
+}
+
+// Level-synchronous SAH collapse of the binary tree under `root` into nodes_out, 6-wide (`wide6`: BvhNode6 + tri_perm) or 4-wide: the head
+// launch, then batches of levels with a read-back after each (1-2 on C3).  First batch: the levels a balanced tree has and eight more;
+// further batches of six while the last level still queued something.  *ok: *emitted nodes in *levels levels, root = dense node 0;
+// !*ok: the binary tree is not whole (BuildState::tree_ok) or the wide tree is deeper than the traversal stack holds.
+static hipError_t collapse_dev(hipStream_t s, uint32_t n, uint32_t root, bool wide6, uint32_t stack_capacity, const Box* leaf_boxes, const uint32_t* order,
+                               const uint2* children, const Box* node_boxes, uint2* q0, uint2* q1, uint32_t ref_base, uint32_t leaf_tag, uint32_t remap,
+                               BvhNode* nodes_out, uint32_t* tri_perm, BuildState* st, bool* ok, uint32_t* emitted, uint32_t* levels) {
+  hipError_t err = hipSuccess;
+  *ok = false;
+  BuildState h;
+  const auto head_kernel = wide6 ? k_emit_sah_head<true> : k_emit_sah_head<false>;
+  const auto level_kernel = wide6 ? k_emit_sah_dev<true> : k_emit_sah_dev<false>;
+  const uint32_t width = wide6 ? 6u : 4u;
+  uint32_t allowed = std::min<uint32_t>(stack_capacity / (width - 1), kMaxLevels - 1);  // levels the traversal stack can hold (width - 1 pushes per level)
+  if (wide6) if (const char* e = getenv("PTAMD_TEST_W6_LEVELS")) allowed = std::min<uint32_t>(allowed, (uint32_t)std::max(1, atoi(e)));  // test hook: makes the 6-wide
+                                                                                       // form "too deep" so that the retry in the 4-wide form runs (tests/test_gpu_parity.py)
+  const uint32_t head = std::min(wide6 ? 4u : kHeadLevels, allowed);                          // width^(head - 1) <= 1 024
+  auto grow = [&](uint32_t b) { return b > n / width ? n : b * width; };
+  uint32_t level = head, level_bound = 1, done_levels = 0, total = 0;
+  bool finished = false;
+  hipLaunchKernelGGL(k_seed_queue, dim3(1), dim3(kMaxLevels), 0, s, st, q0, root);
+  if (head) hipLaunchKernelGGL(head_kernel, dim3(1), dim3(1024), 0, s, st, head, q0, q1, st->level_count, ref_base, leaf_tag, remap, children, leaf_boxes, order,
+                               node_boxes, tri_perm, nodes_out);
+  for (uint32_t l = 0; l < head; l++) level_bound = grow(level_bound);
+  uint32_t batch = (uint32_t)std::ceil(std::log((double)n) / std::log((double)width)) + 8;
+  batch = batch > head ? batch - head : 1;
+  while (!finished) {
+    for (uint32_t k = 0; k < batch && level < allowed; k++, level++) {
+      hipLaunchKernelGGL(level_kernel, dim3((level_bound + 255) / 256), dim3(256), 0, s, st, level, (level & 1u) ? q1 : q0, (level & 1u) ? q0 : q1, st->level_count,
+                         ref_base, leaf_tag, remap, children, leaf_boxes, order, node_boxes, tri_perm, nodes_out);
+      level_bound = grow(level_bound);
     }
-    level = head;
-    for (uint32_t l = 0; l < head; l++) level_bound = grow(level_bound);
-    uint32_t batch = (uint32_t)std::ceil(std::log((double)n) / std::log((double)width)) + 8;
-    batch = batch > head ? batch - head : 1;
-    while (!finished) {
-      for (uint32_t k = 0; k < batch && level < allowed; k++, level++) {
-        if (wide6) hipLaunchKernelGGL(k_emit_sah_dev<true>, dim3((level_bound + 255) / 256), dim3(256), 0, s, st, pass & 1u, level, (level & 1u) ? q1 : q0,
-                                      (level & 1u) ? q0 : q1, st->level_count, ref_base, leaf_tag, remap, children, leaf_boxes, order, node_boxes, tri_perm, nodes_out);
-        else hipLaunchKernelGGL(k_emit_sah_dev<false>, dim3((level_bound + 255) / 256), dim3(256), 0, s, st, pass & 1u, level, (level & 1u) ? q1 : q0,
-                                (level & 1u) ? q0 : q1, st->level_count, ref_base, leaf_tag, remap, children, leaf_boxes, order, node_boxes, tri_perm, nodes_out);
-        level_bound = grow(level_bound);
-      }
-      batch = 6;
-      LB_CHECK(hipMemcpyAsync(&h, st, sizeof(BuildState), hipMemcpyDeviceToHost, s));
-      LB_CHECK(hipStreamSynchronize(s));
-      if (!h.ploc[pass & 1u].ok) goto done;
-      // levels done so far: level l exists when l == 0 or level l - 1 queued something for it
-      total = 0; done_levels = 0;
-      for (uint32_t l = 0, n_in = 1; l < level && n_in > 0; l++) { total += n_in; done_levels = l + 1; n_in = h.level_count[l]; finished = n_in == 0; }
-      if (!finished) {
-        if (level >= allowed) goto done;  // deeper than the traversal stack: the caller falls back
-        level_bound = std::min<uint64_t>((uint64_t)h.level_count[level - 1], (uint64_t)n);  // the next level's real size
-      }
+    batch = 6;
+    LB_CHECK(hipMemcpyAsync(&h, st, sizeof(BuildState), hipMemcpyDeviceToHost, s));
+    LB_CHECK(hipStreamSynchronize(s));
+    if (!h.tree_ok) goto done;
+    // levels done so far: level l exists when l == 0 or level l - 1 queued something for it
+    total = 0; done_levels = 0;
+    for (uint32_t l = 0, n_in = 1; l < level && n_in > 0; l++) { total += n_in; done_levels = l + 1; n_in = h.level_count[l]; finished = n_in == 0; }
+    if (!finished) {
+      if (level >= allowed) goto done;  // deeper than the traversal stack: the caller falls back
+      level_bound = std::min<uint64_t>((uint64_t)h.level_count[level - 1], (uint64_t)n);  // the next level's real size
     }
-    if (wide6 && h.leaf_count != n) goto done;  // (every triangle gets exactly one slot)
   }
+  if (wide6 && h.leaf_count != n) goto done;  // (every triangle gets exactly one slot)
   if (total >= 1 && total <= n - 1) {
     *ok = true;
     *emitted = total;
     *levels = done_levels;
   }
 done:
-  arena.off = mark;
   return err;
 }
 
 // ---- one tree ------------------------------------------------------------------------------------------------------------
 struct TreeInfo { uint32_t root_ref = kInvalidRef, node_span = 0, depth4 = 0; bool wide6 = false; };
 
-// A 4-wide quantised BVH over n >= 1 leaf boxes (device memory), written at nodes_out[0 .. node_span): Morton order (rocPRIM
-// radix sort) -> PLOC binary tree (Karras radix tree as the fallback) -> SAH-guided 4-wide collapse, dense in BFS order.
+// A quantised wide BVH over n >= 1 leaf boxes (device memory), written at nodes_out[0 .. node_span): Morton order (rocPRIM radix sort) ->
+// PLOC binary tree (the Karras radix tree when asked for, or when PLOC gives up) -> SAH-guided collapse, dense in BFS order.
 // Internal child refs are `ref_base + index`, leaf refs `leaf_tag | id` with id = the leaf's index in leaf_boxes[] when
 // `remap`, its position in the Morton order otherwise (the caller then reorders its leaf array by order_out[], n entries,
 // sorted position -> index).  nodes_out needs room for n - 1 records.
-static hipError_t tree_arena_bytes(uint32_t n, size_t* sort_bytes_out, size_t* scan_bytes_out, size_t* bytes) {
-  size_t sort_bytes = 0, scan_bytes = 0;
+static hipError_t tree_arena_bytes(uint32_t n, size_t* sort_bytes_out, size_t* bytes) {
+  size_t sort_bytes = 0;
   *bytes = 0;
   if (n >= 2) {
     hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 63, 0);
     if (e != hipSuccess) return e;
     const size_t N = n;
-    *bytes = Arena::pad(sizeof(int) * 8) + Arena::pad(4 * sizeof(uint32_t)) + 2 * Arena::pad(sizeof(uint64_t) * N) + 2 * Arena::pad(sizeof(uint32_t) * N) +
+    *bytes = Arena::pad(sizeof(int) * 8) + Arena::pad(2 * sizeof(uint32_t)) + 2 * Arena::pad(sizeof(uint64_t) * N) + 2 * Arena::pad(sizeof(uint32_t) * N) +
              Arena::pad(sizeof(uint2) * (N - 1)) + Arena::pad(sizeof(uint32_t) * (N - 1)) + Arena::pad(sizeof(uint32_t) * N) + Arena::pad(sizeof(uint32_t) * (N - 1)) +
-             Arena::pad(sizeof(Box) * (N - 1)) + 2 * Arena::pad(sizeof(uint2) * N) + Arena::pad(sort_bytes) +
-             std::max(ploc_scratch_bytes(n, &scan_bytes), dev_scratch_bytes(n));
+             Arena::pad(sizeof(Box) * (N - 1)) + 2 * Arena::pad(sizeof(uint2) * N) + Arena::pad(sort_bytes) + dev_scratch_bytes(n);
   }
   if (sort_bytes_out) *sort_bytes_out = sort_bytes;
-  if (scan_bytes_out) *scan_bytes_out = scan_bytes;
   return hipSuccess;
 }
 // (`scratch`: tree_arena_bytes(n) bytes of device memory, the caller's)
-// `tri_perm_out` != nullptr asks for the 6-wide form (BvhNode6: ref_base 0, no remap): info->wide6 says whether it was built (only the
-// device-driven PLOC path builds it; the fallbacks give the 4-wide form) — tri_perm_out[slot] = position in the Morton order.
+// `tri_perm_out` != nullptr asks for the 6-wide form (BvhNode6: ref_base 0, no remap): info->wide6 says whether it was built (only from a
+// PLOC tree, below kMaxWide6Triangles, without $PTAMD_BVH4 and when the stack holds its levels; everything else is the 4-wide form) —
+// tri_perm_out[slot] = position in the Morton order.
 static hipError_t build_tree(hipStream_t s, uint32_t n, const Box* leaf_boxes, uint32_t stack_capacity, bool use_ploc, BvhNode* nodes_out,
                              uint32_t ref_base, uint32_t leaf_tag, bool remap, uint32_t* order_out, uint32_t* tri_perm_out, char* scratch,
                              size_t scratch_bytes, TreeInfo* info) {
   hipError_t err = hipSuccess;
   *info = TreeInfo{};
   const uint32_t blocks = (n + 255) / 256;
+  const bool want6 = tri_perm_out != nullptr && n < kMaxWide6Triangles && getenv("PTAMD_BVH4") == nullptr;
   Box* node_boxes = nullptr;
   uint64_t *keys_a = nullptr, *keys_b = nullptr; uint32_t *vals_a = nullptr, *vals_b = nullptr;
   uint2 *children = nullptr, *queue[2] = {nullptr, nullptr}; uint32_t *parent_int = nullptr, *parent_leaf = nullptr, *flags = nullptr;
-  int* bounds = nullptr; uint32_t* counters = nullptr; void* sort_tmp = nullptr; size_t sort_bytes = 0, scan_bytes = 0;
-  uint32_t depth_h[2] = {0, 0};
-  uint32_t root = 0, binary_depth = 0;
+  int* bounds = nullptr; uint32_t* counters = nullptr; void* sort_tmp = nullptr; size_t sort_bytes = 0;
+  BuildState* st = nullptr;
+  uint32_t binary_depth = 0, emitted = 0, levels = 0;
+  bool ploc = use_ploc, ok = false;  // ploc: the binary tree in children[] is PLOC's (root n - 2), not the radix tree (root 0)
   Arena arena;
+  auto radix = [&] { return radix_tree(s, n, keys_b, leaf_boxes, vals_b, children, parent_int, parent_leaf, node_boxes, flags, counters, st); };
+  auto collapse = [&](bool wide6) {
+    return collapse_dev(s, n, ploc ? n - 2 : 0u, wide6, stack_capacity, leaf_boxes, vals_b, children, node_boxes, queue[0], queue[1], ref_base, leaf_tag,
+                        remap ? 1u : 0u, nodes_out, tri_perm_out, st, &ok, &emitted, &levels);
+  };
 
   if (n == 1) {
     const uint32_t zero = 0;
@@ -989,12 +889,11 @@ static hipError_t build_tree(hipStream_t s, uint32_t n, const Box* leaf_boxes, u
     info->root_ref = leaf_tag | 0u;
     return hipSuccess;
   }
-  LB_CHECK(tree_arena_bytes(n, &sort_bytes, &scan_bytes, &arena.cap));
+  LB_CHECK(tree_arena_bytes(n, &sort_bytes, &arena.cap));
   if (arena.cap > scratch_bytes) return hipErrorOutOfMemory;  // (the callers size the scratch with tree_arena_bytes)
   arena.base = scratch;
   bounds = arena.take<int>(8);
-  counters = arena.take<uint32_t>(4);  // [0] max binary depth, [1] emitted (fallback), [2] next level size, [3] unused
-  LB_CHECK(hipMemsetAsync(counters, 0, 4 * sizeof(uint32_t), s));
+  counters = arena.take<uint32_t>(2);  // radix tree: [0] max binary depth, [1] k_emit's node count
   keys_a = arena.take<uint64_t>(n); keys_b = arena.take<uint64_t>(n);
   vals_a = arena.take<uint32_t>(n); vals_b = arena.take<uint32_t>(n);
   children = arena.take<uint2>(n - 1);
@@ -1004,89 +903,41 @@ static hipError_t build_tree(hipStream_t s, uint32_t n, const Box* leaf_boxes, u
   node_boxes = arena.take<Box>(n - 1);
   for (int k = 0; k < 2; k++) queue[k] = arena.take<uint2>(n);
   sort_tmp = arena.take<char>(sort_bytes);
+  st = arena.take<BuildState>(1);
 
   hipLaunchKernelGGL(k_init_bounds, dim3(1), dim3(64), 0, s, bounds);
   hipLaunchKernelGGL(k_bounds, dim3(blocks < 256 ? blocks : 256), dim3(256), 0, s, leaf_boxes, n, bounds);
   hipLaunchKernelGGL(k_morton, dim3(blocks), dim3(256), 0, s, leaf_boxes, n, bounds, keys_a, vals_a);
   LB_CHECK(hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, keys_a, keys_b, vals_a, vals_b, (int)n, 0, 63, s));
 
-  for (;;) {
-    if (use_ploc && device_driven_build()) {
-      // PLOC + collapse without host round trips; anything it cannot finish (pass limit, a tree deeper than the stack) goes the old way
-      bool ok = false;
-      uint32_t emitted = 0, levels = 0;
-      const bool wide6 = tri_perm_out != nullptr && n >= 2 && n < kMaxWide6Triangles && getenv("PTAMD_BVH4") == nullptr;
-      LB_CHECK(build_dev(s, n, leaf_boxes, vals_b, stack_capacity, children, node_boxes, queue[0], queue[1], ref_base, leaf_tag, remap ? 1u : 0u,
-                          nodes_out, wide6, tri_perm_out, arena, &ok, &emitted, &levels));
-      if (!ok && wide6) {  // (e.g. deeper than the stack at five pushes per level: the 4-wide form needs three)
-        LB_CHECK(build_dev(s, n, leaf_boxes, vals_b, stack_capacity, children, node_boxes, queue[0], queue[1], ref_base, leaf_tag, remap ? 1u : 0u,
-                            nodes_out, false, nullptr, arena, &ok, &emitted, &levels));
-      } else if (ok) info->wide6 = wide6;
-      if (ok) {
-        info->root_ref = ref_base + 0u;
-        if (order_out) LB_CHECK(hipMemcpyAsync(order_out, vals_b, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
-        LB_CHECK(hipGetLastError());
-        LB_CHECK(hipStreamSynchronize(s));
-        info->node_span = emitted;
-        info->depth4 = levels;
-        break;
-      }
-      use_ploc = false;
-      continue;
-    }
-    if (use_ploc) {
-      bool ok = false;
-      LB_CHECK(ploc_build(s, n, leaf_boxes, vals_b, children, node_boxes, &root, &ok, arena, scan_bytes));
-      if (!ok) { use_ploc = false; continue; }
-    } else {
-      LB_CHECK(hipMemsetAsync(flags, 0, sizeof(uint32_t) * (size_t)(n - 1), s));
-      LB_CHECK(hipMemsetAsync(counters, 0, 4 * sizeof(uint32_t), s));
-      hipLaunchKernelGGL(k_karras, dim3(blocks), dim3(256), 0, s, keys_b, (int)n, children, parent_int, parent_leaf);
-      hipLaunchKernelGGL(k_refit, dim3(blocks), dim3(256), 0, s, (int)n, children, parent_int, parent_leaf, leaf_boxes, vals_b,
-                         node_boxes, flags, counters);
-      LB_CHECK(hipMemcpyAsync(depth_h, counters, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      LB_CHECK(hipStreamSynchronize(s));
-      binary_depth = depth_h[0];
-      root = 0;
-    }
-    // level-synchronous SAH collapse, dense BFS numbering
-    uint2 *q_in = queue[0], *q_out = queue[1];
-    hipLaunchKernelGGL(k_seed_queue, dim3(1), dim3(1), 0, s, q_in, counters + 2, root);
-    uint32_t n_in = 1, levels = 0, emitted = 0;
-    bool too_deep = false;
-    while (n_in > 0) {
-      if ((levels + 1) * 3 > stack_capacity) { too_deep = true; break; }
-      hipLaunchKernelGGL(k_emit_sah, dim3((n_in + 255) / 256), dim3(256), 0, s, n_in, q_in, q_out, counters + 2, emitted + n_in, ref_base,
-                         leaf_tag, remap ? 1u : 0u, children, leaf_boxes, vals_b, node_boxes, nodes_out);
-      uint32_t h = 0;
-      LB_CHECK(hipMemcpyAsync(&h, counters + 2, sizeof(h), hipMemcpyDeviceToHost, s));
-      LB_CHECK(hipMemsetAsync(counters + 2, 0, sizeof(uint32_t), s));
-      LB_CHECK(hipStreamSynchronize(s));
-      emitted += n_in;
-      n_in = h;
-      std::swap(q_in, q_out);
-      levels++;
-    }
-    if (too_deep && use_ploc) { use_ploc = false; continue; }  // a pathological cluster tree: try the radix tree
-    if (too_deep) {
-      // pathological radix tree: the even-depth collapse bounds the 4-wide depth by half the binary depth (nodes keep their
-      // binary index: the tree spans n - 1 slots)
-      LB_CHECK(hipMemsetAsync(counters + 1, 0, sizeof(uint32_t), s));
-      hipLaunchKernelGGL(k_emit, dim3(blocks), dim3(256), 0, s, (int)n, children, parent_int, leaf_boxes, vals_b, node_boxes, nodes_out, ref_base,
-                         leaf_tag, remap ? 1u : 0u, counters + 1);
-      emitted = n - 1;
-      levels = (binary_depth + 1) / 2;
-      info->root_ref = ref_base + 0u;
-    } else {
-      info->root_ref = ref_base + 0u;  // the root is dense node 0
-    }
-    if (order_out) LB_CHECK(hipMemcpyAsync(order_out, vals_b, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
-    LB_CHECK(hipGetLastError());
-    LB_CHECK(hipStreamSynchronize(s));
-    info->node_span = emitted;
-    info->depth4 = levels;
-    break;
+  // the binary tree
+  if (ploc) LB_CHECK(ploc_dev(s, n, leaf_boxes, vals_b, children, node_boxes, st, arena, &ploc));
+  if (!ploc) LB_CHECK(radix());
+  // the wide tree: 6-wide from a PLOC tree when asked for; 4-wide on the same binary tree when that is deeper than the stack (five pushes per
+  // level, the 4-wide form needs three); a PLOC tree too deep (or not whole) even so is a pathological cluster tree: the radix tree instead
+  if (ploc && want6) { LB_CHECK(collapse(true)); info->wide6 = ok; }
+  if (!ok) LB_CHECK(collapse(false));
+  if (!ok && ploc) {
+    ploc = false;
+    LB_CHECK(radix());
+    LB_CHECK(collapse(false));
   }
+  if (!ok) {
+    // pathological radix tree: the even-depth collapse bounds the 4-wide depth by half the binary depth (nodes keep their
+    // binary index: the tree spans n - 1 slots)
+    hipLaunchKernelGGL(k_emit, dim3(blocks), dim3(256), 0, s, (int)n, children, parent_int, leaf_boxes, vals_b, node_boxes, nodes_out, ref_base,
+                       leaf_tag, remap ? 1u : 0u, counters + 1);
+    LB_CHECK(hipMemcpyAsync(&binary_depth, counters, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    LB_CHECK(hipStreamSynchronize(s));
+    emitted = n - 1;
+    levels = (binary_depth + 1) / 2;
+  }
+  info->root_ref = ref_base + 0u;  // the root is dense node 0 (k_emit: binary node 0)
+  if (order_out) LB_CHECK(hipMemcpyAsync(order_out, vals_b, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
+  LB_CHECK(hipGetLastError());
+  LB_CHECK(hipStreamSynchronize(s));
+  info->node_span = emitted;
+  info->depth4 = levels;
 
 done:
   return err;
@@ -1123,7 +974,7 @@ hipError_t build_lbvh(hipStream_t s, const DeviceScene& S, const PrimTables& pri
   Arena tmp;  // the flattening's temporaries and, behind them, the tree builder's: one kept allocation (LbvhScratch)
   size_t tree_bytes = 0;
   char* tree_scratch = nullptr;
-  LB_CHECK(tree_arena_bytes(n, nullptr, nullptr, &tree_bytes));
+  LB_CHECK(tree_arena_bytes(n, nullptr, &tree_bytes));
   tmp.cap = Arena::pad(sizeof(TriRec) * (size_t)n) + Arena::pad(sizeof(Box) * (size_t)n) + 2 * Arena::pad(sizeof(uint32_t) * (size_t)n) +
             Arena::pad(sizeof(BvhNode) * (size_t)(n > 1 ? n - 1 : 1)) + Arena::pad(tree_bytes);
   LB_CHECK(scratch->ensure(tmp.cap));
@@ -1237,8 +1088,8 @@ hipError_t build_two_level(hipStream_t s, const DeviceScene& S, const MeshInfo* 
   for (uint32_t m = 0; m < mesh_count; m++) { capacity += meshes[m].tri_count; max_mesh_tris = std::max(max_mesh_tris, meshes[m].tri_count); }
 
   // temporaries: one kept allocation (LbvhScratch); the tree builder's part is sized for the largest tree (TLAS or a BLAS)
-  LB_CHECK(tree_arena_bytes(instance_count, nullptr, nullptr, &tree_bytes));
-  LB_CHECK(tree_arena_bytes(max_mesh_tris, nullptr, nullptr, &tb));
+  LB_CHECK(tree_arena_bytes(instance_count, nullptr, &tree_bytes));
+  LB_CHECK(tree_arena_bytes(max_mesh_tris, nullptr, &tb));
   tree_bytes = std::max(tree_bytes, tb);
   tmp.cap = Arena::pad(sizeof(Box) * (size_t)tri_count) + Arena::pad(sizeof(Box) * (size_t)instance_count) +
             Arena::pad(sizeof(Box) * (size_t)std::max(1u, max_mesh_tris)) + Arena::pad(sizeof(BvhNode) * capacity) + Arena::pad(tree_bytes);

@@ -8,7 +8,6 @@ PAIRED_SIZES = (2, 1024, 1025)
 VARIANT_SIZES = (2, 5, 257, 1024, 1025, 2049)
 VARIANT_LAYOUTS = ("scatter", "expo", "coincident")
 INSTANCE_SIZES = (2, 3, 1024, 1025)
-LEGACY_SIZES = (2, 1024, 1025, 2049)
 
 
 def layout_cases():

@@ -7,8 +7,6 @@ can exist (see _check_structure).  Sizes: a leaf root's neighbours (2 ... 9: roo
 reaching both ends (<= 17), multiples of the 256-thread block, kPlocTail = 1 024 (1 024: the single-block tail does everything; 1 025: a batch
 of two device-driven passes first, the second of which must do nothing), the head kernel's width^(head - 1) <= 1 024, and 4 097."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -41,16 +39,15 @@ def _check_structure(st, trees, triangles, slots, rebuilt_four_wide):
     * A tree over L >= 2 leaves has between ceil((L - 1) / (w - 1)) and L - 1 nodes: emit_sah_node / emit_sah_node6 / k_emit turn one binary node
       into one w-wide node with at most w children, a tree with N nodes has N - 1 + L children, and there are L - 1 binary nodes (k_emit's span
       is exactly L - 1).  L = 1 is a leaf root: no node, no level (build_tree's n == 1 branch).
-    * levels * (w - 1) (+ 1 exit marker in the two-level walk) <= 96: build_dev emits at most stack / (w - 1) levels, the per-level loop stops at
-      (levels + 1) * 3 > stack, and pt_start_render refuses what k_emit's estimate leaves deeper.  The issue states this without the marker; the
+    * levels * (w - 1) (+ 1 exit marker in the two-level walk) <= 96: collapse_dev emits at most stack / (w - 1) levels, and pt_start_render refuses what k_emit's estimate leaves deeper.  The issue states this without the marker; the
       marker is renderer.hip's own check, so it is included here.  A tree of `levels` levels has at most w^levels leaves.
-    * w = 6 for the device-driven one-BVH build, 4 for everything else: $PTAMD_BVH4, the radix tree, the per-pass build ($PTAMD_BVH_LEGACY),
+    * w = 6 for the device-driven one-BVH build, 4 for everything else: $PTAMD_BVH4, the radix tree,
       every tree of the two-level structure — and the default build's own retry (`rebuilt_four_wide`): a 6-wide tree of more than 96 / 5 = 19
-      levels is rebuilt 4-wide by the same build call.  That route is observable: more than 19 levels cannot be a 6-wide tree, so the cases
+      levels is collapsed again 4-wide by the same build call.  That route is observable: more than 19 levels cannot be a 6-wide tree, so the cases
       that take it (_rebuilt_four_wide) must SHOW more than 19 levels and are held to the 4-wide bounds; every other case to the 6-wide ones.
       (Only under a session-wide $PTAMD_TEST_W6_LEVELS, which lowers the 6-wide limit for every scene, is either width accepted, consistently.)"""
     two_level = st.accel_two_level == 1
-    four_wide = two_level or any(v in os.environ for v in ("PTAMD_BVH4", "PTAMD_RADIX_TREE", "PTAMD_BVH_LEGACY"))
+    four_wide = two_level or any(v in os.environ for v in ("PTAMD_BVH4", "PTAMD_RADIX_TREE"))
     either = not four_wide and "PTAMD_TEST_W6_LEVELS" in os.environ
     if rebuilt_four_wide and not four_wide and not either:
         assert st.bvh_max_depth > STACK // 5, "expected the 6-wide tree to be too deep and the 4-wide retry to run: %d levels" % st.bvh_max_depth
@@ -109,9 +106,9 @@ def _mosaic_trees(st, sc, n):
 # The cases whose DEFAULT build leaves the 6-wide form by itself: the PLOC tree of `expo` (depths over fifteen decades) is dozens of binary levels of
 # nested boxes, of which the SAH collapse makes more than 19 6-wide levels at 1 024, 1 025 and 2 049 slots (the 4-wide trees that replace them have 22, 23 and 23 levels; at 257 slots
 # the 6-wide tree has 19: exactly the limit, and stays), so
-# build_tree rebuilds the tree 4-wide.  Every other layout, `coincident` included (its identical boxes pair up as (0, 1)(2, 3)... and halve every
-# pass: a balanced tree), is built 6-wide.  No layout here reaches the 256-pass limit, per-pass PLOC, the radix tree or k_emit by itself, as far as
-# pt_stats can show: those routes are entered through $PTAMD_BVH_LEGACY, $PTAMD_RADIX_TREE and $PTAMD_TEST_W6_LEVELS (below, tests/test_gpu_parity.py).
+# build_tree collapses the same binary tree again 4-wide.  Every other layout, `coincident` included (its identical boxes pair up as (0, 1)(2, 3)... and halve every
+# pass: a balanced tree), is built 6-wide.  No layout here reaches the 256-pass limit, the radix tree or k_emit by itself, as far as
+# pt_stats can show: those routes are entered through $PTAMD_RADIX_TREE and $PTAMD_TEST_W6_LEVELS (below, tests/test_gpu_parity.py).
 def _rebuilt_four_wide(n, layout):
     return layout == "expo" and n >= 1024
 
@@ -158,15 +155,3 @@ def test_builder_tlas_over_n_instances(gpu_renderer, n):
     assert st.accel_two_level == 1
     _check_structure(st, [n, 1], n, n, False)
 
-
-def test_builder_sizes_with_per_pass_launches_in_a_child_process():
-    """$PTAMD_BVH_LEGACY (per-pass PLOC, k_ploc_tail, per-level k_emit_sah) is read once per process, so the sizes test runs again in ONE child
-    process with the variable set, at the sizes around the tail.  The child and this session are the only two processes on the GPU."""
-    skip_if_structure_env_preset()   # (also keeps the child, which has the variable preset, from starting children of its own)
-    here = os.path.abspath(__file__)
-    env = dict(os.environ, PTAMD_BVH_LEGACY="1")
-    cmd = [sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider"] + ["%s::test_builder_sizes[%d]" % (here, n) for n in C.LEGACY_SIZES]
-    # (interpreter + library start-up, one renderer, four brute-force references of at most 2 049 slots: ~10 s; a build that hangs ends here)
-    p = subprocess.run(cmd, env=env, cwd=os.path.dirname(os.path.dirname(here)), capture_output=True, text=True, timeout=180)
-    assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
-    assert "%d passed" % len(C.LEGACY_SIZES) in p.stdout, p.stdout[-1000:]

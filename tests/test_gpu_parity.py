@@ -557,8 +557,7 @@ def test_two_level_structure_gives_the_same_hits_and_radiance(gpu_renderer, whic
 @pytest.mark.parametrize("which", ["field", "fuzz", "textured"])
 def test_four_wide_fallback_form_gives_the_same_hits_and_radiance(gpu_renderer, which, monkeypatch):
     """r03: the device build emits 6-wide nodes (BvhNode6) by default — every other test in this file runs on them.  $PTAMD_BVH4 keeps the
-    4-wide form (what the fallback builders — radix tree, per-pass launches, trees deeper than the stack at five pushes per level — and the
-    two-level structure use); it must give the oracle's answers too, from a tree with more nodes."""
+    4-wide form (what the radix tree, trees deeper than the stack at five pushes per level and the two-level structure get); it must give the oracle's answers too, from a tree with more nodes."""
     skip_if_structure_env_preset()
     cases = {"field": [scenes.field_scene(8)], "fuzz": [scenes.random_scene(s) for s in (3, 7, 11, 19)], "textured": [scenes.textured_scene()]}[which]
     for sc in cases:
