@@ -408,6 +408,22 @@ int pt_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out);
 /* The denoised image (W*H*4 floats, alpha 1).  Blocks.  PT_ERR_BAD_STATE for a render started without AOVs. */
 int pt_read_denoised(pt_renderer* r, float* rgba_out);
 
+/* ---- firefly clamp ahead of the denoiser (NEW, an additive extension of ABI 5: new entry points and one new struct, no existing struct changed) ----
+ * At 1-4 spp a single sample 10-1000x brighter than its neighbours passes the luminance edge-stop of its own pixel and is smeared over the
+ * filter's footprint.  With `enabled` set the denoiser clamps such pixels between its prep and its first a-trous step: a valid pixel whose
+ * demodulated luminance L exceeds lim = threshold * M, M the largest luminance among its up to 8 neighbours in the 3x3 window (valid, of its
+ * own class geometry / background, inside the image or the render region), becomes I * (lim / L); its variance is kept.  A pixel with no such
+ * neighbour is left alone.  The clamp needs iterations >= 1: iterations = 0 returns the accumulator either way.
+ * The options take effect at the next pt_read_denoised, or read / present with apply_to_target; no restart is needed.  enabled = 0 gives
+ * the bits of a library without the clamp.  A device group refuses enabled = 1 with PT_ERR_UNSUPPORTED, like the denoiser. */
+typedef struct pt_despeckle_options {
+  uint32_t enabled;   /* default 0 */
+  float threshold;    /* finite and >= 1; default 2 */
+} pt_despeckle_options;
+void pt_default_despeckle_options(pt_despeckle_options* o);
+/* PT_ERR_INVALID_ARGUMENT for a threshold that is not finite or < 1 (checked before the renderer) */
+int pt_set_despeckle_options(pt_renderer* r, const pt_despeckle_options* o);
+
 /* ---- tile-adaptive sampling (NEW, an additive extension of ABI 5: new entry points and one new struct, no existing struct changed) ----
  * A render started while `enabled` is set stops sampling an 8x8 tile of the accumulator once it has converged; pt_render_params.spp
  * becomes the per-pixel maximum.  Checkpoints are at the sample counts c_k = min_spp + k * interval with c_k < spp.  At each, every

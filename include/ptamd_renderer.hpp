@@ -31,6 +31,9 @@
  *   (no counterpart)                                             pt_denoise_options& denoiseOptions() / setDenoiseOptions(...), readbackAov(kind),
  *                                                                readbackDenoised(): first-hit AOVs and the a-trous denoiser (ptamd.h, ABI 5);
  *                                                                `enabled` is handed over at startRender, the rest whenever an image is asked for
+ *   (no counterpart)                                             pt_despeckle_options& despeckleOptions() / setDespeckleOptions(...): the firefly
+ *                                                                clamp ahead of the filter (ptamd.h, ABI 5 extension); handed over whenever an
+ *                                                                image is asked for
  *   (no counterpart)                                             pt_adaptive_options& adaptiveOptions() / setAdaptiveOptions(...),
  *                                                                readbackSampleCounts(): tile-adaptive sampling (ptamd.h, ABI 5 extension);
  *                                                                handed over at startRender
@@ -193,11 +196,17 @@ public:
   // The denoised image, W*H RGBA32F; empty for a render started without AOVs.  Blocks.
   [[nodiscard]] std::vector<float> readbackDenoised() const {
     std::vector<float> out;
-    if (!m_pt || !m_started || !check(pt_set_gmon_options(m_pt, &m_gmonOptions)) || !check(pt_set_denoise_options(m_pt, &m_denoise))) return out;
+    if (!m_pt || !m_started || !check(pt_set_gmon_options(m_pt, &m_gmonOptions)) || !check(pt_set_denoise_options(m_pt, &m_denoise)) ||
+        !check(pt_set_despeckle_options(m_pt, &m_despeckle)))
+      return out;
     out.resize((size_t)m_size.x * m_size.y * 4);
     if (!check(pt_read_denoised(m_pt, out.data()))) out.clear();
     return out;
   }
+  // The firefly clamp ahead of the a-trous filter (ptamd.h, an additive extension of ABI 5).  Edited in place like denoiseOptions(); read
+  // whenever a denoised image is asked for, no restart needed.
+  [[nodiscard]] constexpr pt_despeckle_options& despeckleOptions() { return m_despeckle; }
+  void setDespeckleOptions(const pt_despeckle_options& o) { m_despeckle = o; }
   // Tile-adaptive sampling (ptamd.h, an additive extension of ABI 5).  Edited in place like denoiseOptions(); read at startRender.
   [[nodiscard]] constexpr pt_adaptive_options& adaptiveOptions() { return m_adaptive; }
   void setAdaptiveOptions(const pt_adaptive_options& o) { m_adaptive = o; }
@@ -225,6 +234,7 @@ private:
     pt_default_tonemap_options(&defaults);
     m_outputSpace = defaults.output_space;   // Display P3 (renderer_pt.hpp:182)
     pt_default_denoise_options(&m_denoise);
+    pt_default_despeckle_options(&m_despeckle);
     pt_default_adaptive_options(&m_adaptive);
     pt_default_render_region(&m_region);
     std::vector<int32_t> ord(devices, devices + count);
@@ -249,7 +259,7 @@ private:
     postprocess::flatten(m_exposure, m_chromaticAberration, m_contrastSaturation, m_toneCurve, m_vignette, &post);
     postprocess::flatten(m_tonemap, m_outputSpace, &tonemap);
     return check(pt_set_gmon_options(m_pt, &m_gmonOptions)) && check(pt_set_post_options(m_pt, &post)) && check(pt_set_tonemap_options(m_pt, &tonemap)) &&
-           check(pt_set_denoise_options(m_pt, &m_denoise));
+           check(pt_set_denoise_options(m_pt, &m_denoise)) && check(pt_set_despeckle_options(m_pt, &m_despeckle));
   }
 
   pt_renderer* m_pt = nullptr;
@@ -267,6 +277,7 @@ private:
   pt_colorspace m_outputSpace{};
   pt_gmon_options m_gmonOptions{1.0f};
   pt_denoise_options m_denoise{};
+  pt_despeckle_options m_despeckle{};
   pt_adaptive_options m_adaptive{};
   pt_render_region m_region{};
   mutable void* m_presentStream = nullptr;

@@ -176,6 +176,11 @@ class DenoiseOptions(C.Structure):
 AOV_ALBEDO, AOV_NORMAL, AOV_MOMENTS = 0, 1, 2
 
 
+class DespeckleOptions(C.Structure):
+    """pt_despeckle_options: the firefly clamp ahead of the a-trous filter; threshold finite and >= 1."""
+    _fields_ = [("enabled", C.c_uint32), ("threshold", C.c_float)]
+
+
 class AdaptiveOptions(C.Structure):
     _fields_ = [("enabled", C.c_uint32), ("threshold", C.c_float), ("min_spp", C.c_uint32), ("interval", C.c_uint32)]
 
@@ -244,6 +249,8 @@ SYMBOLS = [
     ("pt_set_denoise_options", C.c_int, [C.c_void_p, C.POINTER(DenoiseOptions)]),
     ("pt_read_aov", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     ("pt_read_denoised", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("pt_default_despeckle_options", None, [C.POINTER(DespeckleOptions)]),
+    ("pt_set_despeckle_options", C.c_int, [C.c_void_p, C.POINTER(DespeckleOptions)]),
     ("pt_default_adaptive_options", None, [C.POINTER(AdaptiveOptions)]),
     ("pt_set_adaptive_options", C.c_int, [C.c_void_p, C.POINTER(AdaptiveOptions)]),
     ("pt_read_sample_counts", C.c_int, [C.c_void_p, C.c_void_p]),

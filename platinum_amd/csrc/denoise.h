@@ -20,9 +20,10 @@ void launch_accumulate_aov_adaptive(hipStream_t s, vec4* albedo, vec4* normal, v
 // The filter over the rectangle `rect` of the current W x H image, as if the rectangle were the whole image (the whole frame: {0, 0, W, H}):
 // prep, `iterations` a-trous steps, the last one remodulated into `out` (W*H vec4; pixels outside rect are left as they are).
 // guide / aux / col0 / col1 are W*H vec4 of scratch each; nsamples = samples folded into the AOVs, or, with tile_n (an adaptive render),
-// tile_n[8x8 tile of the frame] = the samples folded into each pixel of that tile.
+// tile_n[8x8 tile of the frame] = the samples folded into each pixel of that tile.  With despeckle.enabled (and iterations >= 1) the firefly
+// clamp runs between the prep and the first a-trous step, col0 -> col1, and the ping-pong starts from col1.
 void launch_denoise(hipStream_t s, const vec4* acc, const vec4* albedo, const vec4* normal, const vec4* moments, uint32_t W, uint32_t H,
                     uint32_t nsamples, const DenoiseParams& P, uint32_t iterations, vec4* guide, vec4* aux, vec4* col0, vec4* col1, vec4* out,
-                    const uint32_t* tile_n, const Rect& rect);
+                    const uint32_t* tile_n, const Rect& rect, const pt_despeckle_options& despeckle);
 
 }  // namespace pt

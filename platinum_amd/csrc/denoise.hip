@@ -4,6 +4,7 @@
 //   k_accumulate_aov  after k_accumulate / k_gmon: folds Abuf and Lbuf into the three AOV images, per pixel in sample order
 //                     (k_accumulate_aov_adaptive: the same over the active tiles of an adaptive render)
 //   k_dn_prep         demodulation, variance, depth gradient (k_dn_prep_counts: with per-pixel sample counts, adaptive renders)
+//   k_dn_despeckle    the optional firefly clamp between the prep and the first a-trous step (col0 -> col1)
 //   k_atrous          one 5x5 step per launch (ping-pong); the last one remodulates
 // The filter runs over a rectangle of the frame as if it were the whole image (a render region): its kernels take W x H of
 // the rectangle, the frame's width as the row pitch, and pointers to the rectangle's first pixel.
@@ -143,6 +144,13 @@ __global__ void __launch_bounds__(256) k_dn_prep_counts(const vec4* __restrict__
   if (x < W && y < H) dn_prep_pixel_counts(acc, albedo, normal, moments, W, H, pitch, x0, y0, x, y, tile_n, guide, col, aux);
 }
 
+// the firefly clamp (dn_despeckle_pixel): 9 loads of col, up to 9 of guide.w, one divide
+__global__ void __launch_bounds__(256) k_dn_despeckle(const vec4* __restrict__ guide, const vec4* __restrict__ col_in, vec4* __restrict__ col_out,
+                                                      DenoiseParams P, uint32_t pitch, float threshold) {
+  const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
+  if (x < P.W && y < P.H) dn_despeckle_pixel(guide, col_in, col_out, P, pitch, x, y, threshold);
+}
+
 __global__ void __launch_bounds__(256) k_atrous(const vec4* __restrict__ guide, const vec4* __restrict__ aux, const vec4* __restrict__ col_in,
                                                 vec4* __restrict__ col_out, const vec4* __restrict__ acc, vec4* __restrict__ out, DenoiseParams P,
                                                 uint32_t pitch, uint32_t step, uint32_t last) {
@@ -182,7 +190,7 @@ void launch_accumulate_aov_adaptive(hipStream_t s, vec4* albedo, vec4* normal, v
 
 void launch_denoise(hipStream_t s, const vec4* acc, const vec4* albedo, const vec4* normal, const vec4* moments, uint32_t W, uint32_t H,
                     uint32_t nsamples, const DenoiseParams& Pf, uint32_t iterations, vec4* guide, vec4* aux, vec4* col0, vec4* col1, vec4* out,
-                    const uint32_t* tile_n, const Rect& rect) {
+                    const uint32_t* tile_n, const Rect& rect, const pt_despeckle_options& despeckle) {
   // the rectangle as an image of its own: its size, the frame's width as the pitch, every image from the rectangle's first pixel on
   const uint32_t pitch = W, x0 = rect.x0, y0 = rect.y0;
   const size_t org = (size_t)y0 * pitch + x0;
@@ -200,6 +208,10 @@ void launch_denoise(hipStream_t s, const vec4* acc, const vec4* albedo, const ve
   else hipLaunchKernelGGL(k_dn_prep, grid, block, 0, s, acc, albedo, normal, moments, W, H, pitch, (float)nsamples, guide, col0, aux);
   vec4* cin = col0;
   vec4* cout = col1;
+  if (despeckle.enabled) {
+    hipLaunchKernelGGL(k_dn_despeckle, grid, block, 0, s, guide, cin, cout, P, pitch, despeckle.threshold);
+    vec4* t = cin; cin = cout; cout = t;
+  }
   for (uint32_t i = 0; i < iterations; i++) {
     hipLaunchKernelGGL(k_atrous, grid, block, 0, s, guide, aux, cin, cout, acc, out, P, pitch, 1u << i, i + 1 == iterations ? 1u : 0u);
     vec4* t = cin; cin = cout; cout = t;

@@ -712,6 +712,15 @@ int pt_set_denoise_options(pt_renderer* r, const pt_denoise_options* o) {
   return PT_OK;
 }
 
+// the clamp is a stage of the denoiser, which a group does not run
+int pt_set_despeckle_options(pt_renderer* r, const pt_despeckle_options* o) {
+  if (!is_group(r)) return dev_set_despeckle_options(r, o);
+  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (o->enabled) return fail(PT_ERR_UNSUPPORTED, "pt_set_despeckle_options: a device group does not run the denoiser");
+  for (auto* m : r->group->shards) { int rc = dev_set_despeckle_options(m, o); if (rc != PT_OK) return rc; }
+  return PT_OK;
+}
+
 int pt_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out) {
   if (!is_group(r)) return dev_read_aov(r, aov, rgba_out);
   return fail(PT_ERR_BAD_STATE, "pt_read_aov: a device group does not keep AOVs");

@@ -2,6 +2,7 @@
 //
 //   stage_aov        : what one camera ray's first hit contributes to the AOV images (albedo, shading normal, distance)
 //   dn_prep_pixel    : demodulation, variance, depth gradient -> the filter's per-pixel inputs (dn_prep_pixel_counts: per-pixel N)
+//   dn_despeckle_pixel : the optional firefly clamp on the prep's output (pt_despeckle_options)
 //   dn_iterate_pixel : one 5x5 a-trous step (SVGF's spatial filter, Dammertz et al. 2010 / Schied et al. 2017, no temporal part)
 //
 // Written once, as plain C++ under PT_HD: denoise.hip runs it on the device, tests/emu/denoise_emu.cpp on the host, and the two
@@ -136,6 +137,40 @@ PT_HD float dn_blur_variance(const vec4* guide, const vec4* col, const DenoisePa
       sv += w * vq;
     }
   return sv / sw;  // (the centre is always used)
+}
+
+// The firefly clamp at pixel (x, y), between the prep and the first a-trous step (DESIGN.md §3a "Firefly clamp"): a valid pixel whose
+// luminance exceeds `threshold` times the brightest of its 3x3 neighbours (valid, of its own class, inside W x H; row-major over dy,
+// then dx) is scaled down to that limit, its variance kept.  Every other pixel is copied.  Reads col_in only.
+PT_HD void dn_despeckle_pixel(const vec4* guide, const vec4* col_in, vec4* col_out, const DenoiseParams& P, uint32_t pitch, uint32_t x,
+                              uint32_t y, float threshold) {
+  const size_t p = (size_t)y * pitch + x;
+  const vec4 cp = col_in[p];
+  if (!(cp.w >= 0.0f)) { col_out[p] = cp; return; }  // not finite: never a tap, keeps its value
+  const bool geo = guide[p].w >= 0.0f;
+  bool any = false;
+  float M = 0.0f;
+  for (int dy = -1; dy <= 1; dy++)
+    for (int dx = -1; dx <= 1; dx++) {
+      if (dx == 0 && dy == 0) continue;
+      const int qx = (int)x + dx, qy = (int)y + dy;
+      if (qx < 0 || qy < 0 || qx >= (int)P.W || qy >= (int)P.H) continue;
+      const size_t q = (size_t)qy * pitch + (uint32_t)qx;
+      const vec4 cq = col_in[q];
+      if (!(cq.w >= 0.0f) || (guide[q].w >= 0.0f) != geo) continue;
+      const float lq = dn_lum(v3(cq.x, cq.y, cq.z));
+      if (!any || lq > M) M = lq;
+      any = true;
+    }
+  vec4 o = cp;
+  if (any) {
+    const float L = dn_lum(v3(cp.x, cp.y, cp.z)), lim = threshold * M;
+    if (L > lim && L > 0.0f) {
+      const float k = lim / L;
+      o = vec4{cp.x * k, cp.y * k, cp.z * k, cp.w};
+    }
+  }
+  col_out[p] = o;
 }
 
 // One a-trous step at pixel (x, y) with step `s`.  `last`: remodulate, out[p] = colour (alpha 1); `acc` supplies the value of a pixel

@@ -255,6 +255,7 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   pt_default_post_options(&r->post);
   pt_default_tonemap_options(&r->tonemap);
   pt_default_denoise_options(&r->denoise);
+  pt_default_despeckle_options(&r->despeckle);
   pt_default_adaptive_options(&r->adaptive_opts);
   pt_default_render_region(&r->region_opts);
   r->device = device_ordinal;
@@ -862,7 +863,8 @@ int enqueue_denoise(pt_renderer* r) {
   launch_denoise(r->stream, r->acc, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * npix, P.W, P.H, (uint32_t)r->launched, P,
                  r->denoise.iterations, r->dn_guide.p, r->dn_aux.p, r->dn_col[0].p, r->dn_col[1].p, r->denoised.p,
                  r->adaptive ? r->ad_tile_n.p : nullptr,   // an adaptive render: each pixel's own sample count
-                 r->rect);                                   // a region render: the region as an image of its own
+                 r->rect,                                    // a region render: the region as an image of its own
+                 r->despeckle);
   PT_HIP(hipGetLastError());
   return PT_OK;
 }
@@ -886,6 +888,22 @@ int dev_read_denoised(pt_renderer* r, float* rgba_out) {
   if ((rc = enqueue_denoise(r)) != PT_OK) return rc;
   PT_HIP(hipStreamSynchronize(r->stream));
   PT_HIP(hipMemcpy(rgba_out, r->denoised.p, sizeof(vec4) * (size_t)r->S.width * r->S.height, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+extern "C" void pt_default_despeckle_options(pt_despeckle_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->threshold = 2.0f;
+}
+
+// (the options are checked before the renderer, as dev_set_adaptive_options)
+int dev_set_despeckle_options(pt_renderer* r, const pt_despeckle_options* o) {
+  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (!(o->threshold >= 1.0f && o->threshold <= 3.4028234663852886e38f))
+    return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_despeckle_options: threshold must be finite and >= 1");
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_despeckle_options: null renderer");
+  r->despeckle = *o;
   return PT_OK;
 }
 

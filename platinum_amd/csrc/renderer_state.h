@@ -126,6 +126,7 @@ struct pt_renderer {
   DevBuf<uint32_t> render_target;  // RGBA8 (renderer_pt.cpp:832-835)
   // first-hit AOVs + denoiser (denoise.hip): only a render started with denoise.enabled allocates or launches any of it
   pt_denoise_options denoise{};
+  pt_despeckle_options despeckle{};  // the firefly clamp ahead of the filter, read by every enqueue_denoise
   bool aov = false;                 // this render accumulates AOVs
   DevBuf<vec4> Abuf;                // 2 vec4 per Lbuf entry: {albedo, t}, {normal, hit}
   DevBuf<vec4> aov_img;             // [PT_AOV_*][pixel] running means
@@ -263,6 +264,7 @@ int dev_get_stats(pt_renderer* r, pt_stats* out);
 int dev_set_denoise_options(pt_renderer* r, const pt_denoise_options* o);
 int dev_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out);
 int dev_read_denoised(pt_renderer* r, float* rgba_out);
+int dev_set_despeckle_options(pt_renderer* r, const pt_despeckle_options* o);
 int dev_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o);
 int dev_read_sample_counts(pt_renderer* r, uint32_t* out);
 int dev_set_render_region(pt_renderer* r, const pt_render_region* o);

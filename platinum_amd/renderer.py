@@ -168,6 +168,25 @@ class Renderer:
         abi.check(self._lib, self._lib.pt_read_denoised(self._h, out.ctypes.data))
         return out
 
+    # firefly clamp ahead of the denoiser (include/ptamd.h, an additive extension of ABI 5): no reference counterpart
+    def despeckleOptions(self):
+        """The options in effect (pt_default_despeckle_options until setDespeckleOptions is called)."""
+        if getattr(self, "_despeckle", None) is None:
+            self._despeckle = abi.DespeckleOptions()
+            self._lib.pt_default_despeckle_options(C.byref(self._despeckle))
+        o = abi.DespeckleOptions()
+        C.memmove(C.byref(o), C.byref(self._despeckle), C.sizeof(o))
+        return o
+
+    def setDespeckleOptions(self, o=None, **fields):
+        """Sets `o` (default: the current options) with `fields` overriding it, e.g. setDespeckleOptions(enabled=1, threshold=2.0).
+        The options take effect at the next readbackDenoised, or read / present with apply_to_target."""
+        o = self.despeckleOptions() if o is None else o
+        for k, v in fields.items():
+            setattr(o, k, v)
+        abi.check(self._lib, self._lib.pt_set_despeckle_options(self._h, C.byref(o)))
+        self._despeckle = o
+
     # tile-adaptive sampling (include/ptamd.h, an additive extension of ABI 5): no reference counterpart
     def adaptiveOptions(self):
         """The options in effect (pt_default_adaptive_options until setAdaptiveOptions is called)."""

@@ -3,7 +3,8 @@
 
   1. C3 (1920x1080, 128 spp, 8 bounces): wall time of render_step(0) + wait with AOVs off and on, alternated, --runs each;
   2. the device time of the filter (prep + 5 a-trous steps + post-process, HIP events around pt_present_render_target with
-     apply_to_target = 1, minus the same present without it) at 1920x1080 and 3840x2160.
+     apply_to_target = 1, minus the same present without it) at 1920x1080 and 3840x2160, with the firefly clamp
+     (pt_despeckle_options) off and on.
 
 Run each invocation under its own time limit, e.g.  timeout -k 10 900 python tools/denoise_timing.py --json out.json
 """
@@ -27,9 +28,10 @@ def render_ms(r, sc, size, spp, bounces, aov):
     return (time.perf_counter() - t0) * 1e3
 
 
-def present_device_ms(r, hip, apply, reps=20):
+def present_device_ms(r, hip, apply, despeckle=False, reps=20):
     """Device time of one pt_present_render_target (HIP events on the renderer's stream), median of `reps`."""
     r.setDenoiseOptions(apply_to_target=1 if apply else 0)
+    r.setDespeckleOptions(enabled=1 if despeckle else 0)
     _, stream = r.presentRenderTarget()
     s = C.c_void_p(stream)
     hip.hipStreamSynchronize(s)
@@ -75,10 +77,13 @@ def main():
     for size, spp in (((1920, 1080), 16), ((3840, 2160), 4)):
         render_ms(r, sc, size, spp, 8, True)
         with_f = present_device_ms(r, hip, True)
+        with_c = present_device_ms(r, hip, True, despeckle=True)
         without = present_device_ms(r, hip, False)
         key = "%dx%d" % size
-        out["filter_ms"][key] = {"present_denoised": with_f, "present_plain": without, "filter": with_f - without}
-        print("%s: present with the filter %.3f ms, without %.3f ms: filter (5 iterations) %.3f ms" % (key, with_f, without, with_f - without))
+        out["filter_ms"][key] = {"present_denoised": with_f, "present_despeckled": with_c, "present_plain": without, "filter": with_f - without,
+                                 "filter_despeckle": with_c - without, "despeckle": with_c - with_f}
+        print("%s: present with the filter %.3f ms, without %.3f ms: filter (5 iterations) %.3f ms; with the firefly clamp %.3f ms (%+.3f ms)" % (
+            key, with_f, without, with_f - without, with_c - without, with_c - with_f))
     r.close()
     if a.json:
         with open(a.json, "w") as f:

@@ -6,6 +6,7 @@ tracing (GMoN optional), fused post-process + tonemap — to an 8-bit PNG.
     python tools/render_scene.py tests/golden/scene_fixture/mini.json out.png --size 640 360 --spp 64
     python tools/render_scene.py model.glb out.png --camera-pos 0 1.5 6 --camera-target 0 1 0 --env sky
     python tools/render_scene.py builtin:c5 out.png --size 960 540 --spp 32 --bounces 12
+    python tools/render_scene.py builtin:c1 preview.png --size 640 640 --spp 1 --denoise --despeckle
     python tools/render_scene.py builtin:c3 corner.png --size 1920 1080 --spp 4096 --region 1200,600,1500,800
 """
 import argparse, os, struct, sys, time, zlib
@@ -34,11 +35,15 @@ def main():
     ap.add_argument("--env", default="none", help="'sky' = procedural sky, or the path of an .exr / Radiance .hdr environment map")
     ap.add_argument("--exposure", type=float, default=0.0)
     ap.add_argument("--denoise", action="store_true", help="keep first-hit AOVs and write the image through the a-trous denoiser")
+    ap.add_argument("--despeckle", type=float, nargs="?", const=2.0, default=None, metavar="T",
+                    help="with --denoise: clamp a pixel brighter than T x its brightest 3x3 neighbour ahead of the filter (fireflies; default T = 2)")
     ap.add_argument("--adaptive", type=float, default=None, metavar="THRESHOLD",
                     help="tile-adaptive sampling: an 8x8 tile stops once every pixel's relative error is <= THRESHOLD (--spp is the maximum)")
     ap.add_argument("--region", default=None, metavar="X0,Y0,X1,Y1",
                     help="render region: sample only the pixels [X0, X1) x [Y0, Y1) (top-left origin); the rest of the image stays empty (alpha 0)")
     a = ap.parse_args()
+    if a.despeckle is not None and not a.denoise:
+        ap.error("--despeckle is a stage of the denoiser: it needs --denoise")
     region = None
     if a.region is not None:
         try:
@@ -66,6 +71,8 @@ def main():
     r = Renderer(device=0)
     if a.denoise:
         r.setDenoiseOptions(enabled=1, apply_to_target=1)
+    if a.despeckle is not None:
+        r.setDespeckleOptions(enabled=1, threshold=a.despeckle)
     if a.adaptive is not None:
         if a.gmon > 1:
             ap.error("--adaptive does not combine with --gmon")
