@@ -424,6 +424,49 @@ void pt_default_despeckle_options(pt_despeckle_options* o);
 /* PT_ERR_INVALID_ARGUMENT for a threshold that is not finite or < 1 (checked before the renderer) */
 int pt_set_despeckle_options(pt_renderer* r, const pt_despeckle_options* o);
 
+/* ---- auto exposure: a luminance-histogram meter ahead of the post-process (NEW, an additive extension of ABI 5: new entry points and two
+ * new structs, no existing struct changed) ----
+ * With `enabled` set, pt_read_render_target / pt_present_render_target meter the image the post-process is about to read (the accumulator;
+ * the denoised image with apply_to_target; a device group's merged image) over the render's rectangle (the frame, or the render region),
+ * scale its rgb by `gain` into a scratch image and post-process that: target = post-process(image * gain).  pt_post_options.exposure acts on
+ * top as compensation.  Everything is enqueued on the renderer's stream; there is no host round trip.
+ * Per pixel Y = (0.2126 r + 0.7152 g) + 0.0722 b (alpha ignored) is counted, in this order, as `nonfinite` (NaN, +-inf), `below` (Y < 2^-16:
+ * 0, negatives, denormals), `above` (Y >= 2^16), or in bin (bits(Y) >> 20) - 888: 8 bins per octave over [2^-16, 2^16).  Only binned pixels
+ * are metered.  With n their number, lo = (uint64)(n * low_fraction), hi = min(n, (uint64)(n * high_fraction)) in double (lo = 0, hi = n
+ * when hi <= lo), the pixels of ascending rank [lo, hi) are kept: K = hi - lo of them, S = sum over them of (2 * bin + 1).  Then
+ *   mean_log2 = (float)((double)S / (double)(16 K)) - 16     target_ev = min(max(target_log2 - mean_log2, min_ev), max_ev)
+ *   ev = previous ev + (1 - smoothing) * (target_ev - previous ev), or target_ev when there is no previous one     gain = 2^ev
+ * and mean_log2 = target_ev = 0 when n = 0.  The previous ev is kept on the device; pt_start_render keeps it, so the
+ * exposure eases across camera restarts.  enabled = 0 allocates and launches nothing and gives the bits of a library without the meter.
+ * pt_read_accumulator, pt_read_denoised and the AOVs are never scaled. */
+typedef struct pt_exposure_options {
+  uint32_t enabled;        /* default 0; read at every pt_read_render_target / pt_present_render_target, no restart */
+  float target_log2;       /* log2 luminance the metered mean is brought to; default -2.4739313f (log2 0.18); finite, |x| <= 32 */
+  float low_fraction;      /* default 0.10 */
+  float high_fraction;     /* default 0.95; 0 <= low < high <= 1 */
+  float min_ev, max_ev;    /* defaults -16, 16; finite, -32 <= min_ev <= max_ev <= 32 (gain stays finite and non-zero) */
+  float smoothing;         /* default 0; 0 <= s < 1: weight of the previously applied ev */
+} pt_exposure_options;
+void pt_default_exposure_options(pt_exposure_options* o);
+/* PT_ERR_INVALID_ARGUMENT for options outside the ranges above (checked before the renderer) */
+int pt_set_exposure_options(pt_renderer* r, const pt_exposure_options* o);
+/* Forgets the previous ev: the next metered target starts from its own target_ev. */
+int pt_reset_exposure(pt_renderer* r);
+
+typedef struct pt_exposure_meter {
+  uint32_t bins[256];
+  uint32_t below, above, nonfinite, metered;   /* metered = sum of bins */
+  uint32_t kept;  uint32_t _pad;  uint64_t weighted;   /* K and S */
+  float mean_log2, target_ev, ev, gain;
+} pt_exposure_meter;
+/* Meters the image a target read would show now.  Blocks.  Works with enabled = 0 (a UI histogram).  Does NOT advance the smoothing
+ * state: ev is what a target read made at this moment would apply.  PT_ERR_BAD_STATE before pt_start_render. */
+int pt_read_exposure_meter(pt_renderer* r, pt_exposure_meter* out);
+/* Parity surface: upload a host W*H RGBA32F image, run the same three kernels over `rect` ({x0, y0, x1, y1}, or NULL for the whole image)
+ * with `options` and no smoothing state, and return the record and (scaled_out may be NULL) the scaled image.  Needs only pt_create. */
+int pt_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const uint32_t* rect,
+                      const pt_exposure_options* options, pt_exposure_meter* out, float* scaled_out);
+
 /* ---- tile-adaptive sampling (NEW, an additive extension of ABI 5: new entry points and one new struct, no existing struct changed) ----
  * A render started while `enabled` is set stops sampling an 8x8 tile of the accumulator once it has converged; pt_render_params.spp
  * becomes the per-pixel maximum.  Checkpoints are at the sample counts c_k = min_spp + k * interval with c_k < spp.  At each, every

@@ -34,6 +34,9 @@
  *   (no counterpart)                                             pt_despeckle_options& despeckleOptions() / setDespeckleOptions(...): the firefly
  *                                                                clamp ahead of the filter (ptamd.h, ABI 5 extension); handed over whenever an
  *                                                                image is asked for
+ *   (no counterpart)                                             pt_exposure_options& exposureOptions(), resetExposure(), readExposureMeter(): auto
+ *                                                                exposure, a luminance-histogram meter ahead of the post-process (ptamd.h, ABI 5
+ *                                                                extension); handed over whenever a target is asked for
  *   (no counterpart)                                             pt_adaptive_options& adaptiveOptions() / setAdaptiveOptions(...),
  *                                                                readbackSampleCounts(): tile-adaptive sampling (ptamd.h, ABI 5 extension);
  *                                                                handed over at startRender
@@ -207,6 +210,17 @@ public:
   // whenever a denoised image is asked for, no restart needed.
   [[nodiscard]] constexpr pt_despeckle_options& despeckleOptions() { return m_despeckle; }
   void setDespeckleOptions(const pt_despeckle_options& o) { m_despeckle = o; }
+  // Auto exposure (ptamd.h, an additive extension of ABI 5): with enabled set, presentRenderTarget / readbackRenderTarget meter the image's
+  // luminance histogram and scale the image to the target ahead of the post-process; the Exposure pass's stops act on top as compensation.
+  // Edited in place like denoiseOptions(); read whenever a target is asked for, no restart needed.
+  [[nodiscard]] constexpr pt_exposure_options& exposureOptions() { return m_autoExposure; }
+  // Forgets the previously applied ev (a cut to another scene): the next target starts from its own target_ev.
+  void resetExposure() { if (m_pt) check(pt_reset_exposure(m_pt)); }
+  // The histogram and the ev a target asked for now would apply (a UI histogram; works with enabled = 0).  Blocks; false on failure.
+  [[nodiscard]] bool readExposureMeter(pt_exposure_meter* out) const {
+    return m_pt && m_started && out && check(pt_set_denoise_options(m_pt, &m_denoise)) && check(pt_set_despeckle_options(m_pt, &m_despeckle)) &&
+           check(pt_set_exposure_options(m_pt, &m_autoExposure)) && check(pt_read_exposure_meter(m_pt, out));
+  }
   // Tile-adaptive sampling (ptamd.h, an additive extension of ABI 5).  Edited in place like denoiseOptions(); read at startRender.
   [[nodiscard]] constexpr pt_adaptive_options& adaptiveOptions() { return m_adaptive; }
   void setAdaptiveOptions(const pt_adaptive_options& o) { m_adaptive = o; }
@@ -235,6 +249,7 @@ private:
     m_outputSpace = defaults.output_space;   // Display P3 (renderer_pt.hpp:182)
     pt_default_denoise_options(&m_denoise);
     pt_default_despeckle_options(&m_despeckle);
+    pt_default_exposure_options(&m_autoExposure);
     pt_default_adaptive_options(&m_adaptive);
     pt_default_render_region(&m_region);
     std::vector<int32_t> ord(devices, devices + count);
@@ -259,7 +274,8 @@ private:
     postprocess::flatten(m_exposure, m_chromaticAberration, m_contrastSaturation, m_toneCurve, m_vignette, &post);
     postprocess::flatten(m_tonemap, m_outputSpace, &tonemap);
     return check(pt_set_gmon_options(m_pt, &m_gmonOptions)) && check(pt_set_post_options(m_pt, &post)) && check(pt_set_tonemap_options(m_pt, &tonemap)) &&
-           check(pt_set_denoise_options(m_pt, &m_denoise)) && check(pt_set_despeckle_options(m_pt, &m_despeckle));
+           check(pt_set_denoise_options(m_pt, &m_denoise)) && check(pt_set_despeckle_options(m_pt, &m_despeckle)) &&
+           check(pt_set_exposure_options(m_pt, &m_autoExposure));
   }
 
   pt_renderer* m_pt = nullptr;
@@ -278,6 +294,7 @@ private:
   pt_gmon_options m_gmonOptions{1.0f};
   pt_denoise_options m_denoise{};
   pt_despeckle_options m_despeckle{};
+  pt_exposure_options m_autoExposure{};
   pt_adaptive_options m_adaptive{};
   pt_render_region m_region{};
   mutable void* m_presentStream = nullptr;

@@ -181,6 +181,19 @@ class DespeckleOptions(C.Structure):
     _fields_ = [("enabled", C.c_uint32), ("threshold", C.c_float)]
 
 
+class ExposureOptions(C.Structure):
+    """pt_exposure_options: the luminance-histogram meter ahead of the post-process (auto exposure)."""
+    _fields_ = [("enabled", C.c_uint32), ("target_log2", C.c_float), ("low_fraction", C.c_float), ("high_fraction", C.c_float),
+                ("min_ev", C.c_float), ("max_ev", C.c_float), ("smoothing", C.c_float)]
+
+
+class ExposureMeter(C.Structure):
+    """pt_exposure_meter: the histogram (8 bins per octave over [2^-16, 2^16)), the outlier counters and what the meter resolved."""
+    _fields_ = [("bins", C.c_uint32 * 256), ("below", C.c_uint32), ("above", C.c_uint32), ("nonfinite", C.c_uint32), ("metered", C.c_uint32),
+                ("kept", C.c_uint32), ("_pad", C.c_uint32), ("weighted", C.c_uint64),
+                ("mean_log2", C.c_float), ("target_ev", C.c_float), ("ev", C.c_float), ("gain", C.c_float)]
+
+
 class AdaptiveOptions(C.Structure):
     _fields_ = [("enabled", C.c_uint32), ("threshold", C.c_float), ("min_spp", C.c_uint32), ("interval", C.c_uint32)]
 
@@ -251,6 +264,12 @@ SYMBOLS = [
     ("pt_read_denoised", C.c_int, [C.c_void_p, C.c_void_p]),
     ("pt_default_despeckle_options", None, [C.POINTER(DespeckleOptions)]),
     ("pt_set_despeckle_options", C.c_int, [C.c_void_p, C.POINTER(DespeckleOptions)]),
+    ("pt_default_exposure_options", None, [C.POINTER(ExposureOptions)]),
+    ("pt_set_exposure_options", C.c_int, [C.c_void_p, C.POINTER(ExposureOptions)]),
+    ("pt_reset_exposure", C.c_int, [C.c_void_p]),
+    ("pt_read_exposure_meter", C.c_int, [C.c_void_p, C.POINTER(ExposureMeter)]),
+    ("pt_debug_exposure", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(ExposureOptions),
+                                    C.POINTER(ExposureMeter), C.c_void_p]),
     ("pt_default_adaptive_options", None, [C.POINTER(AdaptiveOptions)]),
     ("pt_set_adaptive_options", C.c_int, [C.c_void_p, C.POINTER(AdaptiveOptions)]),
     ("pt_read_sample_counts", C.c_int, [C.c_void_p, C.c_void_p]),

@@ -731,6 +731,37 @@ int pt_read_denoised(pt_renderer* r, float* rgba_out) {
   return fail(PT_ERR_BAD_STATE, "pt_read_denoised: a device group does not keep AOVs");
 }
 
+// Auto exposure: a group post-processes its merged image on the first device, through that member's shared tail, so the members all
+// hold the options and the member that post-processes holds the meter's state.
+int pt_set_exposure_options(pt_renderer* r, const pt_exposure_options* o) {
+  if (!is_group(r)) return dev_set_exposure_options(r, o);
+  for (auto* m : r->group->shards) { int rc = dev_set_exposure_options(m, o); if (rc != PT_OK) return rc; }
+  return PT_OK;
+}
+
+int pt_reset_exposure(pt_renderer* r) {
+  if (!is_group(r)) return dev_reset_exposure(r);
+  for (auto* m : r->group->shards) { int rc = dev_reset_exposure(m); if (rc != PT_OK) return rc; }
+  return PT_OK;
+}
+
+int pt_read_exposure_meter(pt_renderer* r, pt_exposure_meter* out) {
+  if (!is_group(r)) return dev_read_exposure_meter(r, nullptr, out);
+  if (!out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  DeviceGroup* grp = r->group;
+  if (!grp->started) return fail(PT_ERR_BAD_STATE, "pt_read_exposure_meter before pt_start_render");
+  int rc = group_wait(r);
+  if (rc != PT_OK) return rc;
+  pt_renderer* m = first_started(grp);
+  if (!m || m->device != grp->shards[0]->device) return fail(PT_ERR_BAD_STATE, "device group: no member on the first device has samples");
+  return dev_read_exposure_meter(m, grp->merged, out);
+}
+
+int pt_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const uint32_t* rect, const pt_exposure_options* options,
+                      pt_exposure_meter* out, float* scaled_out) {
+  return dev_debug_exposure(is_group(r) ? r->group->shards[0] : r, rgba, width, height, rect, options, out, scaled_out);
+}
+
 // Adaptive sampling is per device: a group would have to agree on each tile's verdict across its members, which is not implemented
 int pt_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o) {
   if (!is_group(r)) return dev_set_adaptive_options(r, o);

@@ -256,6 +256,7 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   pt_default_tonemap_options(&r->tonemap);
   pt_default_denoise_options(&r->denoise);
   pt_default_despeckle_options(&r->despeckle);
+  pt_default_exposure_options(&r->exposure);
   pt_default_adaptive_options(&r->adaptive_opts);
   pt_default_render_region(&r->region_opts);
   r->device = device_ordinal;
@@ -907,6 +908,98 @@ int dev_set_despeckle_options(pt_renderer* r, const pt_despeckle_options* o) {
   return PT_OK;
 }
 
+extern "C" void pt_default_exposure_options(pt_exposure_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->target_log2 = -2.4739313f;   // log2 0.18
+  o->low_fraction = 0.10f; o->high_fraction = 0.95f;
+  o->min_ev = -16.0f; o->max_ev = 16.0f;
+}
+
+// (the options are checked before the renderer, as dev_set_adaptive_options)
+int dev_set_exposure_options(pt_renderer* r, const pt_exposure_options* o) {
+  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (const char* why = exposure_options_error(*o)) return fail(PT_ERR_INVALID_ARGUMENT, std::string("pt_set_exposure_options: ") + why);
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_exposure_options: null renderer");
+  r->exposure = *o;
+  return PT_OK;
+}
+
+// the record, allocated and cleared (no previous ev) on first use
+static int exposure_record(pt_renderer* r) {
+  if (r->exp_rec.p) return PT_OK;
+  PT_HIP(r->exp_rec.alloc(1));
+  PT_HIP(hipMemsetAsync(r->exp_rec.p, 0, sizeof(ExposureRecord), r->stream));
+  return PT_OK;
+}
+
+int dev_reset_exposure(pt_renderer* r) {
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (!r->exp_rec.p) return PT_OK;   // nothing metered yet: nothing to forget
+  PT_HIP(hipSetDevice(r->device));
+  PT_HIP(hipMemsetAsync(&r->exp_rec.p->has_prev, 0, sizeof(uint32_t), r->stream));
+  return PT_OK;
+}
+
+// The meter ahead of the post-process, enqueued on the renderer's stream: meters *src over the render's rectangle, advances the smoothing
+// state, writes *src * gain into the scratch image and points *src at it.
+static int enqueue_exposure(pt_renderer* r, const vec4** src) {
+  const size_t npix = (size_t)r->S.width * r->S.height;
+  { const int rc = exposure_record(r); if (rc != PT_OK) return rc; }
+  PT_HIP(r->exp_img.alloc(npix));
+  PT_HIP(launch_exposure_meter(r->stream, *src, r->S.width, r->rect, r->exposure, r->exp_rec.p, true));
+  launch_exposure_apply(r->stream, *src, r->exp_img.p, (uint32_t)npix, r->exp_rec.p);
+  PT_HIP(hipGetLastError());
+  *src = r->exp_img.p;
+  return PT_OK;
+}
+
+int dev_read_exposure_meter(pt_renderer* r, const vec4* acc_device, pt_exposure_meter* out) {
+  if (!r || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (!r->started) return fail(PT_ERR_BAD_STATE, "pt_read_exposure_meter before pt_start_render");
+  PT_HIP(hipSetDevice(r->device));
+  int rc = dev_wait(r);
+  if (rc != PT_OK) return rc;
+  const vec4* src = acc_device ? acc_device : r->acc;
+  if (!acc_device && r->aov && r->denoise.apply_to_target) {
+    if ((rc = enqueue_denoise(r)) != PT_OK) return rc;
+    src = r->denoised.p;
+  }
+  if ((rc = exposure_record(r)) != PT_OK) return rc;
+  PT_HIP(launch_exposure_meter(r->stream, src, r->S.width, r->rect, r->exposure, r->exp_rec.p, false));
+  PT_HIP(hipStreamSynchronize(r->stream));
+  PT_HIP(hipMemcpy(out, &r->exp_rec.p->meter, sizeof(*out), hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+// the three kernels on an uploaded image, with a record of its own (no smoothing state); the renderer's own state is untouched
+int dev_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const uint32_t* rect, const pt_exposure_options* options,
+                       pt_exposure_meter* out, float* scaled_out) {
+  if (!options || !rgba || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (const char* why = exposure_options_error(*options)) return fail(PT_ERR_INVALID_ARGUMENT, std::string("pt_debug_exposure: ") + why);
+  if (width == 0 || height == 0 || (uint64_t)width * height > (1ull << 28)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_exposure: the image must hold 1..2^28 pixels");
+  Rect rc{0u, 0u, width, height};
+  if (rect) {
+    rc = Rect{rect[0], rect[1], rect[2], rect[3]};
+    if (rc.x0 >= rc.x1 || rc.y0 >= rc.y1 || rc.x1 > width || rc.y1 > height) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_exposure: the rectangle is empty or does not fit the image");
+  }
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_exposure: null renderer");
+  PT_HIP(hipSetDevice(r->device));
+  const size_t npix = (size_t)width * height;
+  DevBuf<vec4> img, scaled;
+  DevBuf<ExposureRecord> rec;
+  PT_HIP(img.alloc(npix)); PT_HIP(scaled.alloc(npix)); PT_HIP(rec.alloc(1));
+  PT_HIP(hipMemcpyAsync(img.p, rgba, sizeof(vec4) * npix, hipMemcpyHostToDevice, r->stream));
+  PT_HIP(hipMemsetAsync(rec.p, 0, sizeof(ExposureRecord), r->stream));
+  PT_HIP(launch_exposure_meter(r->stream, img.p, width, rc, *options, rec.p, false));
+  launch_exposure_apply(r->stream, img.p, scaled.p, (uint32_t)npix, rec.p);
+  PT_HIP(hipGetLastError());
+  PT_HIP(hipStreamSynchronize(r->stream));
+  PT_HIP(hipMemcpy(out, &rec.p->meter, sizeof(*out), hipMemcpyDeviceToHost));
+  if (scaled_out) PT_HIP(hipMemcpy(scaled_out, scaled.p, sizeof(vec4) * npix, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
 extern "C" void pt_default_adaptive_options(pt_adaptive_options* o) {
   if (!o) return;
   memset(o, 0, sizeof(*o));
@@ -983,6 +1076,7 @@ int dev_postprocess_to_host(pt_renderer* r, const vec4* acc_device, uint8_t* rgb
   pc.tm = r->tonemap;
   const Mat3 odt = compute_transform(r->params.working_space, r->tonemap.output_space);  // renderer_pt.cpp:190-191
   pc.odt = PPMat3{odt.c0, odt.c1, odt.c2};
+  if (r->exposure.enabled) { const int rc = enqueue_exposure(r, &acc_device); if (rc != PT_OK) return rc; }
   launch_postprocess(r->stream, acc_device, r->render_target.p, r->S.width, r->S.height, pc);
   PT_HIP(hipGetLastError());
   PT_HIP(hipStreamSynchronize(r->stream));
@@ -1009,6 +1103,7 @@ int dev_present(pt_renderer* r, const vec4* acc_device, void** device_rgba8_out,
     if (rc != PT_OK) return rc;
     src = r->denoised.p;
   }
+  if (r->exposure.enabled) { const int rc = enqueue_exposure(r, &src); if (rc != PT_OK) return rc; }
   launch_postprocess(r->stream, src, r->render_target.p, r->S.width, r->S.height, pc);
   PT_HIP(hipGetLastError());
   *device_rgba8_out = r->render_target.p;

@@ -11,6 +11,7 @@
 #include "host_scene.h"
 #include "adaptive.h"
 #include "denoise.h"
+#include "exposure.h"
 #include "kernels.h"
 #include "pt_bvh.h"
 
@@ -131,6 +132,11 @@ struct pt_renderer {
   DevBuf<vec4> Abuf;                // 2 vec4 per Lbuf entry: {albedo, t}, {normal, hit}
   DevBuf<vec4> aov_img;             // [PT_AOV_*][pixel] running means
   DevBuf<vec4> dn_guide, dn_aux, dn_col[2], denoised;  // the filter's per-pixel buffers and its output
+  // auto exposure (exposure.hip): nothing is allocated or launched until a target is read with exposure.enabled, or the
+  // meter is read.  The record holds the previous ev, so it outlives pt_start_render like the other arrays.
+  pt_exposure_options exposure{};
+  DevBuf<ExposureRecord> exp_rec;   // [1] the meter record and the smoothing state
+  DevBuf<vec4> exp_img;             // the frame * gain: what k_postprocess reads with exposure.enabled
   // tile-adaptive sampling (adaptive.hip): only a render started with adaptive_opts.enabled allocates or launches any of it
   pt_adaptive_options adaptive_opts{};
   bool adaptive = false;            // this render samples adaptively
@@ -220,6 +226,7 @@ struct pt_renderer {
     seg_active[0].release(); seg_active[1].release(); seg_shadow.release(); seg_poison.release(); wave_stats.release(); chunk_table[0].release(); chunk_table[1].release(); shade_order.release(); shade_cost.release(); gmon_buckets_d.release(); render_target.release();
     hit.release(); sq_o.release(); sq_d.release(); sq_c.release(); Lbuf.release(); acc_own.release(); spill.release();
     Abuf.release(); aov_img.release(); dn_guide.release(); dn_aux.release(); dn_col[0].release(); dn_col[1].release(); denoised.release();
+    exp_rec.release(); exp_img.release();
     release_adaptive();
   }
   void release_adaptive() {
@@ -265,6 +272,11 @@ int dev_set_denoise_options(pt_renderer* r, const pt_denoise_options* o);
 int dev_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out);
 int dev_read_denoised(pt_renderer* r, float* rgba_out);
 int dev_set_despeckle_options(pt_renderer* r, const pt_despeckle_options* o);
+int dev_set_exposure_options(pt_renderer* r, const pt_exposure_options* o);
+int dev_reset_exposure(pt_renderer* r);
+int dev_read_exposure_meter(pt_renderer* r, const vec4* acc_device, pt_exposure_meter* out);  // acc_device NULL = what dev_read_render_target shows
+int dev_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const uint32_t* rect, const pt_exposure_options* options,
+                       pt_exposure_meter* out, float* scaled_out);
 int dev_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o);
 int dev_read_sample_counts(pt_renderer* r, uint32_t* out);
 int dev_set_render_region(pt_renderer* r, const pt_render_region* o);

@@ -187,6 +187,48 @@ class Renderer:
         abi.check(self._lib, self._lib.pt_set_despeckle_options(self._h, C.byref(o)))
         self._despeckle = o
 
+    # auto exposure (include/ptamd.h, an additive extension of ABI 5): no reference counterpart
+    def exposureOptions(self):
+        """The options in effect (pt_default_exposure_options until setExposureOptions is called)."""
+        if getattr(self, "_exposure", None) is None:
+            self._exposure = abi.ExposureOptions()
+            self._lib.pt_default_exposure_options(C.byref(self._exposure))
+        o = abi.ExposureOptions()
+        C.memmove(C.byref(o), C.byref(self._exposure), C.sizeof(o))
+        return o
+
+    def setExposureOptions(self, o=None, **fields):
+        """Sets `o` (default: the current options) with `fields` overriding it, e.g. setExposureOptions(enabled=1, smoothing=0.5).
+        The options take effect at the next readbackRenderTarget / presentRenderTarget; no restart is needed."""
+        o = self.exposureOptions() if o is None else o
+        for k, v in fields.items():
+            setattr(o, k, v)
+        abi.check(self._lib, self._lib.pt_set_exposure_options(self._h, C.byref(o)))
+        self._exposure = o
+
+    def resetExposure(self):
+        """Forgets the previously applied ev: the next metered target starts from its own target_ev."""
+        abi.check(self._lib, self._lib.pt_reset_exposure(self._h))
+
+    def readbackExposureMeter(self):
+        """abi.ExposureMeter of the image a target read would show now; does not advance the smoothing state.  Blocks."""
+        m = abi.ExposureMeter()
+        abi.check(self._lib, self._lib.pt_read_exposure_meter(self._h, C.byref(m)))
+        return m
+
+    def debugExposure(self, rgba, rect=None, options=None, scaled=True):
+        """The meter's three kernels on a host (H, W, 4) float32 image over rect = (x0, y0, x1, y1) (default: the whole image) with `options`
+        (default: the current ones) and no smoothing state: (abi.ExposureMeter, the scaled image or None)."""
+        img = np.ascontiguousarray(rgba, dtype=np.float32)
+        h, w = img.shape[:2]
+        o = self.exposureOptions() if options is None else options
+        rc = None if rect is None else (C.c_uint32 * 4)(*rect)
+        m = abi.ExposureMeter()
+        out = np.empty((h, w, 4), np.float32) if scaled else None
+        abi.check(self._lib, self._lib.pt_debug_exposure(self._h, img.ctypes.data, w, h, None if rc is None else C.addressof(rc), C.byref(o),
+                                                         C.byref(m), None if out is None else out.ctypes.data))
+        return m, out
+
     # tile-adaptive sampling (include/ptamd.h, an additive extension of ABI 5): no reference counterpart
     def adaptiveOptions(self):
         """The options in effect (pt_default_adaptive_options until setAdaptiveOptions is called)."""

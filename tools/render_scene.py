@@ -7,6 +7,7 @@ tracing (GMoN optional), fused post-process + tonemap — to an 8-bit PNG.
     python tools/render_scene.py model.glb out.png --camera-pos 0 1.5 6 --camera-target 0 1 0 --env sky
     python tools/render_scene.py builtin:c5 out.png --size 960 540 --spp 32 --bounces 12
     python tools/render_scene.py builtin:c1 preview.png --size 640 640 --spp 1 --denoise --despeckle
+    python tools/render_scene.py builtin:c5 out.png --size 960 540 --spp 32 --auto-exposure
     python tools/render_scene.py builtin:c3 corner.png --size 1920 1080 --spp 4096 --region 1200,600,1500,800
 """
 import argparse, os, struct, sys, time, zlib
@@ -34,6 +35,9 @@ def main():
     ap.add_argument("--focal", type=float, default=28.0)
     ap.add_argument("--env", default="none", help="'sky' = procedural sky, or the path of an .exr / Radiance .hdr environment map")
     ap.add_argument("--exposure", type=float, default=0.0)
+    ap.add_argument("--auto-exposure", type=float, nargs="?", const=-2.4739313, default=None, metavar="TARGET_LOG2",
+                    help="meter the image's luminance histogram and bring its mean to 2^TARGET_LOG2 (default log2 0.18) ahead of the post-process; "
+                         "--exposure acts on top as compensation")
     ap.add_argument("--denoise", action="store_true", help="keep first-hit AOVs and write the image through the a-trous denoiser")
     ap.add_argument("--despeckle", type=float, nargs="?", const=2.0, default=None, metavar="T",
                     help="with --denoise: clamp a pixel brighter than T x its brightest 3x3 neighbour ahead of the filter (fireflies; default T = 2)")
@@ -73,6 +77,8 @@ def main():
         r.setDenoiseOptions(enabled=1, apply_to_target=1)
     if a.despeckle is not None:
         r.setDespeckleOptions(enabled=1, threshold=a.despeckle)
+    if a.auto_exposure is not None:
+        r.setExposureOptions(enabled=1, target_log2=a.auto_exposure)
     if a.adaptive is not None:
         if a.gmon > 1:
             ap.error("--adaptive does not combine with --gmon")
@@ -88,6 +94,10 @@ def main():
     r.setPostProcessOptions(po)
     img = r.readbackRenderTarget()
     write_png_rgba8(a.output, img)
+    if a.auto_exposure is not None:
+        m = r.readbackExposureMeter()   # (no smoothing: the ev a read resolves now is the one the image above got)
+        print(f"auto exposure: {m.metered} pixels metered ({m.below} below, {m.above} above, {m.nonfinite} non-finite), mean log2 luminance {m.mean_log2:.3f}, "
+              f"applied {m.ev:+.3f} EV (gain {m.gain:.4g})")
     st = r.stats()
     print(f"setup {t1 - t0:.2f} s (BVH {st.bvh_build_ms:.1f} ms), render {t2 - t1:.3f} s = {a.size[0] * a.size[1] * a.spp * a.bounces / (t2 - t1) / 1e6:.0f} Msamples/s, wrote {a.output}")
     if a.adaptive is not None:
