@@ -519,6 +519,27 @@ int pt_set_render_region(pt_renderer* r, const pt_render_region* o);
  * activates, ascending; every tile when enabled = 0.  Writes up to `capacity` of them and their total number to *count. */
 int pt_region_tiles(uint32_t width, uint32_t height, const pt_render_region* o, uint32_t* tiles_out, uint32_t capacity, uint32_t* count);
 
+/* ---- camera-ray leaf lists (NEW, an additive extension of ABI 5: one new entry point and one new struct, no existing struct changed) ----
+ * At pt_start_render, for a pinhole camera (apertureRadius <= 0) over the one-BVH structure in its 6-wide form, a full-frame non-adaptive
+ * render builds for every pixel the list of tree nodes whose leaf children the pixel's camera rays can reach, and traces bounce 0 of every
+ * batch from it instead of walking the tree from the root once per sample.  Every output is the bits of a render without the lists
+ * ($PTAMD_NO_CAMERA_LISTS=1 keeps them off).  A pixel whose list does not fit `capacity` entries is traced by the ordinary traversal.
+ * Not built (built = 0, everything else 0) for: a thin-lens camera, the two-level structure, 4-wide nodes, adaptive sampling, a render
+ * region, $PTAMD_NO_CAMERA_LISTS, or when the lists would take more than 1/16 of the free device memory. */
+#define PT_CAMLIST_HIST_BINS 65
+typedef struct pt_camera_list_stats {
+  uint32_t built;           /* 1: this render traces its camera rays from the lists */
+  uint32_t capacity;        /* entries per pixel */
+  uint64_t pixels_listed;   /* pixels with a list (an empty one included) */
+  uint64_t pixels_walk;     /* pixels whose list did not fit: traced by the ordinary traversal */
+  uint64_t entries;         /* entries of all lists */
+  double build_ms;          /* device time of the build (HIP events) */
+  uint32_t length_histogram[PT_CAMLIST_HIST_BINS];  /* pixels by list length before the capacity is applied: 0 .. 63, 64 or more */
+  uint32_t _pad;
+} pt_camera_list_stats;
+/* PT_ERR_BAD_STATE before pt_start_render.  Does not block. */
+int pt_get_camera_list_stats(pt_renderer* r, pt_camera_list_stats* out);
+
 const char* pt_last_error(void);
 
 /* ---------------------------------------------------------------------------------------------------------- */

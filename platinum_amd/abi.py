@@ -203,6 +203,12 @@ class RenderRegion(C.Structure):
     _fields_ = [("enabled", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("x1", C.c_uint32), ("y1", C.c_uint32)]
 
 
+class CameraListStats(C.Structure):
+    """pt_camera_list_stats: the per-pixel leaf lists of the camera rays (built or not, pixels listed / left to the walk, entries, build ms)."""
+    _fields_ = [("built", C.c_uint32), ("capacity", C.c_uint32), ("pixels_listed", C.c_uint64), ("pixels_walk", C.c_uint64),
+                ("entries", C.c_uint64), ("build_ms", C.c_double), ("length_histogram", C.c_uint32 * 65), ("_pad", C.c_uint32)]
+
+
 class HitRecord(C.Structure):
     _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("instance", C.c_int32), ("primitive", C.c_int32)]
 
@@ -276,6 +282,7 @@ SYMBOLS = [
     ("pt_default_render_region", None, [C.POINTER(RenderRegion)]),
     ("pt_set_render_region", C.c_int, [C.c_void_p, C.POINTER(RenderRegion)]),
     ("pt_region_tiles", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(RenderRegion), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("pt_get_camera_list_stats", C.c_int, [C.c_void_p, C.POINTER(CameraListStats)]),
     ("pt_last_error", C.c_char_p, []),
     ("pt_get_constants", C.c_int, [C.c_void_p, C.POINTER(Constants)]),
     ("pt_get_lights", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),

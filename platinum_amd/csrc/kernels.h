@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "pt_camlist.h"
 #include "pt_device.h"
 #include "pt_layout.h"
 #include "pt_post.h"
@@ -50,6 +51,12 @@ uint32_t trace_block_threads(bool two_level);
 uint32_t trace_blocks_per_cu_two_level();  // 256 (7 blocks per CU) for one BVH, 1024 (one block per CU) for the two-level structure
 void launch_trace_closest(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState st, vec4* hit, Segments seg, uint32_t cur,
                           BatchCounters* ctr, uint32_t bounce, uint32_t* spill, int32_t* hitlog, uint32_t log_stride, bool count);
+// Bounce 0 of a render batch from the per-pixel leaf lists `cl` (camera_lists.hip) instead of launch_trace_closest: k_trace_camera (`grid` blocks,
+// camera_blocks_per_cu() per CU) and, when the build flagged pixels (any_unlisted), the ordinary traversal for their rays (`grid_unlisted` blocks
+// as launch_trace_closest takes them).  One-BVH 6-wide structure only.
+void launch_trace_camera(hipStream_t s, uint32_t grid, uint32_t grid_unlisted, const DeviceScene& S, PathState st, vec4* hit, Segments seg,
+                         BatchCounters* ctr, uint32_t* spill, const CameraLists& cl, bool any_unlisted);
+uint32_t camera_blocks_per_cu();
 // `grid` blocks of shade_block_threads() threads (a persistent grid: shade_blocks_per_cu() per CU keeps it resident)
 uint32_t shade_block_threads();
 uint32_t shade_blocks_per_cu();

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "pt_camlist.h"
 #include "pt_denoise.h"
 #include "pt_post.h"
 #include "pt_shade.h"
@@ -397,10 +398,12 @@ __device__ __forceinline__ const BvhNode* stage_nodes(const DeviceScene& S, BvhN
 }
 
 // ---- closest hit ---------------------------------------------------------------------------------------------------
-template <bool COUNT, bool TWO, bool W6 = false>
-__global__ void __launch_bounds__(TWO ? kTraceBlock2 : kBlock, TWO ? PT_TWO_BLOCKS_PER_CU : PT_CLOSEST_WAVES)
-k_trace_closest(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments seg, uint32_t cur, BatchCounters* __restrict__ ctr, uint32_t bounce,
-                uint32_t* __restrict__ spill, int32_t* __restrict__ hitlog, uint32_t log_stride) {
+// (the body of k_trace_closest.  UNLISTED: the instantiation behind k_trace_closest_unlisted, which walks the tree for the camera rays of the
+//  pixels whose list did not fit and drops every other ray of the queue: k_trace_camera has traced those.  `cursor`: the launch's claim cursor.)
+template <bool COUNT, bool TWO, bool W6, bool UNLISTED>
+__device__ __forceinline__ void trace_closest_body(const DeviceScene& S, PathState st, vec4* __restrict__ hit, const Segments& seg, uint32_t cur,
+                                                   BatchCounters* __restrict__ ctr, uint32_t bounce, uint32_t* __restrict__ cursor,
+                                                   uint32_t* __restrict__ spill, int32_t* __restrict__ hitlog, uint32_t log_stride, const CameraLists& cl) {
   PT_TAIL_BEGIN
   constexpr uint32_t kTB = TWO ? kTraceBlock2 : kBlock;
   __shared__ uint32_t lds_stack[(W6 ? kLdsStack6 : kLdsStack) + 1][kTB];
@@ -409,7 +412,7 @@ k_trace_closest(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments se
   const BvhNode* lds_nodes = TWO && kLdsNodes ? stage_nodes(S, lds_nodes_buf) : nullptr;
   const uint32_t lane = wave_lane();
   ChunkClaims src;
-  src.init(seg.table_closest, ctr->chunks_closest[bounce], &ctr->work_closest[bounce], seg, lane);
+  src.init(seg.table_closest, ctr->chunks_closest[bounce], cursor, seg, lane);
   TraversalStack stack;
   stack.lds = &lds_stack[0][threadIdx.x];
   stack.pend = &lds_pend[0][threadIdx.x];
@@ -453,7 +456,9 @@ k_trace_closest(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments se
       ts.dbg = ctr->_pad[1] == bounce + 1u && segment_lbuf_base(seg, slot_segment(seg.nseg, ray)) + (f2u(d4.w) >> kMetaPidShift) == ctr->_pad[0];
       if (ts.dbg) printf("dbg ray slot %u lane %u wave %u o %.9g %.9g %.9g d %.9g %.9g %.9g\n", ray, lane, wave_index(), o4.x, o4.y, o4.z, d4.x, d4.y, d4.z);
 #endif
-      if (trav_init(S, ts, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), 1e-3f, kInf, ir, stack, false, COUNT ? &tc : nullptr)) finish();
+      if (UNLISTED && cl.count[pixel_slot_of_pid(segment_lbuf_base(seg, slot_segment(seg.nseg, ray)) + (f2u(d4.w) >> kMetaPidShift), seg.nsamples)] != kCamWalk)
+        ray = kInvalidRef;   // a listed pixel's ray: hit[ray] holds k_trace_camera's answer
+      else if (trav_init(S, ts, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), 1e-3f, kInf, ir, stack, false, COUNT ? &tc : nullptr)) finish();
     }
     PT_TAIL_T(tail_setup)
     if (__ballot(ray != kInvalidRef) == 0) {
@@ -475,6 +480,83 @@ k_trace_closest(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments se
     }
   }
   PT_TAIL_END(0)
+}
+
+template <bool COUNT, bool TWO, bool W6 = false>
+__global__ void __launch_bounds__(TWO ? kTraceBlock2 : kBlock, TWO ? PT_TWO_BLOCKS_PER_CU : PT_CLOSEST_WAVES)
+k_trace_closest(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments seg, uint32_t cur, BatchCounters* __restrict__ ctr, uint32_t bounce,
+                uint32_t* __restrict__ spill, int32_t* __restrict__ hitlog, uint32_t log_stride) {
+  trace_closest_body<COUNT, TWO, W6, false>(S, st, hit, seg, cur, ctr, bounce, &ctr->work_closest[bounce], spill, hitlog, log_stride, CameraLists{});
+}
+
+// ---- camera rays from per-pixel leaf lists (pt_camlist.h; built once per render by camera_lists.hip) --------------------------------------
+// Bounce 0 of a render batch of a pinhole camera over the 6-wide one-BVH structure.  Same chunk table, same claims, same hit[] record as
+// k_trace_closest; but a camera ray's candidates are known before it exists: its pixel's list names every node with a leaf child the pixel's cone
+// can touch, nearest first.  A lane takes a ray, finds its pixel (slot -> pid -> pixel slot: a chunk straddles pixels whenever the batch is not
+// a multiple of 64 samples) and runs ITS OWN slab test (node6_slabs: the walk's arithmetic) against the leaf children each entry names and
+// trav_leaf on those that pass, until an entry lies beyond best.t * kCamCullSlack.  So a triangle is tested iff its leaf child passes this
+// ray's slab test, as in the walk; what differs is the order in which candidates lower best.t, against which the list trace culls with a
+// wider margin than the walk (kCamCullSlack, pt_camlist.h).  No node stack, no leaf queue, no LDS; the next entry's node is fetched while the current one's triangles are tested.  The 64
+// lanes of a chunk are samples of one pixel (k_raygen): they read the same list and the same nodes.  Pixels flagged kCamWalk are left to
+// k_trace_closest_unlisted.
+#ifndef PT_CAMERA_WAVES
+#define PT_CAMERA_WAVES 6
+#endif
+__global__ void __launch_bounds__(kBlock, PT_CAMERA_WAVES)
+k_trace_camera(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments seg, BatchCounters* __restrict__ ctr, CameraLists cl) {
+  const uint32_t lane = wave_lane();
+  ChunkClaims src;
+  src.init(seg.table_closest, ctr->chunks_closest[0], &ctr->work_closest[0], seg, lane);
+  const BvhNode6* __restrict__ nodes = reinterpret_cast<const BvhNode6*>(S.nodes);
+  for (;;) {
+    const uint32_t ray = src.take(true);   // every lane wants a ray: the lanes of a wave all start and end a chunk together
+    if (__ballot(ray != kInvalidRef) == 0) break;   // (take() returns nothing for every lane only when no chunk is left)
+    if (ray != kInvalidRef) {
+      const vec4 o4 = st.rayO[ray];
+      const vec4 d4 = st.rayD[ray];
+      const uint32_t q = pixel_slot_of_pid(segment_lbuf_base(seg, slot_segment(seg.nseg, ray)) + (f2u(d4.w) >> kMetaPidShift), seg.nsamples);
+      const uint32_t len = cl.count[q];
+      if (len != kCamWalk) {
+        float ir = 0.0f;  // alpha-test payload, as in k_trace_closest
+        if (S.has_alpha) ir = Halton{halton_table(S.halton), f2u(st.att[ray].w), f2u(d4.w) & kMetaDimMask}.sample1d();
+        TravState ts;
+        (void)trav_init(S, ts, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), 1e-3f, kInf, ir, TraversalStack{}, false, nullptr);   // (lists exist only over a tree whose root is a node)
+        const CamListEntry* __restrict__ list = cl.entries + (size_t)q * cl.cap;
+        // The addresses do not depend on the traversal: entry i + 1 is loaded one step ahead, and its node is fetched as soon as entry i's slab
+        // tests are done with the node registers — it arrives while entry i's triangles are tested.  (Holding two whole nodes cost 62 spilled
+        // registers at 8 waves per SIMD.)
+        const CamListEntry none{0u, kInf};
+        CamListEntry e = len ? list[0] : none;
+        uint32_t i = 0, m = 0, base_leaf = 0;   // m: the leaf children of the current entry still to be tested
+        for (;;) {
+          if (m == 0u) {
+            if (i >= len || e.dist > ts.best.t * kCamCullSlack) break;
+            const BvhNode6 n = nodes[e.ref >> 6];
+            m = node6_leaf_hits(n, ts, ts.best.t * kCamCullSlack) & e.ref & 63u;
+            base_leaf = n.base_leaf;
+            i++;
+            e = i < len ? list[i] : none;
+          } else {
+            const uint32_t r = (uint32_t)__builtin_ctz(m);
+            m &= m - 1u;
+            bool fin = false;
+            trav_leaf(S, ts, kLeafBit | (base_leaf + r), false, &fin, nullptr);
+          }
+        }
+        const RayHit& h = ts.best;
+        hit[ray] = vec4{h.t, h.u, h.v, u2f(h.tri == kInvalidRef ? kInvalidRef : (h.tri | ((h.gid & 3u) << 28)))};
+      }
+    }
+  }
+}
+
+// the ordinary traversal for the camera rays of the pixels flagged kCamWalk (launched only when the build flagged any); its claims run on a
+// cursor of its own (work_closest[63]: bounces stop at 50), k_trace_camera has used up bounce 0's
+constexpr uint32_t kUnlistedCursor = 63;
+__global__ void __launch_bounds__(kBlock, PT_CLOSEST_WAVES)
+k_trace_closest_unlisted(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments seg, BatchCounters* __restrict__ ctr, uint32_t* __restrict__ spill,
+                         CameraLists cl) {
+  trace_closest_body<false, false, true, true>(S, st, hit, seg, 0u, ctr, 0u, &ctr->work_closest[kUnlistedCursor], spill, nullptr, 0u, cl);
 }
 
 // ---- shade -----------------------------------------------------------------------------------------------------------
@@ -1071,6 +1153,12 @@ void launch_trace_closest(hipStream_t s, uint32_t grid, const DeviceScene& S, Pa
   else
     hipLaunchKernelGGL((k_trace_closest<false, false>), dim3(grid), dim3(kBlock), 0, s, S, st, hit, seg, cur, ctr, bounce, spill, hitlog, log_stride);
 }
+void launch_trace_camera(hipStream_t s, uint32_t grid, uint32_t grid_unlisted, const DeviceScene& S, PathState st, vec4* hit, Segments seg,
+                         BatchCounters* ctr, uint32_t* spill, const CameraLists& cl, bool any_unlisted) {
+  hipLaunchKernelGGL(k_trace_camera, dim3(grid), dim3(kBlock), 0, s, S, st, hit, seg, ctr, cl);
+  if (any_unlisted) hipLaunchKernelGGL(k_trace_closest_unlisted, dim3(grid_unlisted), dim3(kBlock), 0, s, S, st, hit, seg, ctr, spill, cl);
+}
+uint32_t camera_blocks_per_cu() { return PT_CAMERA_WAVES; }
 uint32_t shade_block_threads() { return kShadeBlock; }
 uint32_t shade_blocks_per_cu() { return (PT_SHADE_WAVES * 4 * 64) / PT_SHADE_BLOCK; }
 void launch_shade(hipStream_t s, uint32_t grid, const DeviceScene* S, PathState sin, PathState sout, const vec4* hit,

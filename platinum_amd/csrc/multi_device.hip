@@ -780,6 +780,16 @@ int pt_set_render_region(pt_renderer* r, const pt_render_region* o) {
   return PT_OK;
 }
 
+// every member of a group builds its own lists of the same camera and scene: the first started member's are reported
+int pt_get_camera_list_stats(pt_renderer* r, pt_camera_list_stats* out) {
+  if (!is_group(r)) return dev_get_camera_list_stats(r, out);
+  if (!out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  DeviceGroup* grp = r->group;
+  pt_renderer* m = grp->started ? first_started(grp) : nullptr;
+  if (!m) return fail(PT_ERR_BAD_STATE, "pt_get_camera_list_stats before pt_start_render");
+  return dev_get_camera_list_stats(m, out);
+}
+
 // a group's render is uniform: every pixel holds the samples of all members
 int pt_read_sample_counts(pt_renderer* r, uint32_t* out) {
   if (!is_group(r)) return dev_read_sample_counts(r, out);

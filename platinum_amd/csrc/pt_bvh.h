@@ -475,10 +475,10 @@ PT_HD BvhNode6 quantize_node6(const Box3* boxes, int n_int, int n_leaf, uint32_t
 // test are queued together as base_leaf << 6 | mask, the triangle rounds take them out one bit at a time).  The nearest internal child
 // becomes `cur`, the others are pushed in slot order (host probe, C3: 13.69 nodes per ray against 13.44 fully sorted and 16.95 with
 // 4-wide nodes; the 6-element sorting network would cost ~35 VALU and six more live registers).
-template <bool COUNT>
-PT_HD void trav_node6(const BvhNode* __restrict__ nodes, TravState& ts, TraversalCount* cnt) {
-  const BvhNode6 n = reinterpret_cast<const BvhNode6*>(nodes)[ts.cur];
-  if (COUNT) cnt->nodes++;
+// The slab tests of one 6-wide node against the ray in ts, culled at far_lim (the walk: best.t * kCullSlack): bit k of the result = child k passed.  *best_k = the
+// nearest internal child that passed.  The ONE place this arithmetic is spelt: the walk (trav_node6) and the list trace of the camera rays
+// (node6_leaf_hits, pt_camlist.h) decide with the same instructions whether a ray tests a leaf child's triangles.
+PT_HD uint32_t node6_slabs(const BvhNode6& n, const TravState& ts, float far_lim, uint32_t* best_k_out) {
   const float ax = node_scale(n.exp[0]) * ts.inv.x, ay = node_scale(n.exp[1]) * ts.inv.y, az = node_scale(n.exp[2]) * ts.inv.z;
   const float bx = (n.origin[0] - ts.o.x) * ts.inv.x, by = (n.origin[1] - ts.o.y) * ts.inv.y, bz = (n.origin[2] - ts.o.z) * ts.inv.z;
   // entry / exit planes per axis by direction sign: children 0..3 one select per dword, children 4, 5 the halves of the third dword
@@ -489,7 +489,6 @@ PT_HD void trav_node6(const BvhNode* __restrict__ nodes, TravState& ts, Traversa
   const uint32_t ny2 = ts.negy ? n.q[1][2] >> 16 : n.q[1][2], fy2 = ts.negy ? n.q[1][2] : n.q[1][2] >> 16;
   const uint32_t nz2 = ts.negz ? n.q[2][2] >> 16 : n.q[2][2], fz2 = ts.negz ? n.q[2][2] : n.q[2][2] >> 16;
   const uint32_t n_int = n.counts & 7u, count = n_int + ((n.counts >> 3) & 7u);
-  const float far_lim = ts.best.t * kCullSlack;
   float best_d = kInf;
   uint32_t best_k = 0, hits = 0;  // hits: bit k = child k passed the slab test
 #pragma unroll
@@ -508,8 +507,24 @@ PT_HD void trav_node6(const BvhNode* __restrict__ nodes, TravState& ts, Traversa
     best_d = nearer ? tn : best_d;
     best_k = nearer ? (uint32_t)k : best_k;
   }
+  *best_k_out = best_k;
+  return hits;
+}
+// ... the leaf children among them: bit r = leaf child r (child n_int + r, triangle slot base_leaf + r) passed
+PT_HD uint32_t node6_leaf_hits(const BvhNode6& n, const TravState& ts, float far_lim) {
+  uint32_t best_k;
+  return node6_slabs(n, ts, far_lim, &best_k) >> (n.counts & 7u);
+}
+
+template <bool COUNT>
+PT_HD void trav_node6(const BvhNode* __restrict__ nodes, TravState& ts, TraversalCount* cnt) {
+  const BvhNode6 n = reinterpret_cast<const BvhNode6*>(nodes)[ts.cur];
+  if (COUNT) cnt->nodes++;
+  uint32_t best_k;
+  const uint32_t hits = node6_slabs(n, ts, ts.best.t * kCullSlack, &best_k);
+  const uint32_t n_int = n.counts & 7u;
 #if defined(PT_DEBUG_PID) && defined(__HIP_DEVICE_COMPILE__)
-  if (ts.dbg) printf("dbg node %u: n_int %u count %u hits %x base_node %u base_leaf %u best.t %.9g\n", ts.cur, n_int, count, hits, n.base_node, n.base_leaf, ts.best.t);
+  if (ts.dbg) printf("dbg node %u: n_int %u count %u hits %x base_node %u base_leaf %u best.t %.9g\n", ts.cur, n_int, n_int + ((n.counts >> 3) & 7u), hits, n.base_node, n.base_leaf, ts.best.t);
 #endif
   // leaf children that were hit: one queue entry (branch-free: no entry -> the scratch row)
   const uint32_t leaf_mask = hits >> n_int;

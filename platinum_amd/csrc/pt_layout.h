@@ -57,6 +57,10 @@ PT_HD uint32_t pixel_of_pid_1spp(uint32_t pid, uint32_t W) {
   const uint32_t ty = tile / tilesX, tx = tile - ty * tilesX;
   return (ty * 8u + (lane >> 3)) * W + tx * 8u + (lane & 7u);
 }
+// ... of a batch of `nsamples`: a pixel's samples are consecutive, so pid / nsamples = tile * 64 + lane, the pixel's SLOT in tile-major order
+// (what the camera-ray lists are indexed by: pt_camlist.h), and that is the pid of the one-sample layout.
+PT_HD uint32_t pixel_slot_of_pid(uint32_t pid, uint32_t nsamples) { return nsamples == 1u ? pid : pid / nsamples; }
+PT_HD uint32_t pixel_of_pid(uint32_t pid, uint32_t nsamples, uint32_t W) { return pixel_of_pid_1spp(pixel_slot_of_pid(pid, nsamples), W); }
 
 // ---- queue segments --------------------------------------------------------------------------------------------------
 // Slot of entry r of segment s.  Segments are interleaved in GROUPS of PT_SEG_GROUP 64-entry chunks: chunks 16g .. 16g + 15 of a

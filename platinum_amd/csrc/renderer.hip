@@ -91,7 +91,13 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
   for (uint32_t b = 0; b < S.max_bounces; b++) {
     {
       ScopedTimer t(r, K_CLOSEST);
-      launch_trace_closest(s, r->closest_grid, S, r->path_state(cur), r->hit.p, seg, (uint32_t)cur, ctr, b, r->spill.p, hitlog, S.width * S.height, count);
+      // the camera rays of a render batch come from the per-pixel leaf lists when the render has them; the debug and measuring batches keep the walk
+      // (the hit log and nodes_per_ray stay what they are)
+      if (b == 0 && mode == BATCH_RENDER && r->cam_lists)
+        launch_trace_camera(s, r->camera_grid, r->closest_grid, S, r->path_state(cur), r->hit.p, seg, ctr, r->spill.p,
+                            CameraLists{r->cam_entries.p, r->cam_count.p, r->cam_cap}, r->cam_stats.pixels_walk != 0);
+      else
+        launch_trace_closest(s, r->closest_grid, S, r->path_state(cur), r->hit.p, seg, (uint32_t)cur, ctr, b, r->spill.p, hitlog, S.width * S.height, count);
     }
     // first-hit AOVs of a render that keeps them (denoise.hip): the camera rays' hits, read from the queue before k_shade consumes it
     if (b == 0 && mode == BATCH_RENDER && r->aov) launch_aov(s, r->grid, r->scene_d.p, r->path_state(cur), r->hit.p, seg, r->Abuf.p);
@@ -266,6 +272,8 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   if (const char* e = getenv("PTAMD_TWO_LEVEL")) r->two_level_override = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("PTAMD_BLOCKS_PER_CU")) r->blocks_per_cu = (uint32_t)std::max(1, std::min(8, atoi(e)));
   if (const char* e = getenv("PTAMD_CLOSEST_BLOCKS_PER_CU")) r->closest_blocks_per_cu = (uint32_t)std::max(1, std::min(8, atoi(e)));
+  if (const char* e = getenv("PTAMD_NO_CAMERA_LISTS")) r->no_camera_lists = atoi(e) != 0;
+  if (const char* e = getenv("PTAMD_TEST_CAMLIST_CAP")) r->cam_cap_override = (uint32_t)std::max(1, std::min((int)kCamListMaxCapacity, atoi(e)));
   if (const char* e = getenv("PTAMD_SHADOW_BLOCKS_PER_CU")) r->shadow_blocks_per_cu = (uint32_t)std::max(1, std::min(8, atoi(e)));
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, r->device) == hipSuccess) r->num_cu = prop.multiProcessorCount;
@@ -508,8 +516,57 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   launch_light_records(r->stream, S, r->light_recs.p, r->light_cdf.p);
   PT_HIP(r->scene_d.upload(std::vector<DeviceScene>(1, S)));  // k_shade reads the table from memory (scalar loads)
 
-  // ---- wavefront buffers ----
   phase("shade / light records");
+
+  // ---- per-pixel leaf lists of the camera rays (camera_lists.hip): taken BEFORE the queues are planned, and bounded ----
+  {
+    r->cam_stats = pt_camera_list_stats{};
+    const bool want = !r->no_camera_lists && !r->two_level && r->bvh.wide6 && S.root_ref != kInvalidRef && !(S.root_ref & kLeafBit) &&
+                      !(S.camera.apertureRadius > 0.0f) && !r->adaptive_opts.enabled && !r->region_opts.enabled;
+    const uint32_t cap = r->cam_cap_override ? r->cam_cap_override : kCamListCapacity;
+    const size_t slots = (size_t)tile_count(p->width, p->height) * 64;
+    const size_t bytes = slots * ((size_t)cap * sizeof(CamListEntry) + sizeof(uint32_t));
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+    free_b += r->cam_entries.bytes_held() + r->cam_count.bytes_held();
+    // the bound: 1/16 of what is free (the lists of a 1920x1080 frame reserve 2.1 GB, a 3840x2160 frame's 8.5 GB; only the entries in use are
+    // ever touched); a render that cannot spare that traces its camera rays as before
+    if (want && bytes <= free_b / 16) {
+      PT_HIP(r->cam_entries.alloc(slots * cap));
+      PT_HIP(r->cam_count.alloc(slots));
+      PT_HIP(r->cam_counters.alloc(1));
+      PT_HIP(hipMemsetAsync(r->cam_counters.p, 0, sizeof(CamListCounters), r->stream));
+      struct EventPair {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+      } ev;
+      PT_HIP(hipEventCreate(&ev.e0));
+      PT_HIP(hipEventCreate(&ev.e1));
+      PT_HIP(hipEventRecord(ev.e0, r->stream));
+      launch_camera_lists(r->stream, S, r->cam_entries.p, r->cam_count.p, cap, r->cam_counters.p);
+      PT_HIP(hipEventRecord(ev.e1, r->stream));
+      PT_HIP(hipEventSynchronize(ev.e1));
+      PT_HIP(hipGetLastError());
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, ev.e0, ev.e1);
+      CamListCounters c{};
+      PT_HIP(hipMemcpy(&c, r->cam_counters.p, sizeof(c), hipMemcpyDeviceToHost));
+      r->cam_cap = cap;
+      r->cam_lists = true;
+      r->cam_stats.built = 1u;
+      r->cam_stats.capacity = cap;
+      r->cam_stats.pixels_listed = c.listed;
+      r->cam_stats.pixels_walk = c.walk;
+      r->cam_stats.entries = c.entries;
+      r->cam_stats.build_ms = ms;
+      for (uint32_t k = 0; k < kCamHistBins; k++) r->cam_stats.length_histogram[k] = c.hist[k];
+    } else {
+      r->release_camera_lists();
+    }
+  }
+  phase("camera lists");
+
+  // ---- wavefront buffers ----
   const uint64_t npix = (uint64_t)p->width * p->height;
   const bool aov = r->denoise.enabled != 0;
   if (!aov) { r->Abuf.release(); r->aov_img.release(); }  // (an AOV-off render holds nothing more than before)
@@ -526,6 +583,9 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
     else free_b += r->queue_bytes_held();  // what the previous render's queues occupy is reused, i.e. available
+    // (the camera-ray lists were taken first; the queues are planned as if they had not been — a quarter of the free memory is the queues' budget,
+    //  and a render sizes its batches the same with and without lists)
+    if (free_b) free_b += r->cam_entries.bytes_held() + r->cam_count.bytes_held();
     if (aov && free_b) {  // AOVs add 32 B per path slot to the ~200 B of queue state the automatic choice assumes
       free_b += r->Abuf.bytes_held();
       free_b = free_b / 232 * 200;
@@ -543,6 +603,7 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   const uint32_t sif = r->samples_in_flight;
   r->grid = (uint32_t)r->num_cu * r->blocks_per_cu;                 // raygen, hit records: 256-thread blocks
   r->shade_grid = (uint32_t)r->num_cu * shade_blocks_per_cu();     // as many blocks as k_shade's registers / LDS keep resident
+  r->camera_grid = (uint32_t)r->num_cu * camera_blocks_per_cu();
   r->closest_grid = (uint32_t)r->num_cu * (r->two_level ? trace_blocks_per_cu_two_level() : r->closest_blocks_per_cu);
   r->shadow_grid = (uint32_t)r->num_cu * (r->two_level ? trace_blocks_per_cu_two_level() : r->shadow_blocks_per_cu);
   r->nstats = std::max(r->grid * (kBlock / 64), r->shade_grid * (shade_block_threads() / 64));
@@ -1045,6 +1106,13 @@ extern "C" void pt_default_render_region(pt_render_region* o) {
 }
 
 // (the options are checked before the renderer, as dev_set_adaptive_options)
+int dev_get_camera_list_stats(pt_renderer* r, pt_camera_list_stats* out) {
+  if (!r || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (!r->started) return fail(PT_ERR_BAD_STATE, "pt_get_camera_list_stats before pt_start_render");
+  *out = r->cam_stats;
+  return PT_OK;
+}
+
 int dev_set_render_region(pt_renderer* r, const pt_render_region* o) {
   if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
   if (o->enabled && (o->x0 >= o->x1 || o->y0 >= o->y1))

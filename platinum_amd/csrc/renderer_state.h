@@ -10,6 +10,7 @@
 
 #include "host_scene.h"
 #include "adaptive.h"
+#include "camera_lists.h"
 #include "denoise.h"
 #include "exposure.h"
 #include "kernels.h"
@@ -158,6 +159,16 @@ struct pt_renderer {
   bool vtiles = false;              // adaptive || region: batches address virtual tiles through ad_list
   Rect rect{};                      // what this render samples: the region, or the whole frame
   uint32_t ad_tiles0 = 0;           // length of the first active list: the lists' capacity, the most tiles a batch can cover
+  // per-pixel leaf lists of the camera rays (camera_lists.hip): built at pt_start_render for a pinhole camera over the 6-wide one-BVH
+  // structure of a full-frame, non-adaptive render; every other render releases them and traces bounce 0 with k_trace_closest as before
+  DevBuf<CamListEntry> cam_entries;    // [pixel slot][cam_cap]
+  DevBuf<uint32_t> cam_count;          // [pixel slot] entries, or kCamWalk
+  DevBuf<CamListCounters> cam_counters;
+  bool cam_lists = false;              // this render traces bounce 0 of its batches from the lists
+  bool no_camera_lists = false;        // $PTAMD_NO_CAMERA_LISTS: never build them (the A/B switch)
+  uint32_t cam_cap = 0, cam_cap_override = 0;   // entries per pixel; $PTAMD_TEST_CAMLIST_CAP (tests only: a tiny capacity exercises the kCamWalk path)
+  pt_camera_list_stats cam_stats{};
+  uint32_t camera_grid = 0;
   uint32_t closest_grid = 0, shadow_grid = 0, closest_blocks_per_cu = PT_CLOSEST_WAVES, shadow_blocks_per_cu = PT_SHADOW_WAVES;  // persistent trace grids, each sized for its kernel's occupancy
   uint32_t last_batch_ns = 0, last_batch_first = 0;  // the batch Lbuf holds ($PTAMD_DEBUG_PIXEL)
   uint32_t nseg = 0, tiles_per_seg = 1, seg_bands = 4, tiles_per_seg_override = 0, nstats = 0, seg_cap = 0, blocks_per_cu = 6, shade_grid = 0, refill_threshold = 48;
@@ -204,6 +215,7 @@ struct pt_renderer {
     acc = nullptr;
     started = false;
     aov = false;
+    cam_lists = false;
     adaptive = false;
     region = false;
     vtiles = false;
@@ -227,8 +239,10 @@ struct pt_renderer {
     hit.release(); sq_o.release(); sq_d.release(); sq_c.release(); Lbuf.release(); acc_own.release(); spill.release();
     Abuf.release(); aov_img.release(); dn_guide.release(); dn_aux.release(); dn_col[0].release(); dn_col[1].release(); denoised.release();
     exp_rec.release(); exp_img.release();
+    release_camera_lists(); cam_counters.release();
     release_adaptive();
   }
+  void release_camera_lists() { cam_entries.release(); cam_count.release(); cam_lists = false; }
   void release_adaptive() {
     release_checkpoints();
     ad_list[0].release(); ad_list[1].release(); ad_count.release(); ad_tile_n.release();
@@ -280,3 +294,4 @@ int dev_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32
 int dev_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o);
 int dev_read_sample_counts(pt_renderer* r, uint32_t* out);
 int dev_set_render_region(pt_renderer* r, const pt_render_region* o);
+int dev_get_camera_list_stats(pt_renderer* r, pt_camera_list_stats* out);

@@ -333,6 +333,12 @@ class Renderer:
         abi.check(self._lib, self._lib.pt_get_stats(self._h, C.byref(s)))
         return s
 
+    def cameraListStats(self):
+        """pt_get_camera_list_stats: the per-pixel leaf lists the camera rays of this render are traced from (built = 0: none)."""
+        s = abi.CameraListStats()
+        abi.check(self._lib, self._lib.pt_get_camera_list_stats(self._h, C.byref(s)))
+        return s
+
     def setProfiling(self, enabled):
         abi.check(self._lib, self._lib.pt_set_profiling(self._h, int(enabled)))
 

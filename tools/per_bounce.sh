@@ -16,7 +16,12 @@ names = [r["Kernel_Name"] for r in rows]
 last = max(i for i, n in enumerate(names) if "k_raygen" in n)   # the timed batch = the LAST raygen onwards
 seq = rows[last:]
 def dur(r): return (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
-cl = [dur(r) for r in seq if "k_trace_closest" in r["Kernel_Name"]]
+# (bounce 0 of a render with camera-ray lists is k_trace_camera, plus k_trace_closest_unlisted when pixels were left to the walk: one entry)
+cl = []
+for r in seq:
+    n = r["Kernel_Name"]
+    if "k_trace_closest_unlisted" in n: cl[-1] += dur(r)
+    elif "k_trace_closest" in n or "k_trace_camera" in n: cl.append(dur(r))
 sh = [dur(r) for r in seq if "k_shade" in r["Kernel_Name"] and "records" not in r["Kernel_Name"]]
 sd = [dur(r) for r in seq if "k_trace_shadow" in r["Kernel_Name"]]
 print("$WL: bounce | closest chunks  ms  Grays/s | shade ms | shadow chunks  ms  Grays/s")
