@@ -15,6 +15,8 @@
 #include <vector>
 
 #include "pt_device.h"
+#include "pt_camlist.h"
+#include "pt_layout.h"
 
 namespace pt {
 
@@ -419,6 +421,74 @@ inline int build_host_scene(const pt_scene_snapshot* scene, const pt_render_para
   C.totalLightPower = totalPower;
 
   return PT_OK;
+}
+
+// ---- the decisions of pt_start_render (renderer.hip), kept free of HIP so that tests/test_start_plan_host.py reaches them ----
+
+// The two-level structure's per-instance records: the inverse of every instance's 3x3 (in double, rounded once) beside its translation.
+// Returns whether EVERY instance is invertible; when one is not, the records are not used.
+inline bool instance_trav_records(const std::vector<InstanceInfo>& instances, std::vector<InstanceTrav>* out) {
+  out->assign(instances.size(), InstanceTrav{});
+  for (size_t i = 0; i < instances.size(); i++) {
+    const InstanceInfo& in = instances[i];
+    M3d m{};
+    for (int k = 0; k < 3; k++) { m.m[0][k] = in.c0[k]; m.m[1][k] = in.c1[k]; m.m[2][k] = in.c2[k]; }
+    const double det = m.m[0][0] * (m.m[1][1] * m.m[2][2] - m.m[2][1] * m.m[1][2]) - m.m[1][0] * (m.m[0][1] * m.m[2][2] - m.m[2][1] * m.m[0][2]) +
+                       m.m[2][0] * (m.m[0][1] * m.m[1][2] - m.m[1][1] * m.m[0][2]);
+    double scale = 0;
+    for (int c = 0; c < 3; c++) for (int k = 0; k < 3; k++) scale = std::max(scale, std::fabs(m.m[c][k]));
+    if (!(std::fabs(det) > 1e-12 * scale * scale * scale) || !std::isfinite(det)) return false;
+    const M3d inv = m3_inv(m);
+    InstanceTrav& t = (*out)[i];
+    for (int k = 0; k < 3; k++) { t.ic0[k] = (float)inv.m[0][k]; t.ic1[k] = (float)inv.m[1][k]; t.ic2[k] = (float)inv.m[2][k]; t.c[k] = in.c3[k]; }
+    t.tri_base = in.tri_global_base; t.mesh = in.mesh; t._pad[0] = t._pad[1] = 0;
+  }
+  return true;
+}
+
+// What flattening costs per triangle: TriRec + nodes + ShadeRec + the builder's scratch at its peak.  Worst case: no triangle finds a partner (a
+// soup, $PTAMD_NO_PAIRS) — one 64-byte slot and TWO 32-byte shade records (entry 2 * slot + half; the B entries unused) per triangle, 32 B more
+// than a paired mesh
+constexpr uint64_t kFlatBytesPerTri = 292;
+struct AccelChoice { bool two_level, automatic; };  // automatic: two-level by PT_ACCEL_AUTO's own rule, not on request (pt_start_render says so on stderr)
+// One BVH over the flattened triangles (fewest node visits per ray) unless the scene repeats its meshes so often that the two-level
+// structure — TLAS over instances + one BLAS per mesh, small enough to sit in LDS — is the better trade (renderer_pt.cpp:653-749 always
+// builds the two-level one).  Every instance must be invertible for that.
+// Measured on C3 (1024 instances of a 1012-triangle mesh, MI355X): the two-level walk costs 1.75x the time of the one-BVH walk per ray
+// (same 17.7 node visits, plus the instance entries) while its structure is 65 KB instead of 82 MB and reads a fraction of the bytes.
+// Rays per second is what this renderer is for, so one BVH is the default and the two-level structure is chosen when flattening would not
+// leave room for the path queues: 8 or more instances per mesh on average, and the flat structure larger than half of `free_bytes`
+// (0: unknown, one BVH).  accel_structure (PT_ACCEL_*) pins the choice; `override_` ($PTAMD_TWO_LEVEL: 0 / 1, -1 = unset) forces it under PT_ACCEL_AUTO.
+inline AccelChoice choose_accel_structure(bool invertible, uint32_t tri_count, uint64_t unique_tris, uint64_t free_bytes,
+                                          uint32_t accel_structure, int override_) {
+  if (accel_structure == PT_ACCEL_ONE_BVH) return {false, false};
+  if (accel_structure == PT_ACCEL_TWO_LEVEL) return {invertible, false};
+  if (override_ >= 0) return {invertible && override_ != 0, false};
+  const bool two = invertible && (uint64_t)tri_count >= 8 * unique_tris && free_bytes != 0 && tri_count * kFlatBytesPerTri > free_bytes / 2;
+  return {two, two};
+}
+
+// The per-pixel leaf lists of the camera rays (camera_lists.hip) exist for a pinhole camera over the 6-wide one-BVH structure (with an inner
+// node for a root) of a full-frame, non-adaptive render.
+inline bool camera_lists_wanted(bool disabled, bool two_level, bool wide6, uint32_t root_ref, float aperture_radius, bool adaptive, bool region) {
+  return !disabled && !two_level && wide6 && root_ref != kInvalidRef && !(root_ref & kLeafBit) && !(aperture_radius > 0.0f) && !adaptive && !region;
+}
+// `cap` entries and a count per pixel slot, whole tiles
+inline uint64_t camera_list_bytes(uint32_t width, uint32_t height, uint32_t cap) {
+  return (uint64_t)tile_count(width, height) * 64 * ((uint64_t)cap * sizeof(CamListEntry) + sizeof(uint32_t));
+}
+// the bound: 1/16 of what is free, lists of a previous render included (the lists of a 1920x1080 frame reserve 2.1 GB, a 3840x2160 frame's
+// 8.5 GB; only the entries in use are ever touched); a render that cannot spare that traces its camera rays as before.  free_bytes 0: unknown.
+inline bool camera_lists_fit(uint64_t bytes, uint64_t free_bytes, uint64_t lists_held) {
+  return free_bytes != 0 && bytes <= (free_bytes + lists_held) / 16;
+}
+// What plan_queues may count on (0: unknown).  What the previous render's queues occupy is reused, i.e. available.  The camera-ray lists were
+// taken first; the queues are planned as if they had not been — a quarter of the free memory is the queues' budget, and a render sizes its
+// batches the same with and without lists.  AOVs add 32 B per path slot (Abuf) to the ~200 B of queue state the automatic choice assumes.
+inline uint64_t queue_budget(uint64_t free_bytes, uint64_t queues_held, uint64_t lists_held, bool aov, uint64_t abuf_held) {
+  if (free_bytes == 0) return 0;
+  const uint64_t b = free_bytes + queues_held + lists_held;
+  return aov ? (b + abuf_held) / 232 * 200 : b;
 }
 
 }  // namespace pt

@@ -20,7 +20,8 @@ struct Segments {
   uint32_t* shadow;     // [segment] shadow rays in the segment
   uint32_t* poison;     // [segment] != 0: a path of the segment carries a throughput that is not finite (k_shade's scan of the misses)
   WaveStats* stats;     // [nstats] per physical wave of the producer kernels
-  uint32_t* table_closest;  // dense lists of non-empty chunks, (k << 16) | segment, rebuilt by k_chunk_tables
+  uint32_t* table_closest;  // dense lists of non-empty chunks, chunk_entry(segment, k, rays) (kernels.hip: 16 bits of segment, 10 of k, 6 of rays - 1), rebuilt by k_chunk_tables;
+                            // 8 entries of padding behind capacity / 64: a trace wave loads a whole run of up to 8 chunks wherever the list ends
   uint32_t* table_shadow;
   uint32_t* shade_order;    // [nseg] the segments by falling size of the closest-hit queue: the order in which k_shade's waves claim them (k_chunk_tables)
   uint32_t* shade_cost;     // [bounce][nseg] 100 MHz ticks k_shade spent on the segment at that bounce in the PREVIOUS batch of this render (0: none yet)
@@ -97,10 +98,14 @@ struct LbvhResult {
   bool wide6 = false;         // nodes[] holds BvhNode6 records (pt_device.h)
 };
 // The builder's temporaries: ONE device allocation that is kept between builds and only ever grows (a hipFree is a device synchronisation
-// and took ~0.2 ms of a 2.2 ms build; C3 needs ~0.4 GB).  Owned by the renderer; release() gives the memory back.
+// and took ~0.2 ms of a 2.2 ms build; C3 needs ~0.4 GB).  Owned by the renderer and given back with it; release() may be called any number of times.
 struct LbvhScratch {
   char* base = nullptr;
   size_t cap = 0;
+  LbvhScratch() = default;
+  LbvhScratch(const LbvhScratch&) = delete;
+  LbvhScratch& operator=(const LbvhScratch&) = delete;
+  ~LbvhScratch() { release(); }
   hipError_t ensure(size_t bytes);
   void release();
 };

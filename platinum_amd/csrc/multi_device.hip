@@ -232,24 +232,6 @@ void group_destroy(pt_renderer* front) {
   delete front;
 }
 
-// what dev_start_render would reject, checked BEFORE the group's previous render is torn down (renderer.hip dev_start_render)
-int group_validate_params(const pt_scene_snapshot* scene, const pt_render_params* p) {
-  if (!scene || !p) return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: null argument");
-  if (p->spp == 0 || p->width == 0 || p->height == 0) return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: empty size or spp");
-  if (p->stream) return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: a caller stream cannot drive a device group (every member owns its stream)");
-  if (p->max_bounces < 1 || p->max_bounces > 50)
-    return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: max_bounces must be 1..50 (620 Halton dimensions, kernel.metal:5)");
-  if ((uint64_t)p->width * p->height > (1ull << 28)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: image too large");
-  if (p->integrator != PT_INTEGRATOR_SIMPLE && p->integrator != PT_INTEGRATOR_MIS) return fail(PT_ERR_INVALID_ARGUMENT, "bad integrator");
-  if (p->nonfinite_policy > PT_NONFINITE_ZERO) return fail(PT_ERR_INVALID_ARGUMENT, "bad nonfinite_policy");
-  if (p->accel_structure > PT_ACCEL_TWO_LEVEL) return fail(PT_ERR_INVALID_ARGUMENT, "bad accel_structure");
-  if ((p->flags & PT_FLAG_GMON) && (p->gmon_buckets < 1 || p->gmon_buckets > 32))
-    return fail(PT_ERR_INVALID_ARGUMENT, "gmon_buckets must be 1..32 (gmon.metal:12 maxBuckets)");
-  if (scene->instance_count && (!scene->instances || !scene->instance_materials || !scene->meshes))
-    return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: null scene arrays");
-  return PT_OK;
-}
-
 // a failed (re)start leaves the group with NO render: nothing a later pt_wait / pt_read_* could merge or present
 int group_abandon(DeviceGroup* grp, int rc) {
   const std::string why = pt_last_error_string();  // (release_images makes HIP calls; keep the first error's text)
@@ -263,8 +245,8 @@ int group_abandon(DeviceGroup* grp, int rc) {
 int group_start_render(pt_renderer* front, const pt_scene_snapshot* scene, const pt_render_params* p) {
   DeviceGroup* grp = front->group;
   {
-    const int rc = group_validate_params(scene, p);
-    if (rc != PT_OK) return rc;  // the previous render (if any) stays as it was
+    const int rc = validate_start_params(scene, p, /*own_streams=*/true);  // what dev_start_render would reject, BEFORE the previous render is torn down:
+    if (rc != PT_OK) return rc;                                            // it (if any) stays as it was
   }
   const size_t N = grp->shards.size();
   const bool gmon = (p->flags & PT_FLAG_GMON) != 0;

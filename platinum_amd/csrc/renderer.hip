@@ -52,6 +52,33 @@ struct ScopedTimer {  // records a pair of events around one launch when profili
   }
 };
 
+// Times a stretch of one stream with a pair of events: the first is recorded on construction (`started` tells whether that worked); stop() records
+// the second, waits for it and gives the milliseconds between.  The events go with the object, on every path out of its scope.
+struct EventStopwatch {
+  hipStream_t s;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  hipError_t started;
+  explicit EventStopwatch(hipStream_t s_) : s(s_) {
+    started = hipEventCreate(&e0);
+    if (started == hipSuccess) started = hipEventCreate(&e1);
+    if (started == hipSuccess) started = hipEventRecord(e0, s);
+  }
+  hipError_t stop(float* ms) {
+    hipError_t e = hipEventRecord(e1, s);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    if (e == hipSuccess) (void)hipEventElapsedTime(ms, e0, e1);
+    return e;
+  }
+  ~EventStopwatch() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+
+// Free device memory now; 0 when the runtime cannot tell.  Every budget of pt_start_render reads 0 as "unknown" and then credits nothing
+// (host_scene.h choose_accel_structure, camera_lists_fit, queue_budget).
+size_t free_device_bytes() {
+  size_t free_b = 0, total_b = 0;
+  return hipMemGetInfo(&free_b, &total_b) == hipSuccess ? free_b : 0;
+}
+
 enum BatchMode { BATCH_RENDER, BATCH_DEBUG, BATCH_MEASURE };
 
 // One batch: `ns` samples of every pixel, first sample index `first`, `n0` samples already in the accumulator.
@@ -313,7 +340,7 @@ void dev_destroy(pt_renderer* r) {
   (void)hipSetDevice(r->device);
   if (r->stream) (void)hipStreamSynchronize(r->stream);
   r->drop_timed();
-  r->release_all();  // the scene arrays, the queues AND the BVH builder's kept scratch (LbvhScratch has no destructor of its own)
+  r->free_scene();  // the acceleration structure is raw pointers; every device array and the BVH builder's kept scratch go with `delete r`
   if (r->batch_done) (void)hipEventDestroy(r->batch_done);
   if (r->ad_event) (void)hipEventDestroy(r->ad_event);
   if (r->ad_host_count) (void)hipHostFree(r->ad_host_count);
@@ -321,9 +348,11 @@ void dev_destroy(pt_renderer* r) {
   delete r;
 }
 
-int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_render_params* p) {
-  if (!r || !scene || !p) return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: null argument");
+int validate_start_params(const pt_scene_snapshot* scene, const pt_render_params* p, bool own_streams) {
+  if (!scene || !p) return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: null argument");
   if (p->width == 0 || p->height == 0 || p->spp == 0) return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: empty size or spp");
+  if (own_streams && p->stream)
+    return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: a caller stream cannot drive a device group (every member owns its stream)");
   if (p->max_bounces < 1 || p->max_bounces > 50)
     return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: max_bounces must be 1..50 (620 Halton dimensions, kernel.metal:5)");
   if ((uint64_t)p->width * p->height > (1ull << 28)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: image too large");
@@ -334,6 +363,21 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
     return fail(PT_ERR_INVALID_ARGUMENT, "gmon_buckets must be 1..32 (gmon.metal:12 maxBuckets)");
   if (scene->instance_count && (!scene->instances || !scene->instance_materials || !scene->meshes))
     return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: null scene arrays");
+  return PT_OK;
+}
+
+// ---- pt_start_render, phase by phase (dev_start_render below runs them in this order).  r->S, the HostScene and r->bvh carry the scene from
+//      one phase to the next; what a phase needs of the renderer's options (denoise, adaptive, region) it reads there. ----
+namespace {
+
+Rect render_rect(const pt_renderer* r, const pt_render_params* p) {
+  const pt_render_region& g = r->region_opts;
+  return g.enabled ? Rect{g.x0, g.y0, g.x1, g.y1} : Rect{0u, 0u, p->width, p->height};
+}
+
+// 1. the parameters, then what this renderer's options rule out
+int validate_start(const pt_renderer* r, const pt_scene_snapshot* scene, const pt_render_params* p) {
+  if (const int rc = validate_start_params(scene, p, /*own_streams=*/false)) return rc;
   if (r->adaptive_opts.enabled && (p->flags & PT_FLAG_GMON))
     return fail(PT_ERR_UNSUPPORTED, "pt_start_render: adaptive sampling does not support PT_FLAG_GMON (a bucket would have to be resolved per tile count)");
   if (r->region_opts.enabled) {
@@ -345,53 +389,39 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
     if (p->flags & PT_FLAG_GMON)
       return fail(PT_ERR_UNSUPPORTED, "pt_start_render: a render region does not support PT_FLAG_GMON (the GMoN kernels index the radiance buffer by image pixel)");
   }
-  PT_HIP(hipSetDevice(r->device));
-  if (r->stream) PT_HIP(hipStreamSynchronize(r->stream));
-  r->drop_timed();
-  r->free_scene();
-  r->params = *p;
-  r->stream = p->stream ? (hipStream_t)p->stream : r->own_stream;
-  const auto t_up0 = std::chrono::steady_clock::now();
-  const bool phase_log = getenv("PTAMD_START_PHASES") != nullptr;   // analysis aid: where a (re)start spends its wall time
-  auto phase = [&, t_last = std::chrono::steady_clock::now()](const char* what) mutable {
-    if (!phase_log) return;
-    (void)hipDeviceSynchronize();
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "ptamd start: %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
+  return PT_OK;
+}
 
-  // ---- flatten the snapshot, derive constants and the light table (host_scene.h) ----
-  HostScene hs;
-  {
-    std::string err;
-    const int rc = build_host_scene(scene, p, r->lut_w_E, r->lut_w_Eavg, &hs, &err);
-    if (rc != PT_OK) return fail(rc, err);
-  }
-  if (hs.tri_count >= (1u << 27)) return fail(PT_ERR_UNSUPPORTED, "more than 2^27 flattened triangles (the hit record keeps 28 bits for 2 * leaf slot + half)");
-  if (hs.instances.size() >= (1u << kSlotInstBits)) return fail(PT_ERR_UNSUPPORTED, "more than 2^26 instances (a leaf slot keeps 26 bits for the instance)");
-  phase("host flatten + light table");
-  r->instance_count = (uint32_t)hs.instances.size();
-  r->tri_count = hs.tri_count;
-  r->constants = hs.constants;
-  r->lights = hs.lights;
+// 2a. flatten the snapshot, derive constants and the light table (host_scene.h)
+int flatten_scene(pt_renderer* r, const pt_scene_snapshot* scene, const pt_render_params* p, HostScene* hs) {
+  std::string err;
+  const int rc = build_host_scene(scene, p, r->lut_w_E, r->lut_w_Eavg, hs, &err);
+  if (rc != PT_OK) return fail(rc, err);
+  if (hs->tri_count >= (1u << 27)) return fail(PT_ERR_UNSUPPORTED, "more than 2^27 flattened triangles (the hit record keeps 28 bits for 2 * leaf slot + half)");
+  if (hs->instances.size() >= (1u << kSlotInstBits)) return fail(PT_ERR_UNSUPPORTED, "more than 2^26 instances (a leaf slot keeps 26 bits for the instance)");
+  return PT_OK;
+}
+
+// 2b. upload it and fill r->S with everything but the acceleration structure and the records
+int upload_scene(pt_renderer* r, const pt_render_params* p, HostScene* hs) {
+  r->instance_count = (uint32_t)hs->instances.size();
+  r->tri_count = hs->tri_count;
+  r->constants = hs->constants;
+  r->lights = hs->lights;
   const pt_constants& C = r->constants;
-  const Mat3 idt = hs.idt;
-
-  // ---- upload ----
-  PT_HIP(r->positions.upload(hs.positions));
-  PT_HIP(r->vdata.upload(hs.vdata));
-  PT_HIP(r->indices.upload(hs.indices));
-  PT_HIP(r->slots.upload(hs.slots));
-  PT_HIP(r->meshes.upload(hs.meshes));
-  PT_HIP(r->instances.upload(hs.instances));
-  PT_HIP(r->materials.upload(hs.materials));
+  PT_HIP(r->positions.upload(hs->positions));
+  PT_HIP(r->vdata.upload(hs->vdata));
+  PT_HIP(r->indices.upload(hs->indices));
+  PT_HIP(r->slots.upload(hs->slots));
+  PT_HIP(r->meshes.upload(hs->meshes));
+  PT_HIP(r->instances.upload(hs->instances));
+  PT_HIP(r->materials.upload(hs->materials));
   PT_HIP(r->lights_d.upload(r->lights));
-  PT_HIP(r->tex_data.upload(hs.tex_data));
-  PT_HIP(r->tex_decode.upload(hs.tex_decode));
-  PT_HIP(r->textures.upload(hs.textures));
-  PT_HIP(r->env_alias_d.upload(hs.env_alias));
-  r->env_alias = std::move(hs.env_alias);
+  PT_HIP(r->tex_data.upload(hs->tex_data));
+  PT_HIP(r->tex_decode.upload(hs->tex_decode));
+  PT_HIP(r->textures.upload(hs->textures));
+  PT_HIP(r->env_alias_d.upload(hs->env_alias));
+  r->env_alias = std::move(hs->env_alias);
 
   DeviceScene& S = r->S;
   memset(&S, 0, sizeof(S));
@@ -400,12 +430,12 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   S.halton = r->halton.p;
   S.luts = r->luts;
   S.camera = C.camera;
-  S.idt = idt;
+  S.idt = hs->idt;
   S.width = p->width; S.height = p->height;
-  S.tex_data = r->tex_data.p; S.tex_decode = r->tex_decode.p; S.textures = r->textures.p; S.tex_native = hs.tex_native; S.env_alias = r->env_alias_d.p;
-  S.env_texture = hs.env_texture;
+  S.tex_data = r->tex_data.p; S.tex_decode = r->tex_decode.p; S.textures = r->textures.p; S.tex_native = hs->tex_native; S.env_alias = r->env_alias_d.p;
+  S.env_texture = hs->env_texture;
   S.envLightCount = C.envLightCount;
-  S.has_alpha = hs.has_alpha ? 1u : 0u;
+  S.has_alpha = hs->has_alpha ? 1u : 0u;
   S.lightCount = C.lightCount;
   S.totalLightPower = C.totalLightPower;
   S.flags = p->flags;
@@ -413,99 +443,68 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   S.max_bounces = p->max_bounces;
   S.tri_count = r->tri_count;
   S.root_ref = kInvalidRef;
-  phase("upload");
-  PT_HIP(hipDeviceSynchronize());
-  r->upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_up0).count();
+  return PT_OK;
+}
 
-  // ---- acceleration structure (replaces rebuildAccelerationStructures, renderer_pt.cpp:653-749) ----
-  {
-    struct EventPair {  // destroyed on every path out of this block
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } ev;
-    PT_HIP(hipEventCreate(&ev.e0));
-    PT_HIP(hipEventCreate(&ev.e1));
-    PT_HIP(hipEventRecord(ev.e0, r->stream));
-    // One BVH over the flattened triangles (fewest node visits per ray) unless the scene repeats its meshes so often that the
-    // two-level structure — TLAS over instances + one BLAS per mesh, small enough to sit in LDS — is the better trade
-    // (renderer_pt.cpp:653-749 always builds the two-level one).  Every instance must be invertible for that.
-    uint64_t unique_tris = 0;
-    for (const MeshInfo& m : hs.meshes) unique_tris += m.tri_count;
-    std::vector<InstanceTrav> itrav(hs.instances.size());
-    bool invertible = true;
-    for (size_t i = 0; i < hs.instances.size(); i++) {
-      const InstanceInfo& in = hs.instances[i];
-      M3d m{};
-      for (int k = 0; k < 3; k++) { m.m[0][k] = in.c0[k]; m.m[1][k] = in.c1[k]; m.m[2][k] = in.c2[k]; }
-      const double det = m.m[0][0] * (m.m[1][1] * m.m[2][2] - m.m[2][1] * m.m[1][2]) - m.m[1][0] * (m.m[0][1] * m.m[2][2] - m.m[2][1] * m.m[0][2]) +
-                         m.m[2][0] * (m.m[0][1] * m.m[1][2] - m.m[1][1] * m.m[0][2]);
-      double scale = 0;
-      for (int c = 0; c < 3; c++) for (int k = 0; k < 3; k++) scale = std::max(scale, std::fabs(m.m[c][k]));
-      if (!(std::fabs(det) > 1e-12 * scale * scale * scale) || !std::isfinite(det)) { invertible = false; break; }
-      const M3d inv = m3_inv(m);
-      InstanceTrav& t = itrav[i];
-      for (int k = 0; k < 3; k++) { t.ic0[k] = (float)inv.m[0][k]; t.ic1[k] = (float)inv.m[1][k]; t.ic2[k] = (float)inv.m[2][k]; t.c[k] = in.c3[k]; }
-      t.tri_base = in.tri_global_base; t.mesh = in.mesh; t._pad[0] = t._pad[1] = 0;
-    }
-    // Measured on C3 (1024 instances of a 1012-triangle mesh, MI355X): the two-level walk costs 1.75x the time of the one-BVH
-    // walk per ray (same 17.7 node visits, plus the instance entries) while its structure is 65 KB instead of 82 MB and reads
-    // a fraction of the bytes.  Rays per second is what this renderer is for, so one BVH is the default and the two-level
-    // structure is chosen when flattening would not leave room for the path queues (or on request, $PTAMD_TWO_LEVEL=1).
-    {
-      size_t free_b = 0, total_b = 0;
-      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-      // TriRec + nodes + ShadeRec + the builder's scratch at its peak.  Worst case: no triangle finds a partner (a soup, $PTAMD_NO_PAIRS) — one 64-byte
-      // slot and TWO 32-byte shade records (entry 2 * slot + half; the B entries unused) per triangle, 32 B more than a paired mesh
-      const uint64_t flat_bytes = (uint64_t)r->tri_count * 292ull;
-      r->two_level = invertible && (uint64_t)r->tri_count >= 8 * unique_tris && free_b != 0 && flat_bytes > free_b / 2;
-      // The switch is not silent: the two structures agree bit for bit except where fp32 Moeller-Trumbore reports a FALSE hit that
-      // lies outside an instance's tighter object-space boxes (fuzz seed 310601: one pixel-sample in ~1 500 scenes).
-      if (r->two_level && p->accel_structure == PT_ACCEL_AUTO && r->two_level_override < 0 && !getenv("PTAMD_QUIET"))
-        fprintf(stderr, "ptamd: PT_ACCEL_AUTO chose the TWO-LEVEL structure (flattening %u triangles would take %.1f GB of the %.1f GB free): 1.75x the "
-                        "traversal time of one BVH, and closest hits can differ from it where fp32 Moeller-Trumbore accepts a triangle the ray passes "
-                        "outside of (the seed-310601 class: ~1 pixel-sample per 1 500 scenes); PT_ACCEL_ONE_BVH / PT_ACCEL_TWO_LEVEL pin the choice\n",
-                r->tri_count, (double)flat_bytes / 1e9, (double)free_b / 1e9);
-    }
-    if (p->accel_structure == PT_ACCEL_ONE_BVH) r->two_level = false;
-    else if (p->accel_structure == PT_ACCEL_TWO_LEVEL) r->two_level = invertible;
-    else if (r->two_level_override >= 0) r->two_level = invertible && r->two_level_override != 0;
-    hipError_t be;
-    if (r->two_level) {
-      PT_HIP(r->inst_trav.upload(itrav));
-      be = build_two_level(r->stream, S, hs.meshes.data(), (uint32_t)hs.meshes.size(), r->instance_count, r->tri_count,
-                           (uint32_t)(kLdsStack + kSpillStack), &r->bvh_scratch, &r->bvh);
-    } else {
-      // leaf slots: two consecutive triangles of a mesh that share an edge go into ONE slot ($PTAMD_NO_PAIRS: one triangle per slot, as r3 had it)
-      build_primitives(&hs, getenv("PTAMD_NO_PAIRS") == nullptr);
-      PT_HIP(r->prim_tri_d.upload(hs.prim_tri));
-      PT_HIP(r->mesh_prim_base_d.upload(hs.mesh_prim_base));
-      PT_HIP(r->inst_prim_base_d.upload(hs.inst_prim_base));
-      PrimTables prims;
-      prims.prim_tri = r->prim_tri_d.p; prims.mesh_prim_base = r->mesh_prim_base_d.p; prims.inst_prim_base = r->inst_prim_base_d.p;
-      prims.slot_count = hs.prim_count;
-      be = build_lbvh(r->stream, S, prims, r->instance_count, (uint32_t)(kLdsStack + kSpillStack), &r->bvh_scratch, &r->bvh);
-    }
-    if (be != hipSuccess)
-      return fail(be == hipErrorOutOfMemory ? PT_ERR_OUT_OF_MEMORY : PT_ERR_HIP, std::string("LBVH build failed: ") + hipGetErrorString(be));
-    PT_HIP(hipEventRecord(ev.e1, r->stream));
-    PT_HIP(hipEventSynchronize(ev.e1));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ev.e0, ev.e1);
-    r->bvh_ms = ms;
-    // traversal stack: <= 3 pushes per 4-wide level; 4-wide depth = ceil(binary depth / 2)
-    if (r->bvh.depth4 * (r->bvh.wide6 ? 5u : 3u) + (r->two_level ? 1 : 0) > (uint32_t)(kLdsStack + kSpillStack))
-      return fail(PT_ERR_UNSUPPORTED, "BVH too deep for the traversal stack (degenerate geometry: thousands of coincident triangles?)");
-    S.nodes = r->bvh.nodes;
-    S.tris = r->bvh.tris;
-    S.slot_count = r->slot_count = r->bvh.slot_count;
-    S.root_ref = r->bvh.root_ref;
-    S.node_count = r->bvh.node_count;
-    S.two_level = r->two_level ? 1u : 0u;
-    S.wide6 = r->bvh.wide6 ? 1u : 0u;
-    S.inst_trav = r->inst_trav.p;
-    S.mesh_trav = r->bvh.mesh_trav;
+// 3. the acceleration structure (replaces rebuildAccelerationStructures, renderer_pt.cpp:653-749): which one (host_scene.h
+// choose_accel_structure), its build, and its place in r->S
+int build_accel(pt_renderer* r, const pt_render_params* p, HostScene* hs) {
+  DeviceScene& S = r->S;
+  EventStopwatch watch(r->stream);
+  PT_HIP(watch.started);
+  uint64_t unique_tris = 0;
+  for (const MeshInfo& m : hs->meshes) unique_tris += m.tri_count;
+  std::vector<InstanceTrav> itrav;
+  const bool invertible = instance_trav_records(hs->instances, &itrav);
+  const size_t free_b = free_device_bytes();
+  const AccelChoice choice = choose_accel_structure(invertible, r->tri_count, unique_tris, free_b, p->accel_structure, r->two_level_override);
+  r->two_level = choice.two_level;
+  // The switch is not silent: the two structures agree bit for bit except where fp32 Moeller-Trumbore reports a FALSE hit that
+  // lies outside an instance's tighter object-space boxes (fuzz seed 310601: one pixel-sample in ~1 500 scenes).
+  if (choice.automatic && !getenv("PTAMD_QUIET"))
+    fprintf(stderr, "ptamd: PT_ACCEL_AUTO chose the TWO-LEVEL structure (flattening %u triangles would take %.1f GB of the %.1f GB free): 1.75x the "
+                    "traversal time of one BVH, and closest hits can differ from it where fp32 Moeller-Trumbore accepts a triangle the ray passes "
+                    "outside of (the seed-310601 class: ~1 pixel-sample per 1 500 scenes); PT_ACCEL_ONE_BVH / PT_ACCEL_TWO_LEVEL pin the choice\n",
+            r->tri_count, (double)(r->tri_count * kFlatBytesPerTri) / 1e9, (double)free_b / 1e9);
+  hipError_t be;
+  if (r->two_level) {
+    PT_HIP(r->inst_trav.upload(itrav));
+    be = build_two_level(r->stream, S, hs->meshes.data(), (uint32_t)hs->meshes.size(), r->instance_count, r->tri_count,
+                         (uint32_t)(kLdsStack + kSpillStack), &r->bvh_scratch, &r->bvh);
+  } else {
+    // leaf slots: two consecutive triangles of a mesh that share an edge go into ONE slot ($PTAMD_NO_PAIRS: one triangle per slot, as r3 had it)
+    build_primitives(hs, getenv("PTAMD_NO_PAIRS") == nullptr);
+    PT_HIP(r->prim_tri_d.upload(hs->prim_tri));
+    PT_HIP(r->mesh_prim_base_d.upload(hs->mesh_prim_base));
+    PT_HIP(r->inst_prim_base_d.upload(hs->inst_prim_base));
+    PrimTables prims;
+    prims.prim_tri = r->prim_tri_d.p; prims.mesh_prim_base = r->mesh_prim_base_d.p; prims.inst_prim_base = r->inst_prim_base_d.p;
+    prims.slot_count = hs->prim_count;
+    be = build_lbvh(r->stream, S, prims, r->instance_count, (uint32_t)(kLdsStack + kSpillStack), &r->bvh_scratch, &r->bvh);
   }
-  phase("acceleration structure");
+  if (be != hipSuccess)
+    return fail(be == hipErrorOutOfMemory ? PT_ERR_OUT_OF_MEMORY : PT_ERR_HIP, std::string("LBVH build failed: ") + hipGetErrorString(be));
+  float ms = 0;
+  PT_HIP(watch.stop(&ms));
+  r->bvh_ms = ms;
+  // traversal stack: <= 3 pushes per 4-wide level; 4-wide depth = ceil(binary depth / 2)
+  if (r->bvh.depth4 * (r->bvh.wide6 ? 5u : 3u) + (r->two_level ? 1 : 0) > (uint32_t)(kLdsStack + kSpillStack))
+    return fail(PT_ERR_UNSUPPORTED, "BVH too deep for the traversal stack (degenerate geometry: thousands of coincident triangles?)");
+  S.nodes = r->bvh.nodes;
+  S.tris = r->bvh.tris;
+  S.slot_count = r->slot_count = r->bvh.slot_count;
+  S.root_ref = r->bvh.root_ref;
+  S.node_count = r->bvh.node_count;
+  S.two_level = r->two_level ? 1u : 0u;
+  S.wide6 = r->bvh.wide6 ? 1u : 0u;
+  S.inst_trav = r->inst_trav.p;
+  S.mesh_trav = r->bvh.mesh_trav;
+  return PT_OK;
+}
+
+// 4. the shade and light records, then the device copy of r->S, which is complete with them
+int build_records(pt_renderer* r) {
+  DeviceScene& S = r->S;
   PT_HIP(r->shade_recs.alloc(std::max<size_t>(1, 2 * (size_t)r->slot_count)));  // entry 2 * slot + half
   S.shade_recs = r->shade_recs.p;
   launch_shade_records(r->stream, S, r->shade_recs.p);
@@ -515,58 +514,50 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   S.light_cdf = r->light_cdf.p;
   launch_light_records(r->stream, S, r->light_recs.p, r->light_cdf.p);
   PT_HIP(r->scene_d.upload(std::vector<DeviceScene>(1, S)));  // k_shade reads the table from memory (scalar loads)
+  return PT_OK;
+}
 
-  phase("shade / light records");
-
-  // ---- per-pixel leaf lists of the camera rays (camera_lists.hip): taken BEFORE the queues are planned, and bounded ----
-  {
-    r->cam_stats = pt_camera_list_stats{};
-    const bool want = !r->no_camera_lists && !r->two_level && r->bvh.wide6 && S.root_ref != kInvalidRef && !(S.root_ref & kLeafBit) &&
-                      !(S.camera.apertureRadius > 0.0f) && !r->adaptive_opts.enabled && !r->region_opts.enabled;
-    const uint32_t cap = r->cam_cap_override ? r->cam_cap_override : kCamListCapacity;
-    const size_t slots = (size_t)tile_count(p->width, p->height) * 64;
-    const size_t bytes = slots * ((size_t)cap * sizeof(CamListEntry) + sizeof(uint32_t));
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-    free_b += r->cam_entries.bytes_held() + r->cam_count.bytes_held();
-    // the bound: 1/16 of what is free (the lists of a 1920x1080 frame reserve 2.1 GB, a 3840x2160 frame's 8.5 GB; only the entries in use are
-    // ever touched); a render that cannot spare that traces its camera rays as before
-    if (want && bytes <= free_b / 16) {
-      PT_HIP(r->cam_entries.alloc(slots * cap));
-      PT_HIP(r->cam_count.alloc(slots));
-      PT_HIP(r->cam_counters.alloc(1));
-      PT_HIP(hipMemsetAsync(r->cam_counters.p, 0, sizeof(CamListCounters), r->stream));
-      struct EventPair {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-      } ev;
-      PT_HIP(hipEventCreate(&ev.e0));
-      PT_HIP(hipEventCreate(&ev.e1));
-      PT_HIP(hipEventRecord(ev.e0, r->stream));
-      launch_camera_lists(r->stream, S, r->cam_entries.p, r->cam_count.p, cap, r->cam_counters.p);
-      PT_HIP(hipEventRecord(ev.e1, r->stream));
-      PT_HIP(hipEventSynchronize(ev.e1));
-      PT_HIP(hipGetLastError());
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, ev.e0, ev.e1);
-      CamListCounters c{};
-      PT_HIP(hipMemcpy(&c, r->cam_counters.p, sizeof(c), hipMemcpyDeviceToHost));
-      r->cam_cap = cap;
-      r->cam_lists = true;
-      r->cam_stats.built = 1u;
-      r->cam_stats.capacity = cap;
-      r->cam_stats.pixels_listed = c.listed;
-      r->cam_stats.pixels_walk = c.walk;
-      r->cam_stats.entries = c.entries;
-      r->cam_stats.build_ms = ms;
-      for (uint32_t k = 0; k < kCamHistBins; k++) r->cam_stats.length_histogram[k] = c.hist[k];
-    } else {
-      r->release_camera_lists();
-    }
+// 5. the per-pixel leaf lists of the camera rays (camera_lists.hip): taken BEFORE the queues are planned, and bounded (host_scene.h
+// camera_lists_fit); a render that does not get them gives back those of the previous one
+int build_camera_lists(pt_renderer* r, const pt_render_params* p) {
+  const DeviceScene& S = r->S;
+  r->cam_stats = pt_camera_list_stats{};
+  const bool want = camera_lists_wanted(r->no_camera_lists, r->two_level, r->bvh.wide6, S.root_ref, S.camera.apertureRadius,
+                                        r->adaptive_opts.enabled != 0, r->region_opts.enabled != 0);
+  const uint32_t cap = r->cam_cap_override ? r->cam_cap_override : kCamListCapacity;
+  const size_t slots = (size_t)tile_count(p->width, p->height) * 64;
+  const size_t free_b = free_device_bytes();
+  if (!want || !camera_lists_fit(camera_list_bytes(p->width, p->height, cap), free_b, r->cam_entries.bytes_held() + r->cam_count.bytes_held())) {
+    r->release_camera_lists();
+    return PT_OK;
   }
-  phase("camera lists");
+  PT_HIP(r->cam_entries.alloc(slots * cap));
+  PT_HIP(r->cam_count.alloc(slots));
+  PT_HIP(r->cam_counters.alloc(1));
+  PT_HIP(hipMemsetAsync(r->cam_counters.p, 0, sizeof(CamListCounters), r->stream));
+  EventStopwatch watch(r->stream);
+  PT_HIP(watch.started);
+  launch_camera_lists(r->stream, S, r->cam_entries.p, r->cam_count.p, cap, r->cam_counters.p);
+  float ms = 0;
+  PT_HIP(watch.stop(&ms));
+  PT_HIP(hipGetLastError());
+  CamListCounters c{};
+  PT_HIP(hipMemcpy(&c, r->cam_counters.p, sizeof(c), hipMemcpyDeviceToHost));
+  r->cam_cap = cap;
+  r->cam_lists = true;
+  r->cam_stats.built = 1u;
+  r->cam_stats.capacity = cap;
+  r->cam_stats.pixels_listed = c.listed;
+  r->cam_stats.pixels_walk = c.walk;
+  r->cam_stats.entries = c.entries;
+  r->cam_stats.build_ms = ms;
+  for (uint32_t k = 0; k < kCamHistBins; k++) r->cam_stats.length_histogram[k] = c.hist[k];
+  return PT_OK;
+}
 
-  // ---- wavefront buffers ----
+// 6. the wavefront buffers: the queue plan for the memory at hand (host_scene.h queue_budget, queue_plan.h), the grids, and every array a batch
+// of this render touches
+int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
   const uint64_t npix = (uint64_t)p->width * p->height;
   const bool aov = r->denoise.enabled != 0;
   if (!aov) { r->Abuf.release(); r->aov_img.release(); }  // (an AOV-off render holds nothing more than before)
@@ -574,25 +565,16 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   const bool region = r->region_opts.enabled != 0;
   if (!adaptive) r->release_checkpoints();                  // (nor does an adaptive-off render;
   if (!adaptive && !region) r->release_adaptive();          //  a region render keeps the tile lists and counts, which both use)
-  const Rect rect = region ? Rect{r->region_opts.x0, r->region_opts.y0, r->region_opts.x1, r->region_opts.y1} : Rect{0u, 0u, p->width, p->height};
   // Queue segments (kernels.hip): one per 8x8 tile (a few tiles each once the image has more than 32640 of them), each with
   // room for its tiles under all samples in flight; queue_plan.h holds the sizing and every index-width limit.  The producers
   // (raygen, shade) are persistent grids whose waves take segments round-robin; the trace kernels claim chunks from a table,
   // so every grid is sized for its own kernel's occupancy.
   {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-    else free_b += r->queue_bytes_held();  // what the previous render's queues occupy is reused, i.e. available
-    // (the camera-ray lists were taken first; the queues are planned as if they had not been — a quarter of the free memory is the queues' budget,
-    //  and a render sizes its batches the same with and without lists)
-    if (free_b) free_b += r->cam_entries.bytes_held() + r->cam_count.bytes_held();
-    if (aov && free_b) {  // AOVs add 32 B per path slot to the ~200 B of queue state the automatic choice assumes
-      free_b += r->Abuf.bytes_held();
-      free_b = free_b / 232 * 200;
-    }
+    const uint64_t budget = queue_budget(free_device_bytes(), r->queue_bytes_held(), r->cam_entries.bytes_held() + r->cam_count.bytes_held(), aov,
+                                         r->Abuf.bytes_held());
     pt_queue_plan plan{};
     const char* why = "";
-    const int rc = plan_queues(p->width, p->height, p->spp, p->samples_in_flight, free_b, r->tiles_per_seg_override, r->seg_bands, &plan, &why);
+    const int rc = plan_queues(p->width, p->height, p->spp, p->samples_in_flight, budget, r->tiles_per_seg_override, r->seg_bands, &plan, &why);
     if (rc != PT_OK) return fail(rc, std::string("pt_start_render: ") + why);
     r->samples_in_flight = plan.samples_in_flight;
     r->tiles_per_seg = plan.tiles_per_seg;
@@ -643,6 +625,7 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
     PT_HIP(hipMemsetAsync(r->aov_img.p, 0, sizeof(vec4) * 3 * npix, r->stream));
   }
   if (adaptive || region) {  // every tile the rectangle touches starts active (the whole frame: [0, tiles)), ascending (adaptive.hip)
+    const Rect rect = render_rect(r, p);
     const uint32_t tiles = tile_count(p->width, p->height);
     std::vector<uint32_t> first(rect_tiles(rect, p->width, nullptr, 0));
     (void)rect_tiles(rect, p->width, first.data(), (uint32_t)first.size());
@@ -665,8 +648,11 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   }
   PT_HIP(hipMemsetAsync(r->totals.p, 0, sizeof(Totals), r->stream));
   PT_HIP(hipStreamSynchronize(r->stream));
+  return PT_OK;
+}
 
-  phase("queues + accumulator");
+// 7. nothing can fail any more: the render exists from here on
+void reset_progress(pt_renderer* r, const pt_render_params* p) {
   for (int k = 0; k < K_CLASSES; k++) { r->ms_class[k] = 0; r->launches[k] = 0; }
   r->accumulated = 0;
   r->launched = 0;
@@ -674,17 +660,56 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   r->last_batch_ns = 0;   // Lbuf holds nothing of THIS render yet
   r->batch_done_valid = false;
   r->total = p->spp;
-  r->aov = aov;
-  r->adaptive = adaptive;
-  r->region = region;
-  r->vtiles = adaptive || region;
-  r->rect = rect;
+  r->aov = r->denoise.enabled != 0;
+  r->adaptive = r->adaptive_opts.enabled != 0;
+  r->region = r->region_opts.enabled != 0;
+  r->vtiles = r->adaptive || r->region;
+  r->rect = render_rect(r, p);
   r->ad_cur = 0;
   r->ad_event_valid = false;
   r->ad_next = r->adaptive_opts.min_spp;   // the first checkpoint (none when min_spp >= spp)
   r->started = true;
   r->render_start = std::chrono::steady_clock::now();
   r->timer_ms = 0;
+}
+
+}  // namespace
+
+int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_render_params* p) {
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_start_render: null argument");
+  int rc = validate_start(r, scene, p);
+  if (rc != PT_OK) return rc;
+  PT_HIP(hipSetDevice(r->device));
+  if (r->stream) PT_HIP(hipStreamSynchronize(r->stream));
+  r->drop_timed();
+  r->free_scene();
+  r->params = *p;
+  r->stream = p->stream ? (hipStream_t)p->stream : r->own_stream;
+  const auto t_up0 = std::chrono::steady_clock::now();
+  const bool phase_log = getenv("PTAMD_START_PHASES") != nullptr;   // analysis aid: where a (re)start spends its wall time
+  auto phase = [&, t_last = std::chrono::steady_clock::now()](const char* what) mutable {
+    if (!phase_log) return;
+    (void)hipDeviceSynchronize();
+    const auto now = std::chrono::steady_clock::now();
+    fprintf(stderr, "ptamd start: %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
+    t_last = now;
+  };
+  HostScene hs;
+  if ((rc = flatten_scene(r, scene, p, &hs)) != PT_OK) return rc;
+  phase("host flatten + light table");
+  if ((rc = upload_scene(r, p, &hs)) != PT_OK) return rc;
+  phase("upload");
+  PT_HIP(hipDeviceSynchronize());
+  r->upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_up0).count();
+  if ((rc = build_accel(r, p, &hs)) != PT_OK) return rc;
+  phase("acceleration structure");
+  if ((rc = build_records(r)) != PT_OK) return rc;
+  phase("shade / light records");
+  if ((rc = build_camera_lists(r, p)) != PT_OK) return rc;
+  phase("camera lists");
+  if ((rc = allocate_buffers(r, p)) != PT_OK) return rc;
+  phase("queues + accumulator");
+  reset_progress(r, p);
   return PT_OK;
 }
 

@@ -107,7 +107,7 @@ struct pt_renderer {
   DevBuf<pt_alias_entry> env_alias_d;
   std::vector<pt_alias_entry> env_alias;
   LbvhResult bvh{};
-  LbvhScratch bvh_scratch{};  // the builder's temporaries, kept between builds (release_all gives them back)
+  LbvhScratch bvh_scratch{};  // the builder's temporaries, kept between builds
   DeviceScene S{};
   pt_render_params params{};
   pt_constants constants{};
@@ -206,7 +206,7 @@ struct pt_renderer {
   Segments segments() { return Segments{{seg_active[0].p, seg_active[1].p}, seg_shadow.p, seg_poison.p, wave_stats.p, chunk_table[0].p, chunk_table[1].p, shade_order.p, shade_cost.p, seg_cap, nseg, tiles_per_seg, /*nsamples: set per batch*/ 0u, seg_bands, nstats, refill_threshold}; }
 
   // A restart keeps every device array (they are re-filled, and only re-allocated when they must grow); what it drops is the
-  // acceleration structure of the previous scene and the "started" state.  release_all() returns the memory (pt_destroy).
+  // acceleration structure of the previous scene and the "started" state.  The arrays' destructors return the memory (pt_destroy).
   void free_scene() {
     if (bvh.nodes) (void)hipFree(bvh.nodes);
     if (bvh.tris) (void)hipFree(bvh.tris);
@@ -228,20 +228,6 @@ struct pt_renderer {
     for (int k = 0; k < 2; k++) b += st_rayO[k].bytes_held() + st_rayD[k].bytes_held() + st_att[k].bytes_held();
     return b;
   }
-  void release_all() {
-    free_scene();
-    positions.release(); vdata.release(); indices.release(); slots.release(); meshes.release(); instances.release();
-    materials.release(); lights_d.release(); tex_data.release(); tex_decode.release(); textures.release(); env_alias_d.release(); scene_d.release(); shade_recs.release(); light_recs.release(); light_cdf.release();
-    inst_trav.release(); prim_tri_d.release(); mesh_prim_base_d.release(); inst_prim_base_d.release();
-    bvh_scratch.release();
-    for (int k = 0; k < 2; k++) { st_rayO[k].release(); st_rayD[k].release(); st_att[k].release(); }
-    seg_active[0].release(); seg_active[1].release(); seg_shadow.release(); seg_poison.release(); wave_stats.release(); chunk_table[0].release(); chunk_table[1].release(); shade_order.release(); shade_cost.release(); gmon_buckets_d.release(); render_target.release();
-    hit.release(); sq_o.release(); sq_d.release(); sq_c.release(); Lbuf.release(); acc_own.release(); spill.release();
-    Abuf.release(); aov_img.release(); dn_guide.release(); dn_aux.release(); dn_col[0].release(); dn_col[1].release(); denoised.release();
-    exp_rec.release(); exp_img.release();
-    release_camera_lists(); cam_counters.release();
-    release_adaptive();
-  }
   void release_camera_lists() { cam_entries.release(); cam_count.release(); cam_lists = false; }
   void release_adaptive() {
     release_checkpoints();
@@ -260,6 +246,8 @@ struct pt_renderer {
 int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out);
 void dev_destroy(pt_renderer* r);
 int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_render_params* p);
+// what a start refuses for its parameters alone, a device group's (own_streams: a caller stream cannot drive it) and a single device's alike
+int validate_start_params(const pt_scene_snapshot* scene, const pt_render_params* p, bool own_streams);
 int dev_render_step(pt_renderer* r, uint32_t max_spp);
 int dev_wait(pt_renderer* r);
 int dev_status(const pt_renderer* r);
