@@ -131,9 +131,9 @@ typedef struct pt_camera {
   float sensor_size[2];     /* mm, default {36,24} */
   float focal_length;       /* mm */
   float aperture;           /* f-number, 0 = pinhole */
-  uint32_t aperture_blades;
+  uint32_t aperture_blades; /* sides of the aperture polygon (used when roundness < 1); fewer than 3 count as 3 */
   float roundness;
-  float bokeh_power;
+  float bokeh_power;        /* any float: the lens radius sqrt(u)^(2^bokeh_power) is 0 / 1 at the extremes, a NaN counts as 0 */
   float focus_distance;
 } pt_camera;
 
@@ -395,7 +395,7 @@ void* pt_accumulator_device_ptr(pt_renderer* r);
 typedef struct pt_denoise_options {
   uint32_t enabled;          /* accumulate AOVs for renders started from now on (read at pt_start_render) */
   uint32_t iterations;       /* 0..8, default 5; 0 = demodulate + remodulate only (the accumulator itself) */
-  float sigma_luminance, sigma_normal, sigma_depth;   /* 4, 128, 1: finite and > 0 */
+  float sigma_luminance, sigma_normal, sigma_depth;   /* 4, 128, 1: finite and > 0; a sigma_normal above 2^24 counts as 2^24 */
   uint32_t apply_to_target;  /* pt_read_render_target / pt_present_render_target post-process the denoised image (of a render
                                 started with AOVs; a render without them shows its accumulator as before) */
 } pt_denoise_options;
@@ -466,6 +466,31 @@ int pt_read_exposure_meter(pt_renderer* r, pt_exposure_meter* out);
  * with `options` and no smoothing state, and return the record and (scaled_out may be NULL) the scaled image.  Needs only pt_create. */
 int pt_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const uint32_t* rect,
                       const pt_exposure_options* options, pt_exposure_meter* out, float* scaled_out);
+
+/* ---- math probe (NEW, an additive extension of ABI 5: one entry point and one enum) ----
+ * Parity surface: the deterministic fp32 math, the sample warps and the Halton sequence of the kernels, evaluated on the device on their own.
+ * One elementwise launch on the renderer's stream computes function `fn` on n elements: a[i] (and b[i] for a function of two arguments) in,
+ * out0[i] (and out1[i] for a function of two results) out, upload and read-back inside the call.  Every array holds n 4-byte elements, float
+ * unless stated.  Needs only pt_create.
+ *   PT_MATH_SINCOS          sincos(a): out0 = sin, out1 = cos          PT_MATH_COS    cos(a)
+ *   PT_MATH_ATAN2           atan2(y = a, x = b)                         PT_MATH_ACOS   acos(a)
+ *   PT_MATH_LOG2 / EXP2     log2(a), exp2(a)                            PT_MATH_POWR   powr(x = a, y = b)
+ *   PT_MATH_PP_LOG2 / PP_EXP2 / PP_EXP2S / PP_POWR, PT_MATH_DN_EXP2 / DN_POWR: the range-guarded forms of the post-process and the denoiser
+ *   PT_MATH_SAMPLE_DISK, PT_MATH_SAMPLE_TRI_UNIFORM: u = (a, b) -> (out0, out1)
+ *   PT_MATH_SAMPLE_COSINE_HEMISPHERE: u = (a, b) -> x = out0[i], y = out1[i], z = out1[n + i]: out1 holds 2n floats for this function alone
+ *   PT_MATH_HALTON          halton(index = a, dimension = b), both uint32, b < 620, from the renderer's own table
+ *   PT_MATH_HALTON_OFFSET   the sample-stream offset of pixel (x = a & 0xffff, y = a >> 16) and sample b (a, b, out0: uint32)
+ *   PT_MATH_BOKEH_POWR      the thin-lens radius: lens sample u = a, bokehPower = b -> sqrt(u)^(2^b), defined for every float b
+ * The unguarded functions are evaluated as they stand: outside their domains the result is unspecified.
+ * PT_ERR_INVALID_ARGUMENT, before the renderer is looked at: fn >= PT_MATH_COUNT, n = 0 or n > 2^24, a null a or out0, a null b / out1 for a
+ * function that reads / writes it; then a null renderer. */
+enum {
+  PT_MATH_SINCOS = 0, PT_MATH_COS = 1, PT_MATH_ATAN2 = 2, PT_MATH_ACOS = 3, PT_MATH_LOG2 = 4, PT_MATH_EXP2 = 5, PT_MATH_POWR = 6,
+  PT_MATH_PP_LOG2 = 7, PT_MATH_PP_EXP2 = 8, PT_MATH_PP_EXP2S = 9, PT_MATH_PP_POWR = 10, PT_MATH_DN_EXP2 = 11, PT_MATH_DN_POWR = 12,
+  PT_MATH_SAMPLE_DISK = 13, PT_MATH_SAMPLE_COSINE_HEMISPHERE = 14, PT_MATH_SAMPLE_TRI_UNIFORM = 15,
+  PT_MATH_HALTON = 16, PT_MATH_HALTON_OFFSET = 17, PT_MATH_BOKEH_POWR = 18, PT_MATH_COUNT = 19
+};
+int pt_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const void* b, void* out0, void* out1);
 
 /* ---- tile-adaptive sampling (NEW, an additive extension of ABI 5: new entry points and one new struct, no existing struct changed) ----
  * A render started while `enabled` is set stops sampling an 8x8 tile of the accumulator once it has converged; pt_render_params.spp

@@ -149,4 +149,17 @@ static inline float powr_det(float x, float y) {
   return exp2_det(y * log2_det(x));
 }
 
+// Thin-lens radius x^(2^bokehPower), total over the floats: each exponential is +inf from 128 up, 0 below -127 (a NaN argument too),
+// exp2_det in between; a NaN bokehPower counts as 0 (exponent 1).  x in [0, 1).
+static inline float exp2_total(float y) {
+  if (y >= 128.0f) return INFINITY;
+  if (y >= -127.0f) return exp2_det(y);
+  return 0.0f;
+}
+static inline float bokeh_powr(float x, float bokehPower) {
+  if (x <= 0.0f) return 0.0f;
+  float e = std::isnan(bokehPower) ? 1.0f : exp2_total(bokehPower);
+  return exp2_total(e * log2_det(x));
+}
+
 }  // namespace orc

@@ -965,7 +965,7 @@ void update_constants(orc_scene& sc, const pt_camera& cam) {
   c.camera.pixelDeltaU = to_pt(vu / sizex);
   c.camera.pixelDeltaV = to_pt(vv / sizey);
   c.camera.apertureRadius = cam.aperture > 0.0f ? (cam.focal_length / 2000.0f) / cam.aperture : 0.0f;
-  c.camera.apertureBlades = cam.aperture_blades;
+  c.camera.apertureBlades = cam.aperture_blades < 3u ? 3u : cam.aperture_blades;  // ptamd.h pt_camera
   c.camera.apertureRoundness = cam.roundness;
   c.camera.bokehPower = cam.bokeh_power;
 }
@@ -1089,7 +1089,7 @@ Ray spawnRayFromCamera(const pt_camera_data& camera, uint32_t px, uint32_t py, f
   ray.origin = from_pt(camera.position);
   if (camera.apertureRadius > 0.0f) {
     float2 lensPos = sampleDiskPolar(lensSample);
-    lensPos.x = powr_det(lensPos.x, exp2_det(camera.bokehPower));
+    lensPos.x = bokeh_powr(lensPos.x, camera.bokehPower);
     if (camera.apertureRoundness < 1.0f) {
       float n = (float)camera.apertureBlades;
       float rPolygon = cos_det(PI_F / n) / cos_det(fmodf(lensPos.y + 1.5f * PI_F, 2.0f * PI_F / n) - PI_F / n);
@@ -1701,6 +1701,39 @@ void orc_sample_cosine_hemisphere(float u0, float u1, float out[3]) {
   float3 w = sampleCosineHemisphere({u0, u1}); out[0] = w.x; out[1] = w.y; out[2] = w.z;
 }
 void orc_sample_tri_uniform(float u0, float u1, float out[2]) { float2 b = sampleTriUniform({u0, u1}); out[0] = b.x; out[1] = b.y; }
+// The oracle's twin of pt_debug_math (include/ptamd.h): function fn (PT_MATH_*) on n elements, the same arguments and results.  The
+// guarded forms are the post-process's own (post_oracle.inc); the denoiser has no oracle, so its two guards are restated here from
+// exponents not above -125 (a NaN too) count as -125.
+void orc_math_batch(uint32_t fn, uint32_t n, const void* a_, const void* b_, void* out0_, void* out1_) {
+  const float* a = (const float*)a_; const float* b = (const float*)b_;
+  const uint32_t* ai = (const uint32_t*)a_; const uint32_t* bi = (const uint32_t*)b_;
+  float* o0 = (float*)out0_; float* o1 = (float*)out1_;
+  auto dn_exp2 = [](float y) { return exp2_det(y > -125.0f ? y : -125.0f); };
+  for (uint32_t i = 0; i < n; i++) {
+    switch (fn) {
+      case PT_MATH_SINCOS: sincos_det(a[i], &o0[i], &o1[i]); break;
+      case PT_MATH_COS: o0[i] = cos_det(a[i]); break;
+      case PT_MATH_ATAN2: o0[i] = atan2_det(a[i], b[i]); break;
+      case PT_MATH_ACOS: o0[i] = acos_det(a[i]); break;
+      case PT_MATH_LOG2: o0[i] = log2_det(a[i]); break;
+      case PT_MATH_EXP2: o0[i] = exp2_det(a[i]); break;
+      case PT_MATH_POWR: o0[i] = powr_det(a[i], b[i]); break;
+      case PT_MATH_PP_LOG2: o0[i] = post::log2s(a[i]); break;
+      case PT_MATH_PP_EXP2: o0[i] = post::exp2g(a[i]); break;
+      case PT_MATH_PP_EXP2S: o0[i] = post::exp2s(a[i]); break;
+      case PT_MATH_PP_POWR: o0[i] = post::powrg(a[i], b[i]); break;
+      case PT_MATH_DN_EXP2: o0[i] = dn_exp2(a[i]); break;
+      case PT_MATH_DN_POWR: o0[i] = a[i] <= 0.0f ? 0.0f : dn_exp2(b[i] * log2_det(a[i])); break;
+      case PT_MATH_SAMPLE_DISK: { float2 p = sampleDisk({a[i], b[i]}); o0[i] = p.x; o1[i] = p.y; break; }
+      case PT_MATH_SAMPLE_COSINE_HEMISPHERE: { float3 w = sampleCosineHemisphere({a[i], b[i]}); o0[i] = w.x; o1[i] = w.y; o1[n + i] = w.z; break; }
+      case PT_MATH_SAMPLE_TRI_UNIFORM: { float2 p = sampleTriUniform({a[i], b[i]}); o0[i] = p.x; o1[i] = p.y; break; }
+      case PT_MATH_HALTON: o0[i] = HaltonSampler::halton(ai[i], bi[i]); break;
+      case PT_MATH_HALTON_OFFSET: ((uint32_t*)out0_)[i] = HaltonSampler(ai[i] & 0xffffu, ai[i] >> 16, bi[i]).m_offset; break;
+      case PT_MATH_BOKEH_POWR: o0[i] = bokeh_powr(sampleDiskPolar({a[i], 0.0f}).x, b[i]); break;  // spawnRayFromCamera
+      default: break;
+    }
+  }
+}
 // ---- LUT generator restatement (pins A7-A9 against reference-held data) -------------------------------------------------
 // The eight energy tables the renderer loads (resource/lut/*.exr -> platinum_amd/data/ggx_luts.bin) are Monte-Carlo integrals
 // of the reference's own lobes, produced by its tool /root/reference/src/frontend/windows/tools/shaders/ms_lut_gen.metal:

@@ -8,6 +8,10 @@ import ctypes as C
 import os
 
 PT_ABI_VERSION = 5
+# pt_debug_math's functions (include/ptamd.h PT_MATH_*)
+(PT_MATH_SINCOS, PT_MATH_COS, PT_MATH_ATAN2, PT_MATH_ACOS, PT_MATH_LOG2, PT_MATH_EXP2, PT_MATH_POWR, PT_MATH_PP_LOG2, PT_MATH_PP_EXP2,
+ PT_MATH_PP_EXP2S, PT_MATH_PP_POWR, PT_MATH_DN_EXP2, PT_MATH_DN_POWR, PT_MATH_SAMPLE_DISK, PT_MATH_SAMPLE_COSINE_HEMISPHERE,
+ PT_MATH_SAMPLE_TRI_UNIFORM, PT_MATH_HALTON, PT_MATH_HALTON_OFFSET, PT_MATH_BOKEH_POWR, PT_MATH_COUNT) = range(20)
 
 # renderer_pt.hpp:21-26
 STATUS_BLOCKED, STATUS_READY, STATUS_BUSY, STATUS_DONE = 0, 1, 4, 8
@@ -276,6 +280,7 @@ SYMBOLS = [
     ("pt_read_exposure_meter", C.c_int, [C.c_void_p, C.POINTER(ExposureMeter)]),
     ("pt_debug_exposure", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(ExposureOptions),
                                     C.POINTER(ExposureMeter), C.c_void_p]),
+    ("pt_debug_math", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pt_default_adaptive_options", None, [C.POINTER(AdaptiveOptions)]),
     ("pt_set_adaptive_options", C.c_int, [C.c_void_p, C.POINTER(AdaptiveOptions)]),
     ("pt_read_sample_counts", C.c_int, [C.c_void_p, C.c_void_p]),

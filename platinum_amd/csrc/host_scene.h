@@ -383,7 +383,7 @@ inline int build_host_scene(const pt_scene_snapshot* scene, const pt_render_para
     C.camera.pixelDeltaU = to_pt(vu / sx);
     C.camera.pixelDeltaV = to_pt(vv / sy);
     C.camera.apertureRadius = cam.aperture > 0.0f ? (cam.focal_length / 2000.0f) / cam.aperture : 0.0f;
-    C.camera.apertureBlades = cam.aperture_blades;
+    C.camera.apertureBlades = cam.aperture_blades < 3u ? 3u : cam.aperture_blades;  // (pt_camera: a polygon has three sides; pi / 0 leaves cos_det's domain)
     C.camera.apertureRoundness = cam.roundness;
     C.camera.bokehPower = cam.bokeh_power;
   }

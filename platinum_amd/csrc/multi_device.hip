@@ -744,6 +744,10 @@ int pt_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32_
   return dev_debug_exposure(is_group(r) ? r->group->shards[0] : r, rgba, width, height, rect, options, out, scaled_out);
 }
 
+int pt_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const void* b, void* out0, void* out1) {
+  return dev_debug_math(is_group(r) ? r->group->shards[0] : r, fn, n, a, b, out0, out1);
+}
+
 // Adaptive sampling is per device: a group would have to agree on each tile's verdict across its members, which is not implemented
 int pt_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o) {
   if (!is_group(r)) return dev_set_adaptive_options(r, o);

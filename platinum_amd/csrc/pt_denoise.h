@@ -53,9 +53,12 @@ struct DenoiseParams {
 constexpr float kDnAlbedoMin = 1e-3f;
 constexpr float kDnEps = 1e-6f;
 constexpr float kDnLog2e = 1.44269504088896340736f;
+constexpr float kDnSigmaNormalMax = 16777216.0f;  // 2^24: what a larger pt_denoise_options.sigma_normal counts as (see dn_exp2)
 
 // exp2_det builds 2^n from the exponent bits: valid down to n = -126.  Weights below 2^-125 are taken as 2^-125 (a NaN argument too),
-// so that a tap is never dropped by an underflow and the sum never sees a denormal.
+// so that a tap is never dropped by an underflow and the sum never sees a denormal.  There is no upper guard: a weight's exponent is
+// never positive, except sigma_n * log2(n . n') when the dot product of two unit normals rounds above 1 (by less than 2^-20), and the
+// host caps sigma_n at kDnSigmaNormalMax, which keeps that product below 24.
 PT_HD float dn_exp2(float y) { return exp2_det(y > -125.0f ? y : -125.0f); }
 PT_HD float dn_exp(float x) { return dn_exp2(x * kDnLog2e); }
 PT_HD float dn_powr(float x, float y) { return x <= 0.0f ? 0.0f : dn_exp2(y * log2_det(x)); }

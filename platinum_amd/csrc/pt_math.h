@@ -120,5 +120,15 @@ PT_HD float exp2_det(float y) {
   return p * u2f((uint32_t)(n + 127) << 23);
 }
 PT_HD float powr_det(float x, float y) { return x <= 0.0f ? 0.0f : exp2_det(y * log2_det(x)); }
+// The thin-lens radius x^(2^bokehPower) (kernel.metal:207) for ANY float bokehPower: both exponentials go through pt_post.h's pp_exp2
+// rule (+inf from 128 up, 0 below -127, exp2_det's own bits between), ordered so that a NaN argument gives 0 instead of reaching the
+// cast in exp2_det.  A NaN bokehPower counts as 0 (exponent 1: the uniform disk).  x = sqrt(u) lies in [0, 1): the radius is finite and
+// <= 1 whatever the exponent (an exponent of +inf gives 0, an exponent of 0 gives 1).
+PT_HD float bokeh_powr(float x, float bokehPower) {
+  auto guarded = [](float y) { return y >= 128.0f ? kInf : (y >= -127.0f ? exp2_det(y) : 0.0f); };
+  if (x <= 0.0f) return 0.0f;
+  const float e = bokehPower == bokehPower ? guarded(bokehPower) : 1.0f;
+  return guarded(e * log2_det(x));
+}
 
 }  // namespace pt

@@ -99,7 +99,7 @@ PT_HD RayGenOut stage_raygen(const DeviceScene& S, uint32_t px, uint32_t py, uin
   vec3 origin = ld3(cam.position);
   if (cam.apertureRadius > 0.0f) {  // kernel.metal:205-226
     vec2 lensPos = sampleDiskPolar(lensSample);
-    lensPos.x = powr_det(lensPos.x, exp2_det(cam.bokehPower));
+    lensPos.x = bokeh_powr(lensPos.x, cam.bokehPower);  // total over the floats (pt_math.h)
     if (cam.apertureRoundness < 1.0f) {
       const float n = (float)cam.apertureBlades;
       const float rPolygon = cos_det(kPi / n) / cos_det(fmodf(lensPos.y + 1.5f * kPi, 2.0f * kPi / n) - kPi / n);

@@ -946,7 +946,7 @@ int enqueue_denoise(pt_renderer* r) {
   }
   DenoiseParams P;
   P.W = r->S.width; P.H = r->S.height;
-  P.sigma_l = r->denoise.sigma_luminance; P.sigma_n = r->denoise.sigma_normal; P.sigma_z = r->denoise.sigma_depth;
+  P.sigma_l = r->denoise.sigma_luminance; P.sigma_n = fminf(r->denoise.sigma_normal, kDnSigmaNormalMax); P.sigma_z = r->denoise.sigma_depth;
   launch_denoise(r->stream, r->acc, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * npix, P.W, P.H, (uint32_t)r->launched, P,
                  r->denoise.iterations, r->dn_guide.p, r->dn_aux.p, r->dn_col[0].p, r->dn_col[1].p, r->denoised.p,
                  r->adaptive ? r->ad_tile_n.p : nullptr,   // an adaptive render: each pixel's own sample count
@@ -1083,6 +1083,29 @@ int dev_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32
   PT_HIP(hipStreamSynchronize(r->stream));
   PT_HIP(hipMemcpy(out, &rec.p->meter, sizeof(*out), hipMemcpyDeviceToHost));
   if (scaled_out) PT_HIP(hipMemcpy(scaled_out, scaled.p, sizeof(vec4) * npix, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+// one elementwise launch of math_probe.hip on uploaded arguments; the renderer's own state is untouched (the Halton table is read)
+int dev_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const void* b, void* out0, void* out1) {
+  if (fn >= PT_MATH_COUNT) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_math: unknown function");
+  if (n == 0 || n > (1u << 24)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_math: n must be 1..2^24");
+  const bool reads_b = math_probe_reads_b(fn), writes_1 = math_probe_writes_out1(fn);
+  if (!a || !out0 || (reads_b && !b) || (writes_1 && !out1)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_math: null argument");
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_math: null renderer");
+  PT_HIP(hipSetDevice(r->device));
+  const size_t n1 = fn == PT_MATH_SAMPLE_COSINE_HEMISPHERE ? 2 * (size_t)n : n;  // words of out1
+  DevBuf<uint32_t> da, db, d0, d1;
+  PT_HIP(da.alloc(n)); PT_HIP(d0.alloc(n));
+  if (reads_b) PT_HIP(db.alloc(n));
+  if (writes_1) PT_HIP(d1.alloc(n1));
+  PT_HIP(hipMemcpyAsync(da.p, a, sizeof(uint32_t) * n, hipMemcpyHostToDevice, r->stream));
+  if (reads_b) PT_HIP(hipMemcpyAsync(db.p, b, sizeof(uint32_t) * n, hipMemcpyHostToDevice, r->stream));
+  launch_math_probe(r->stream, fn, n, da.p, db.p, d0.p, d1.p, r->halton.p);
+  PT_HIP(hipGetLastError());
+  PT_HIP(hipStreamSynchronize(r->stream));
+  PT_HIP(hipMemcpy(out0, d0.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+  if (writes_1) PT_HIP(hipMemcpy(out1, d1.p, sizeof(uint32_t) * n1, hipMemcpyDeviceToHost));
   return PT_OK;
 }
 

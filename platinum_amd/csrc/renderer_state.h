@@ -13,6 +13,8 @@
 #include "camera_lists.h"
 #include "denoise.h"
 #include "exposure.h"
+#include "math_probe.h"
+#include "pt_math_probe.h"
 #include "kernels.h"
 #include "pt_bvh.h"
 
@@ -277,6 +279,7 @@ int dev_set_despeckle_options(pt_renderer* r, const pt_despeckle_options* o);
 int dev_set_exposure_options(pt_renderer* r, const pt_exposure_options* o);
 int dev_reset_exposure(pt_renderer* r);
 int dev_read_exposure_meter(pt_renderer* r, const vec4* acc_device, pt_exposure_meter* out);  // acc_device NULL = what dev_read_render_target shows
+int dev_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const void* b, void* out0, void* out1);
 int dev_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const uint32_t* rect, const pt_exposure_options* options,
                        pt_exposure_meter* out, float* scaled_out);
 int dev_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o);

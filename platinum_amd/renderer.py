@@ -229,6 +229,21 @@ class Renderer:
                                                          C.byref(m), None if out is None else out.ctypes.data))
         return m, out
 
+    def debugMath(self, fn, a, b=None):
+        """pt_debug_math: function abi.PT_MATH_* on the device, elementwise on the 4-byte arrays a (and b).  Returns (out0, out1) as uint32
+        words (view them as float32 where the function returns floats); out1 is None for a function of one result and holds 2n words for
+        PT_MATH_SAMPLE_COSINE_HEMISPHERE (y, then z)."""
+        a = np.ascontiguousarray(a)
+        b = None if b is None else np.ascontiguousarray(b)
+        assert a.dtype.itemsize == 4 and a.ndim == 1 and (b is None or (b.dtype.itemsize == 4 and b.shape == a.shape))
+        n = a.size
+        two = fn in (abi.PT_MATH_SINCOS, abi.PT_MATH_SAMPLE_DISK, abi.PT_MATH_SAMPLE_COSINE_HEMISPHERE, abi.PT_MATH_SAMPLE_TRI_UNIFORM)
+        out0 = np.empty(n, np.uint32)
+        out1 = np.empty(2 * n if fn == abi.PT_MATH_SAMPLE_COSINE_HEMISPHERE else n, np.uint32) if two else None
+        abi.check(self._lib, self._lib.pt_debug_math(self._h, fn, n, a.ctypes.data, None if b is None else b.ctypes.data, out0.ctypes.data,
+                                                     None if out1 is None else out1.ctypes.data))
+        return out0, out1
+
     # tile-adaptive sampling (include/ptamd.h, an additive extension of ABI 5): no reference counterpart
     def adaptiveOptions(self):
         """The options in effect (pt_default_adaptive_options until setAdaptiveOptions is called)."""

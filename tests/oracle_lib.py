@@ -86,6 +86,8 @@ def lib():
     L.orc_avg_dielectric_fresnel_fit.restype = C.c_float
     L.orc_avg_dielectric_fresnel_fit.argtypes = [C.c_float]
     L.orc_sincos.argtypes = [C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.orc_math_batch.restype = None
+    L.orc_math_batch.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.orc_log2.restype = C.c_float
     L.orc_log2.argtypes = [C.c_float]
     L.orc_exp2.restype = C.c_float
