@@ -467,6 +467,54 @@ int pt_read_exposure_meter(pt_renderer* r, pt_exposure_meter* out);
 int pt_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const uint32_t* rect,
                       const pt_exposure_options* options, pt_exposure_meter* out, float* scaled_out);
 
+/* ---- bloom: an energy-conserving glare pyramid ahead of the post-process (NEW, an additive extension of ABI 5: new entry points and two
+ * new structs, no existing struct changed) ----
+ * With `enabled` set, pt_read_render_target / pt_present_render_target scatter a fraction `intensity` of the light above `threshold` with a
+ * wide point-spread function and leave the rest in place:  out = in - intensity * bright(in) + intensity * (PSF * bright(in)).  It runs over
+ * the full frame on the renderer's stream, after the denoised-image selection and after auto exposure (so `threshold` is in the units of
+ * the auto-exposed image) and ahead of the post-process (pt_post_options.exposure acts after it).  fp32, no contraction, every sum in the
+ * order written here.
+ * Plan: level 0 is the frame; level l+1 is ((w_l + 1) / 2) x ((h_l + 1) / 2); L = min(levels, halvings until a level is 1 x 1).  A 1 x 1
+ * frame has L = 0 and keeps its bits.  The pyramid holds levels 1..L back to back, 16 bytes per texel.
+ * Bright pass b of a pixel rgb (alpha ignored): Y = (0.2126 r + 0.7152 g) + 0.0722 b.  b = 0 when !(|Y| <= 3e38), a channel is not finite
+ * or Y <= 0; otherwise s = min(max((Y - threshold) + knee, 0), 2 knee), soft = (s s) / (4 knee + 1e-6), w = max(soft, Y - threshold) / Y,
+ * b.c = min(max(rgb.c, 0) w, 2^64).  A NaN or infinite pixel scatters nothing.
+ * Down: D_0 = b; D_{l+1}(x, y) = sum over j = 0..3, then i = 0..3, from 0, of (k[j] k[i]) D_l(clamp(2x - 1 + i), clamp(2y - 1 + j)),
+ * k = (1, 3, 3, 1) / 8.
+ * Up: up(C)(x, y) with cx = x >> 1 takes (cx - 1, 1/4), (cx, 3/4) for even x and (cx, 3/4), (cx + 1, 1/4) for odd x, the same in y, indices
+ * clamped to the coarse level, summed as ((ya,xa) + (ya,xb)) + (yb,xa)) + (yb,xb) with weights wy wx.
+ * Combine: U_L = D_L; U_l = D_l + scatter * up(U_{l+1}) for l = L-1..1; norm = sum over k < L of scatter^k (fp32, running sum += running
+ * power from k = 0); B = up(U_1) / norm; out.c = in.c + intensity * (B.c - b.c); a channel that is not finite and alpha keep their bits.
+ * enabled = 0 allocates and launches nothing and gives the bits of a library without bloom.  pt_read_accumulator, pt_read_denoised, the
+ * AOVs and pt_read_exposure_meter never see it.  With a render region the zeros outside it receive scattered light; their alpha stays 0. */
+#define PT_BLOOM_MAX_LEVELS 12u
+typedef struct pt_bloom_options {
+  uint32_t enabled;     /* default 0; read at every pt_read_render_target / pt_present_render_target, no restart */
+  float intensity;      /* default 0.05; the scattered fraction, in [0, 1] */
+  float threshold;      /* default 0; luminance above which light scatters; finite, >= 0 */
+  float knee;           /* default 0; half-width of the soft transition around the threshold; finite, >= 0 */
+  float scatter;        /* default 1; weight of each coarser octave relative to the one below it, in (0, 1] */
+  uint32_t levels;      /* default 6; 1..PT_BLOOM_MAX_LEVELS */
+} pt_bloom_options;
+void pt_default_bloom_options(pt_bloom_options* o);
+/* PT_ERR_INVALID_ARGUMENT for options outside the ranges above (checked before the renderer) */
+int pt_set_bloom_options(pt_renderer* r, const pt_bloom_options* o);
+
+typedef struct pt_bloom_plan {
+  uint32_t levels;         /* L */
+  uint32_t total_texels;   /* texels of the levels 1..L */
+  uint32_t width[PT_BLOOM_MAX_LEVELS + 1], height[PT_BLOOM_MAX_LEVELS + 1];   /* [0] is the frame; entries past L are 0 */
+  uint32_t offset[PT_BLOOM_MAX_LEVELS + 1];                                    /* first texel of level l in the pyramid; [0] is 0 */
+} pt_bloom_plan;
+/* Pure host arithmetic (exported for tests, like pt_plan_queues).  PT_ERR_INVALID_ARGUMENT for an image outside 1..2^28 pixels or levels
+ * outside 1..PT_BLOOM_MAX_LEVELS. */
+int pt_plan_bloom(uint32_t width, uint32_t height, uint32_t levels, pt_bloom_plan* out);
+/* Parity surface: upload a host W*H RGBA32F image, run the same launches with `options` (whatever `enabled` says) and return the bloomed
+ * image and (pyramid_out may be NULL) U_1..U_L as pt_plan_bloom lays them out, total_texels x 4 floats (.w is 0).  Needs only pt_create.
+ * The image must hold 1..2^28 pixels. */
+int pt_debug_bloom(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const pt_bloom_options* options, float* out,
+                   float* pyramid_out);
+
 /* ---- math probe (NEW, an additive extension of ABI 5: one entry point and one enum) ----
  * Parity surface: the deterministic fp32 math, the sample warps and the Halton sequence of the kernels, evaluated on the device on their own.
  * One elementwise launch on the renderer's stream computes function `fn` on n elements: a[i] (and b[i] for a function of two arguments) in,

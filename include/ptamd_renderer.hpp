@@ -37,6 +37,9 @@
  *   (no counterpart)                                             pt_exposure_options& exposureOptions(), resetExposure(), readExposureMeter(): auto
  *                                                                exposure, a luminance-histogram meter ahead of the post-process (ptamd.h, ABI 5
  *                                                                extension); handed over whenever a target is asked for
+ *   (no counterpart)                                             pt_bloom_options& bloomOptions(): bloom, an energy-conserving glare pyramid ahead of
+ *                                                                the post-process (ptamd.h, ABI 5 extension); handed over whenever a target is
+ *                                                                asked for
  *   (no counterpart)                                             pt_adaptive_options& adaptiveOptions() / setAdaptiveOptions(...),
  *                                                                readbackSampleCounts(): tile-adaptive sampling (ptamd.h, ABI 5 extension);
  *                                                                handed over at startRender
@@ -221,6 +224,10 @@ public:
     return m_pt && m_started && out && check(pt_set_denoise_options(m_pt, &m_denoise)) && check(pt_set_despeckle_options(m_pt, &m_despeckle)) &&
            check(pt_set_exposure_options(m_pt, &m_autoExposure)) && check(pt_read_exposure_meter(m_pt, out));
   }
+  // Bloom (ptamd.h, an additive extension of ABI 5): with enabled set, presentRenderTarget / readbackRenderTarget scatter `intensity` of the
+  // light above `threshold` through a down/up image pyramid, after auto exposure and ahead of the post-process.  Edited in place like
+  // denoiseOptions(); read whenever a target is asked for, no restart needed.
+  [[nodiscard]] constexpr pt_bloom_options& bloomOptions() { return m_bloom; }
   // Tile-adaptive sampling (ptamd.h, an additive extension of ABI 5).  Edited in place like denoiseOptions(); read at startRender.
   [[nodiscard]] constexpr pt_adaptive_options& adaptiveOptions() { return m_adaptive; }
   void setAdaptiveOptions(const pt_adaptive_options& o) { m_adaptive = o; }
@@ -250,6 +257,7 @@ private:
     pt_default_denoise_options(&m_denoise);
     pt_default_despeckle_options(&m_despeckle);
     pt_default_exposure_options(&m_autoExposure);
+    pt_default_bloom_options(&m_bloom);
     pt_default_adaptive_options(&m_adaptive);
     pt_default_render_region(&m_region);
     std::vector<int32_t> ord(devices, devices + count);
@@ -275,7 +283,7 @@ private:
     postprocess::flatten(m_tonemap, m_outputSpace, &tonemap);
     return check(pt_set_gmon_options(m_pt, &m_gmonOptions)) && check(pt_set_post_options(m_pt, &post)) && check(pt_set_tonemap_options(m_pt, &tonemap)) &&
            check(pt_set_denoise_options(m_pt, &m_denoise)) && check(pt_set_despeckle_options(m_pt, &m_despeckle)) &&
-           check(pt_set_exposure_options(m_pt, &m_autoExposure));
+           check(pt_set_exposure_options(m_pt, &m_autoExposure)) && check(pt_set_bloom_options(m_pt, &m_bloom));
   }
 
   pt_renderer* m_pt = nullptr;
@@ -295,6 +303,7 @@ private:
   pt_denoise_options m_denoise{};
   pt_despeckle_options m_despeckle{};
   pt_exposure_options m_autoExposure{};
+  pt_bloom_options m_bloom{};
   pt_adaptive_options m_adaptive{};
   pt_render_region m_region{};
   mutable void* m_presentStream = nullptr;

@@ -198,6 +198,22 @@ class ExposureMeter(C.Structure):
                 ("mean_log2", C.c_float), ("target_ev", C.c_float), ("ev", C.c_float), ("gain", C.c_float)]
 
 
+class BloomOptions(C.Structure):
+    """pt_bloom_options: the glare pyramid ahead of the post-process (bloom)."""
+    _fields_ = [("enabled", C.c_uint32), ("intensity", C.c_float), ("threshold", C.c_float), ("knee", C.c_float), ("scatter", C.c_float),
+                ("levels", C.c_uint32)]
+
+
+BLOOM_MAX_LEVELS = 12
+
+
+class BloomPlan(C.Structure):
+    """pt_bloom_plan: the levels of the bloom pyramid ([0] is the frame) and where each starts in the pyramid buffer."""
+    _fields_ = [("levels", C.c_uint32), ("total_texels", C.c_uint32),
+                ("width", C.c_uint32 * (BLOOM_MAX_LEVELS + 1)), ("height", C.c_uint32 * (BLOOM_MAX_LEVELS + 1)),
+                ("offset", C.c_uint32 * (BLOOM_MAX_LEVELS + 1))]
+
+
 class AdaptiveOptions(C.Structure):
     _fields_ = [("enabled", C.c_uint32), ("threshold", C.c_float), ("min_spp", C.c_uint32), ("interval", C.c_uint32)]
 
@@ -281,6 +297,10 @@ SYMBOLS = [
     ("pt_debug_exposure", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(ExposureOptions),
                                     C.POINTER(ExposureMeter), C.c_void_p]),
     ("pt_debug_math", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pt_default_bloom_options", None, [C.POINTER(BloomOptions)]),
+    ("pt_set_bloom_options", C.c_int, [C.c_void_p, C.POINTER(BloomOptions)]),
+    ("pt_plan_bloom", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(BloomPlan)]),
+    ("pt_debug_bloom", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(BloomOptions), C.c_void_p, C.c_void_p]),
     ("pt_default_adaptive_options", None, [C.POINTER(AdaptiveOptions)]),
     ("pt_set_adaptive_options", C.c_int, [C.c_void_p, C.POINTER(AdaptiveOptions)]),
     ("pt_read_sample_counts", C.c_int, [C.c_void_p, C.c_void_p]),

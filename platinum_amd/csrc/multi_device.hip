@@ -748,6 +748,17 @@ int pt_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const 
   return dev_debug_math(is_group(r) ? r->group->shards[0] : r, fn, n, a, b, out0, out1);
 }
 
+// Bloom: as auto exposure, every member holds the options and the member that post-processes the merged image does the work.
+int pt_set_bloom_options(pt_renderer* r, const pt_bloom_options* o) {
+  if (!is_group(r)) return dev_set_bloom_options(r, o);
+  for (auto* m : r->group->shards) { int rc = dev_set_bloom_options(m, o); if (rc != PT_OK) return rc; }
+  return PT_OK;
+}
+
+int pt_debug_bloom(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const pt_bloom_options* options, float* out, float* pyramid_out) {
+  return dev_debug_bloom(is_group(r) ? r->group->shards[0] : r, rgba, width, height, options, out, pyramid_out);
+}
+
 // Adaptive sampling is per device: a group would have to agree on each tile's verdict across its members, which is not implemented
 int pt_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o) {
   if (!is_group(r)) return dev_set_adaptive_options(r, o);

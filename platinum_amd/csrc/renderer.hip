@@ -290,6 +290,7 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   pt_default_denoise_options(&r->denoise);
   pt_default_despeckle_options(&r->despeckle);
   pt_default_exposure_options(&r->exposure);
+  pt_default_bloom_options(&r->bloom);
   pt_default_adaptive_options(&r->adaptive_opts);
   pt_default_render_region(&r->region_opts);
   r->device = device_ordinal;
@@ -1109,6 +1110,63 @@ int dev_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const
   return PT_OK;
 }
 
+extern "C" void pt_default_bloom_options(pt_bloom_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->intensity = 0.05f;
+  o->scatter = 1.0f;
+  o->levels = 6u;
+}
+
+// (the options are checked before the renderer, as dev_set_exposure_options)
+int dev_set_bloom_options(pt_renderer* r, const pt_bloom_options* o) {
+  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (const char* why = bloom_options_error(*o)) return fail(PT_ERR_INVALID_ARGUMENT, std::string("pt_set_bloom_options: ") + why);
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_bloom_options: null renderer");
+  r->bloom = *o;
+  return PT_OK;
+}
+
+extern "C" int pt_plan_bloom(uint32_t width, uint32_t height, uint32_t levels, pt_bloom_plan* out) {
+  if (!out) return fail(PT_ERR_INVALID_ARGUMENT, "pt_plan_bloom: null argument");
+  if (width == 0 || height == 0 || (uint64_t)width * height > (1ull << 28)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_plan_bloom: the image must hold 1..2^28 pixels");
+  if (levels < 1u || levels > PT_BLOOM_MAX_LEVELS) return fail(PT_ERR_INVALID_ARGUMENT, "pt_plan_bloom: 1 <= levels <= 12 is required");
+  bloom_plan(width, height, levels, out);
+  return PT_OK;
+}
+
+// Bloom ahead of the post-process, enqueued on the renderer's stream: blooms the full frame *src into the scratch image and points *src
+// at it.  (*src is the accumulator, the denoised image, a group's merged image or the auto-exposed image, never bloom_img itself.)
+static int enqueue_bloom(pt_renderer* r, const vec4** src) {
+  pt_bloom_plan plan;
+  bloom_plan(r->S.width, r->S.height, r->bloom.levels, &plan);
+  PT_HIP(r->bloom_img.alloc((size_t)r->S.width * r->S.height));
+  PT_HIP(r->bloom_pyr.alloc(plan.total_texels ? plan.total_texels : 1u));
+  PT_HIP(launch_bloom(r->stream, *src, r->bloom_img.p, r->bloom_pyr.p, plan, r->bloom));
+  *src = r->bloom_img.p;
+  return PT_OK;
+}
+
+// the same launches on an uploaded image, with buffers of its own; the renderer's own state is untouched
+int dev_debug_bloom(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const pt_bloom_options* options, float* out, float* pyramid_out) {
+  if (!options || !rgba || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (const char* why = bloom_options_error(*options)) return fail(PT_ERR_INVALID_ARGUMENT, std::string("pt_debug_bloom: ") + why);
+  if (width == 0 || height == 0 || (uint64_t)width * height > (1ull << 28)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_bloom: the image must hold 1..2^28 pixels");
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_bloom: null renderer");
+  PT_HIP(hipSetDevice(r->device));
+  const size_t npix = (size_t)width * height;
+  pt_bloom_plan plan;
+  bloom_plan(width, height, options->levels, &plan);
+  DevBuf<vec4> img, bloomed, pyr;
+  PT_HIP(img.alloc(npix)); PT_HIP(bloomed.alloc(npix)); PT_HIP(pyr.alloc(plan.total_texels ? plan.total_texels : 1u));
+  PT_HIP(hipMemcpyAsync(img.p, rgba, sizeof(vec4) * npix, hipMemcpyHostToDevice, r->stream));
+  PT_HIP(launch_bloom(r->stream, img.p, bloomed.p, pyr.p, plan, *options));
+  PT_HIP(hipStreamSynchronize(r->stream));
+  PT_HIP(hipMemcpy(out, bloomed.p, sizeof(vec4) * npix, hipMemcpyDeviceToHost));
+  if (pyramid_out && plan.total_texels) PT_HIP(hipMemcpy(pyramid_out, pyr.p, sizeof(vec4) * plan.total_texels, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
 extern "C" void pt_default_adaptive_options(pt_adaptive_options* o) {
   if (!o) return;
   memset(o, 0, sizeof(*o));
@@ -1193,6 +1251,7 @@ int dev_postprocess_to_host(pt_renderer* r, const vec4* acc_device, uint8_t* rgb
   const Mat3 odt = compute_transform(r->params.working_space, r->tonemap.output_space);  // renderer_pt.cpp:190-191
   pc.odt = PPMat3{odt.c0, odt.c1, odt.c2};
   if (r->exposure.enabled) { const int rc = enqueue_exposure(r, &acc_device); if (rc != PT_OK) return rc; }
+  if (r->bloom.enabled) { const int rc = enqueue_bloom(r, &acc_device); if (rc != PT_OK) return rc; }
   launch_postprocess(r->stream, acc_device, r->render_target.p, r->S.width, r->S.height, pc);
   PT_HIP(hipGetLastError());
   PT_HIP(hipStreamSynchronize(r->stream));
@@ -1220,6 +1279,7 @@ int dev_present(pt_renderer* r, const vec4* acc_device, void** device_rgba8_out,
     src = r->denoised.p;
   }
   if (r->exposure.enabled) { const int rc = enqueue_exposure(r, &src); if (rc != PT_OK) return rc; }
+  if (r->bloom.enabled) { const int rc = enqueue_bloom(r, &src); if (rc != PT_OK) return rc; }
   launch_postprocess(r->stream, src, r->render_target.p, r->S.width, r->S.height, pc);
   PT_HIP(hipGetLastError());
   *device_rgba8_out = r->render_target.p;

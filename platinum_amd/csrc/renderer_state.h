@@ -10,6 +10,7 @@
 
 #include "host_scene.h"
 #include "adaptive.h"
+#include "bloom.h"
 #include "camera_lists.h"
 #include "denoise.h"
 #include "exposure.h"
@@ -140,6 +141,11 @@ struct pt_renderer {
   pt_exposure_options exposure{};
   DevBuf<ExposureRecord> exp_rec;   // [1] the meter record and the smoothing state
   DevBuf<vec4> exp_img;             // the frame * gain: what k_postprocess reads with exposure.enabled
+  // bloom (bloom.hip): nothing is allocated or launched until a target is read with bloom.enabled.  Both arrays are sized
+  // for the frame on use and outlive pt_start_render like the other arrays.
+  pt_bloom_options bloom{};
+  DevBuf<vec4> bloom_pyr;           // the levels 1..L of the pyramid, back to back (pt_plan_bloom)
+  DevBuf<vec4> bloom_img;           // the bloomed frame: what k_postprocess reads with bloom.enabled
   // tile-adaptive sampling (adaptive.hip): only a render started with adaptive_opts.enabled allocates or launches any of it
   pt_adaptive_options adaptive_opts{};
   bool adaptive = false;            // this render samples adaptively
@@ -282,6 +288,8 @@ int dev_read_exposure_meter(pt_renderer* r, const vec4* acc_device, pt_exposure_
 int dev_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const void* b, void* out0, void* out1);
 int dev_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const uint32_t* rect, const pt_exposure_options* options,
                        pt_exposure_meter* out, float* scaled_out);
+int dev_set_bloom_options(pt_renderer* r, const pt_bloom_options* o);
+int dev_debug_bloom(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const pt_bloom_options* options, float* out, float* pyramid_out);
 int dev_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o);
 int dev_read_sample_counts(pt_renderer* r, uint32_t* out);
 int dev_set_render_region(pt_renderer* r, const pt_render_region* o);

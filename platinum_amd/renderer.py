@@ -244,6 +244,41 @@ class Renderer:
                                                      None if out1 is None else out1.ctypes.data))
         return out0, out1
 
+    # bloom (include/ptamd.h, an additive extension of ABI 5): no reference counterpart
+    def bloomOptions(self):
+        """The options in effect (pt_default_bloom_options until setBloomOptions is called)."""
+        if getattr(self, "_bloom", None) is None:
+            self._bloom = abi.BloomOptions()
+            self._lib.pt_default_bloom_options(C.byref(self._bloom))
+        o = abi.BloomOptions()
+        C.memmove(C.byref(o), C.byref(self._bloom), C.sizeof(o))
+        return o
+
+    def setBloomOptions(self, o=None, **fields):
+        """Sets `o` (default: the current options) with `fields` overriding it, e.g. setBloomOptions(enabled=1, intensity=0.1).
+        The options take effect at the next readbackRenderTarget / presentRenderTarget; no restart is needed."""
+        o = self.bloomOptions() if o is None else o
+        for k, v in fields.items():
+            setattr(o, k, v)
+        abi.check(self._lib, self._lib.pt_set_bloom_options(self._h, C.byref(o)))
+        self._bloom = o
+
+    def debugBloom(self, rgba, options=None, pyramid=False):
+        """Bloom's launches on a host (H, W, 4) float32 image with `options` (default: the current ones; `enabled` is not looked at): the
+        bloomed image, or with pyramid=True (image, U_1..U_L as an (abi.BloomPlan.total_texels, 4) array laid out by pt_plan_bloom)."""
+        img = np.ascontiguousarray(rgba, dtype=np.float32)
+        h, w = img.shape[:2]
+        o = self.bloomOptions() if options is None else options
+        out = np.empty((h, w, 4), np.float32)
+        pyr = None
+        if pyramid:
+            plan = abi.BloomPlan()
+            abi.check(self._lib, self._lib.pt_plan_bloom(w, h, o.levels, C.byref(plan)))
+            pyr = np.zeros((plan.total_texels, 4), np.float32)
+        abi.check(self._lib, self._lib.pt_debug_bloom(self._h, img.ctypes.data, w, h, C.byref(o), out.ctypes.data,
+                                                      None if pyr is None or pyr.size == 0 else pyr.ctypes.data))
+        return (out, pyr) if pyramid else out
+
     # tile-adaptive sampling (include/ptamd.h, an additive extension of ABI 5): no reference counterpart
     def adaptiveOptions(self):
         """The options in effect (pt_default_adaptive_options until setAdaptiveOptions is called)."""

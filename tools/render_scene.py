@@ -8,6 +8,7 @@ tracing (GMoN optional), fused post-process + tonemap — to an 8-bit PNG.
     python tools/render_scene.py builtin:c5 out.png --size 960 540 --spp 32 --bounces 12
     python tools/render_scene.py builtin:c1 preview.png --size 640 640 --spp 1 --denoise --despeckle
     python tools/render_scene.py builtin:c5 out.png --size 960 540 --spp 32 --auto-exposure
+    python tools/render_scene.py builtin:c5 out.png --size 960 540 --spp 32 --auto-exposure --bloom 0.1
     python tools/render_scene.py builtin:c3 corner.png --size 1920 1080 --spp 4096 --region 1200,600,1500,800
 """
 import argparse, os, struct, sys, time, zlib
@@ -38,6 +39,8 @@ def main():
     ap.add_argument("--auto-exposure", type=float, nargs="?", const=-2.4739313, default=None, metavar="TARGET_LOG2",
                     help="meter the image's luminance histogram and bring its mean to 2^TARGET_LOG2 (default log2 0.18) ahead of the post-process; "
                          "--exposure acts on top as compensation")
+    ap.add_argument("--bloom", type=float, nargs="?", const=0.05, default=None, metavar="INTENSITY",
+                    help="scatter this fraction of the light (default 0.05) with a wide glare pyramid, after --auto-exposure and ahead of the post-process")
     ap.add_argument("--denoise", action="store_true", help="keep first-hit AOVs and write the image through the a-trous denoiser")
     ap.add_argument("--despeckle", type=float, nargs="?", const=2.0, default=None, metavar="T",
                     help="with --denoise: clamp a pixel brighter than T x its brightest 3x3 neighbour ahead of the filter (fireflies; default T = 2)")
@@ -79,6 +82,8 @@ def main():
         r.setDespeckleOptions(enabled=1, threshold=a.despeckle)
     if a.auto_exposure is not None:
         r.setExposureOptions(enabled=1, target_log2=a.auto_exposure)
+    if a.bloom is not None:
+        r.setBloomOptions(enabled=1, intensity=a.bloom)
     if a.adaptive is not None:
         if a.gmon > 1:
             ap.error("--adaptive does not combine with --gmon")
