@@ -58,6 +58,13 @@ void launch_trace_closest(hipStream_t s, uint32_t grid, const DeviceScene& S, Pa
 void launch_trace_camera(hipStream_t s, uint32_t grid, uint32_t grid_unlisted, const DeviceScene& S, PathState st, vec4* hit, Segments seg,
                          BatchCounters* ctr, uint32_t* spill, const CameraLists& cl, bool any_unlisted);
 uint32_t camera_blocks_per_cu();
+// launch_raygen + launch_chunk_tables(bounce 0) + launch_trace_camera of a full-frame render batch with lists, with the first and the last as ONE
+// kernel (k_camera_primary, `grid` blocks, primary_blocks_per_cu() per CU): the camera rays are generated and traced in registers, and every word
+// the two kernels leave in memory is written as they write it.  The caller runs the table pass behind it — unless the build flagged pixels
+// (any_unlisted): then the table pass and k_trace_closest_unlisted, which claims from that table, follow here.
+void launch_camera_primary(hipStream_t s, uint32_t grid, uint32_t grid_unlisted, const DeviceScene& S, PathState st, vec4* Lbuf, vec4* hit, Segments seg,
+                           BatchCounters* ctr, uint32_t first_sample, uint32_t nsamples, uint32_t* spill, const CameraLists& cl, bool any_unlisted);
+uint32_t primary_blocks_per_cu();
 // `grid` blocks of shade_block_threads() threads (a persistent grid: shade_blocks_per_cu() per CU keeps it resident)
 uint32_t shade_block_threads();
 uint32_t shade_blocks_per_cu();

@@ -521,28 +521,7 @@ k_trace_camera(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments seg
         if (S.has_alpha) ir = Halton{halton_table(S.halton), f2u(st.att[ray].w), f2u(d4.w) & kMetaDimMask}.sample1d();
         TravState ts;
         (void)trav_init(S, ts, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), 1e-3f, kInf, ir, TraversalStack{}, false, nullptr);   // (lists exist only over a tree whose root is a node)
-        const CamListEntry* __restrict__ list = cl.entries + (size_t)q * cl.cap;
-        // The addresses do not depend on the traversal: entry i + 1 is loaded one step ahead, and its node is fetched as soon as entry i's slab
-        // tests are done with the node registers — it arrives while entry i's triangles are tested.  (Holding two whole nodes cost 62 spilled
-        // registers at 8 waves per SIMD.)
-        const CamListEntry none{0u, kInf};
-        CamListEntry e = len ? list[0] : none;
-        uint32_t i = 0, m = 0, base_leaf = 0;   // m: the leaf children of the current entry still to be tested
-        for (;;) {
-          if (m == 0u) {
-            if (i >= len || e.dist > ts.best.t * kCamCullSlack) break;
-            const BvhNode6 n = nodes[e.ref >> 6];
-            m = node6_leaf_hits(n, ts, ts.best.t * kCamCullSlack) & e.ref & 63u;
-            base_leaf = n.base_leaf;
-            i++;
-            e = i < len ? list[i] : none;
-          } else {
-            const uint32_t r = (uint32_t)__builtin_ctz(m);
-            m &= m - 1u;
-            bool fin = false;
-            trav_leaf(S, ts, kLeafBit | (base_leaf + r), false, &fin, nullptr);
-          }
-        }
+        cam_trace_ray(S, ts, nodes, cl.entries + (size_t)q * cl.cap, len);   // (pt_camlist.h: shared with k_camera_primary and tests/emu)
         const RayHit& h = ts.best;
         hit[ray] = vec4{h.t, h.u, h.v, u2f(h.tri == kInvalidRef ? kInvalidRef : (h.tri | ((h.gid & 3u) << 28)))};
       }
@@ -557,6 +536,159 @@ __global__ void __launch_bounds__(kBlock, PT_CLOSEST_WAVES)
 k_trace_closest_unlisted(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments seg, BatchCounters* __restrict__ ctr, uint32_t* __restrict__ spill,
                          CameraLists cl) {
   trace_closest_body<false, false, true, true>(S, st, hit, seg, 0u, ctr, 0u, &ctr->work_closest[kUnlistedCursor], spill, nullptr, 0u, cl);
+}
+
+// ---- bounce 0 in one kernel: k_raygen + k_trace_camera for a full-frame render batch with lists --------------------------------------------
+// k_trace_camera needs no stack, no leaf queue and no LDS, and the wave that generates 64 samples of a pixel knows the pixel: it goes
+// straight to that pixel's list with the ray in registers.  What k_raygen leaves in memory (rayO, rayD, att, Lbuf, the segment's count and
+// poison flag, paths / closest of WaveStats) and what k_trace_camera leaves (hit[]) is written word for word, to the same slots: the ray is
+// never read back, and the state stores drain while the trace waits for its nodes.  k_chunk_tables still runs behind it (shade_order, and
+// the table k_trace_closest_unlisted claims from).
+//
+// Work units: a segment costs k_raygen the same everywhere, here its cost follows the list lengths.  A unit is PT_PRIMARY_UNIT consecutive wave
+// iterations of a segment, claimed from bounce 0's cursor (work_closest[0]: nothing else uses it in this path); where a unit's first ray lands
+// in the segment is a closed form (pt_layout.h camera_rays_before), so units need nothing from one another.  The unit that starts a segment
+// writes its count.
+//
+// One pixel per iteration: when the 64 rays of an iteration are samples of ONE pixel (always when the batch's sample count is a multiple of
+// 64), the list, its entries and their nodes are the same for all lanes; only best.t, the cull decision and the leaf masks are per lane.  The
+// wave then walks the list with a wave-uniform index (cam_trace_wave: entry, node and triangle records are fetched once per wave, from
+// addresses the compiler can prove uniform) and leaves when no lane's cull test passes.  Per lane the entries, the children and the
+// triangles come in cam_trace_list's order, so the bits are those of the per-lane loop, which iterations that straddle two pixels still take.
+#ifndef PT_PRIMARY_WAVES
+#define PT_PRIMARY_WAVES 6
+#endif
+#ifndef PT_PRIMARY_UNIT
+#define PT_PRIMARY_UNIT 16
+#endif
+#ifndef PT_PRIMARY_UNIFORM
+#define PT_PRIMARY_UNIFORM 1   // 0: every batch takes the per-lane instantiation (the A/B build of profiles/r08_fused_camera.md)
+#endif
+constexpr uint32_t kPrimaryUnit = PT_PRIMARY_UNIT;
+
+// (`on`: this lane holds a ray.  len, list and nodes are wave-uniform.)
+__device__ __forceinline__ void cam_trace_wave(const DeviceScene& S, TravState& ts, bool on, const BvhNode6* __restrict__ nodes,
+                                               const CamListEntry* __restrict__ list, uint32_t len) {
+  const CamListEntry none{0u, kInf};
+  // two entries ahead, one node ahead: entry i + 1 has arrived when entry i's slab tests free the node registers
+  CamListEntry e = len ? list[0] : none, e1 = len > 1u ? list[1] : none;
+  BvhNode6 n = nodes[e.ref >> 6];
+  for (uint32_t i = 0; i < len; i++) {
+    const CamListEntry e2 = i + 2u < len ? list[i + 2u] : none;
+    const float lim = ts.best.t * kCamCullSlack;
+    on = on && !(e.dist > lim);   // (dist rises and best.t falls along the list: a lane that has left stays out, as after cam_trace_list's break)
+    if (__ballot(on) == 0) break;
+    uint32_t m = 0;
+    if (on) m = node6_leaf_hits(n, ts, lim) & e.ref & 63u;
+    const uint32_t base_leaf = n.base_leaf;
+    n = nodes[e1.ref >> 6];
+    uint32_t any = 0;   // the children some lane still has to test: a wave-uniform mask
+#pragma unroll
+    for (uint32_t r = 0; r < 6u; r++) any |= __ballot((m >> r) & 1u) != 0 ? 1u << r : 0u;
+    while (any) {   // children in rising order for every lane, one wave-uniform leaf at a time
+      const uint32_t r = (uint32_t)__builtin_ctz(any);
+      any &= any - 1u;
+      bool fin = false;
+      if ((m >> r) & 1u) trav_leaf(S, ts, kLeafBit | (base_leaf + r), false, &fin, nullptr);
+    }
+    e = e1; e1 = e2;
+  }
+}
+
+// ONE_PIXEL: the batch's sample count is a multiple of 64, every iteration is one pixel and the wave walks its list together; otherwise every
+// ray walks its own pixel's list (cam_trace_ray, as in k_trace_camera).  Two instantiations, chosen per batch by launch_camera_primary: with both
+// walks in one kernel the allocator spilled 46 registers into the entry and triangle loops, apart the wave walk needs no scratch at all.
+template <bool ONE_PIXEL>
+__global__ void __launch_bounds__(kBlock, PT_PRIMARY_WAVES)
+k_camera_primary(DeviceScene S, PathState st, vec4* __restrict__ Lbuf, vec4* __restrict__ hit, Segments seg, BatchCounters* __restrict__ ctr,
+                 uint32_t first_sample, uint32_t nsamples, uint32_t tilesX, uint32_t tilesY, const CamListEntry* __restrict__ cl_entries,
+                 const uint32_t* __restrict__ cl_count, uint32_t cl_cap, const BvhNode6* __restrict__ nodes) {
+  PT_TAIL_BEGIN
+  const uint32_t bounce = 0;
+  (void)bounce;
+  const uint32_t lane = wave_lane();
+  const uint32_t tiles = tilesX * tilesY;
+  const uint32_t seg_iters = seg.tiles_per_seg * nsamples;                     // wave iterations of a segment (k_raygen's k)
+  const uint32_t seg_units = (seg_iters + kPrimaryUnit - 1u) / kPrimaryUnit;
+  const uint32_t units = seg.nseg * seg_units;
+  uint32_t started = 0;
+  for (;;) {
+    PT_TAIL_MARK
+    uint32_t u = 0;
+    if (lane == 0) u = atomicAdd(&ctr->work_closest[0], 1u);
+    u = __builtin_amdgcn_readfirstlane(u);
+    PT_TAIL_T(tail_take)
+    if (u >= units) break;
+    const uint32_t sg = u / seg_units, k0 = (u - sg * seg_units) * kPrimaryUnit;
+    const uint32_t k1 = k0 + kPrimaryUnit < seg_iters ? k0 + kPrimaryUnit : seg_iters;
+    const uint32_t first_tile = segment_first_tile(seg, sg);
+    if (k0 == 0u && lane == 0) {
+      seg.active[0][sg] = camera_rays_before(first_tile, seg_iters, nsamples, tilesX, tiles, S.width, S.height);
+      seg.poison[sg] = 0u;
+    }
+    const uint32_t n_first = camera_rays_before(first_tile, k0, nsamples, tilesX, tiles, S.width, S.height);
+    uint32_t n_out = n_first;
+    for (uint32_t k = k0; k < k1; k++) {
+      const uint32_t tile = first_tile + k / nsamples;
+      if (tile >= tiles) break;  // wave-uniform
+      const uint32_t r0 = (k % nsamples) * 64u, r = r0 + lane;   // ray r of the tile's 64 * nsamples, pixel-major
+      const uint32_t pl = r / nsamples, s = r - pl * nsamples;
+      const PixelXY q = tile_pixel(tile, pl, tilesX);
+      const bool valid = q.x < S.width && q.y < S.height;
+      RayGenOut rg;
+      if (valid) rg = stage_raygen(S, q.x, q.y, first_sample + s);
+      const unsigned long long m = __ballot(valid);
+      uint32_t j = 0;
+      if (valid) {
+        j = seg_slot(seg.nseg, sg, n_out + wave_prefix(m));
+        const uint32_t pid = lbuf_index(tile, s, nsamples, pl);
+        const uint32_t rel = pid - first_tile * nsamples * 64u;  // relative to the segment's window (segment_lbuf_base)
+        st.rayO[j] = vec4{rg.o.x, rg.o.y, rg.o.z, 0.0f};
+        st.rayD[j] = vec4{rg.d.x, rg.d.y, rg.d.z, u2f((rg.dim & kMetaDimMask) | (rel << kMetaPidShift))};
+        st.att[j] = vec4{1.0f, 1.0f, 1.0f, u2f(rg.offset)};
+        Lbuf[pid] = vec4{0.0f, 0.0f, 0.0f, 1.0f};
+      }
+      n_out += (uint32_t)__popcll(m);
+      if (m == 0) continue;
+      // ---- k_trace_camera for these rays ----
+      // a ray's list: that of its pixel's slot (pixel_slot_of_pid of its pid); a count of kCamWalk leaves the pixel to k_trace_closest_unlisted
+      if constexpr (ONE_PIXEL) {
+        const uint32_t qs = tile * 64u + r0 / nsamples;
+        const uint32_t len = __builtin_amdgcn_readfirstlane(cl_count[qs]);
+        if (len == kCamWalk) continue;
+        TravState ts;
+        if (valid) {
+          float ir = 0.0f;  // alpha-test payload, as in k_trace_closest
+          if (S.has_alpha) ir = Halton{halton_table(S.halton), rg.offset, rg.dim & kMetaDimMask}.sample1d();
+          (void)trav_init(S, ts, rg.o, rg.d, 1e-3f, kInf, ir, TraversalStack{}, false, nullptr);   // (lists exist only over a tree whose root is a node)
+        }
+        cam_trace_wave(S, ts, valid, nodes, cl_entries + (size_t)qs * cl_cap, len);
+        if (valid) {
+          const RayHit& h = ts.best;
+          hit[j] = vec4{h.t, h.u, h.v, u2f(h.tri == kInvalidRef ? kInvalidRef : (h.tri | ((h.gid & 3u) << 28)))};
+        }
+      } else if (valid) {
+        const uint32_t qs = tile * 64u + pl;
+        const uint32_t len = cl_count[qs];
+        if (len != kCamWalk) {
+          float ir = 0.0f;
+          if (S.has_alpha) ir = Halton{halton_table(S.halton), rg.offset, rg.dim & kMetaDimMask}.sample1d();
+          TravState ts;
+          (void)trav_init(S, ts, rg.o, rg.d, 1e-3f, kInf, ir, TraversalStack{}, false, nullptr);
+          cam_trace_ray(S, ts, nodes, cl_entries + (size_t)qs * cl_cap, len);
+          const RayHit& h = ts.best;
+          hit[j] = vec4{h.t, h.u, h.v, u2f(h.tri == kInvalidRef ? kInvalidRef : (h.tri | ((h.gid & 3u) << 28)))};
+        }
+      }
+    }
+    started += n_out - n_first;
+  }
+  if (lane == 0) {
+    WaveStats& ws = seg.stats[wave_index()];
+    ws.paths += started;
+    ws.closest += started;
+  }
+  PT_TAIL_END(0)
 }
 
 // ---- shade -----------------------------------------------------------------------------------------------------------
@@ -1159,6 +1291,21 @@ void launch_trace_camera(hipStream_t s, uint32_t grid, uint32_t grid_unlisted, c
   if (any_unlisted) hipLaunchKernelGGL(k_trace_closest_unlisted, dim3(grid_unlisted), dim3(kBlock), 0, s, S, st, hit, seg, ctr, spill, cl);
 }
 uint32_t camera_blocks_per_cu() { return PT_CAMERA_WAVES; }
+void launch_camera_primary(hipStream_t s, uint32_t grid, uint32_t grid_unlisted, const DeviceScene& S, PathState st, vec4* Lbuf, vec4* hit, Segments seg,
+                           BatchCounters* ctr, uint32_t first_sample, uint32_t nsamples, uint32_t* spill, const CameraLists& cl, bool any_unlisted) {
+  const BvhNode6* nodes = reinterpret_cast<const BvhNode6*>(S.nodes);
+  if (PT_PRIMARY_UNIFORM && nsamples % 64u == 0u)
+    hipLaunchKernelGGL(k_camera_primary<true>, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, hit, seg, ctr, first_sample, nsamples, tiles_x(S.width),
+                       tiles_y(S.height), cl.entries, cl.count, cl.cap, nodes);
+  else
+    hipLaunchKernelGGL(k_camera_primary<false>, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, hit, seg, ctr, first_sample, nsamples, tiles_x(S.width),
+                       tiles_y(S.height), cl.entries, cl.count, cl.cap, nodes);
+  if (any_unlisted) {   // the walk claims from bounce 0's chunk table: the table pass comes first (the caller runs it otherwise)
+    launch_chunk_tables(s, seg, 0, ctr, 0, 0, false);
+    hipLaunchKernelGGL(k_trace_closest_unlisted, dim3(grid_unlisted), dim3(kBlock), 0, s, S, st, hit, seg, ctr, spill, cl);
+  }
+}
+uint32_t primary_blocks_per_cu() { return PT_PRIMARY_WAVES; }
 uint32_t shade_block_threads() { return kShadeBlock; }
 uint32_t shade_blocks_per_cu() { return (PT_SHADE_WAVES * 4 * 64) / PT_SHADE_BLOCK; }
 void launch_shade(hipStream_t s, uint32_t grid, const DeviceScene* S, PathState sin, PathState sout, const vec4* hit,

@@ -148,4 +148,31 @@ PT_HD void cam_trace_list(const DeviceScene& S, TravState& ts, const CamListEntr
   }
 }
 
+
+// cam_trace_list as the kernels run it per lane (k_trace_camera, and k_camera_primary where the lanes of a wave iteration belong to more than
+// one pixel): the same entries, children and triangles in the same order, as ONE loop whose step is either "next entry" or "next triangle".
+// The addresses do not depend on the traversal: entry i + 1 is loaded one step ahead, and its node is fetched as soon as entry i's slab
+// tests are done with the node registers — it arrives while entry i's triangles are tested.  (Holding two whole nodes cost 62 spilled
+// registers at 8 waves per SIMD.)  tests/emu holds it to cam_trace_list ray by ray.
+PT_HD void cam_trace_ray(const DeviceScene& S, TravState& ts, const BvhNode6* __restrict__ nodes, const CamListEntry* __restrict__ list, uint32_t len) {
+  const CamListEntry none{0u, kInf};
+  CamListEntry e = len ? list[0] : none;
+  uint32_t i = 0, m = 0, base_leaf = 0;   // m: the leaf children of the current entry still to be tested
+  for (;;) {
+    if (m == 0u) {
+      if (i >= len || e.dist > ts.best.t * kCamCullSlack) break;
+      const BvhNode6 n = nodes[e.ref >> 6];
+      m = node6_leaf_hits(n, ts, ts.best.t * kCamCullSlack) & e.ref & 63u;
+      base_leaf = n.base_leaf;
+      i++;
+      e = i < len ? list[i] : none;
+    } else {
+      const uint32_t r = (uint32_t)__builtin_ctz(m);
+      m &= m - 1u;
+      bool fin = false;
+      trav_leaf(S, ts, kLeafBit | (base_leaf + r), false, &fin, nullptr);
+    }
+  }
+}
+
 }  // namespace pt

@@ -94,4 +94,43 @@ PT_HD uint32_t segment_lbuf_base(uint32_t nseg, uint32_t bands, uint32_t tiles_p
   return segment_first_tile(nseg, bands, tiles_per_seg, sg) * nsamples * 64u;
 }
 
+
+// ---- where a camera ray lands in its segment ---------------------------------------------------------------------------
+// k_raygen walks a segment's tiles in order and each tile's 64 * nsamples rays pixel-major, sample-minor (ray r of a tile: pixel lane
+// r / nsamples, sample r % nsamples), 64 rays per wave iteration, and packs the rays of the pixels inside the image by ballot: packing keeps
+// the order.  The pixels of a tile inside the image form a rectangle vw x vh at the tile's origin, so a ray's place in its segment is a closed
+// form: (valid pixels before its pixel in the segment) * nsamples + sample.  k_camera_primary (kernels.hip) places a run of a segment's rays
+// with it, without the rays before them.
+PT_HD uint32_t tile_valid_w(uint32_t tile, uint32_t tilesX, uint32_t W) {
+  const uint32_t x0 = (tile % tilesX) * 8u;
+  return x0 >= W ? 0u : (W - x0 < 8u ? W - x0 : 8u);
+}
+PT_HD uint32_t tile_valid_h(uint32_t tile, uint32_t tilesX, uint32_t H) {
+  const uint32_t y0 = (tile / tilesX) * 8u;
+  return y0 >= H ? 0u : (H - y0 < 8u ? H - y0 : 8u);
+}
+// valid pixels of a tile whose lane is below `lane` (lane <= 64)
+PT_HD uint32_t tile_pixels_before(uint32_t lane, uint32_t vw, uint32_t vh) {
+  const uint32_t y = lane >> 3, x = lane & 7u;
+  return (y < vh ? y : vh) * vw + (y < vh ? (x < vw ? x : vw) : 0u);
+}
+// valid rays among rays [0, r) of a tile (r <= 64 * nsamples)
+PT_HD uint32_t tile_rays_before(uint32_t r, uint32_t nsamples, uint32_t vw, uint32_t vh) {
+  const uint32_t pl = r / nsamples, s = r - pl * nsamples;
+  const bool in = pl < 64u && (pl & 7u) < vw && (pl >> 3) < vh;
+  return tile_pixels_before(pl, vw, vh) * nsamples + (in ? s : 0u);
+}
+// Entry index (the r of seg_slot) of the first ray of wave iteration k of a segment whose first tile is `first_tile`: iteration k covers rays
+// [(k % nsamples) * 64, + 64) of tile first_tile + k / nsamples.  With k = tiles_per_seg * nsamples: the segment's ray count.  Tiles at or past
+// `tiles` (the segments behind the image's last tile) hold nothing.
+PT_HD uint32_t camera_rays_before(uint32_t first_tile, uint32_t k, uint32_t nsamples, uint32_t tilesX, uint32_t tiles, uint32_t W, uint32_t H) {
+  const uint32_t t_end = k / nsamples;
+  uint32_t n = 0;
+  for (uint32_t t = 0; t < t_end && first_tile + t < tiles; t++)
+    n += tile_valid_w(first_tile + t, tilesX, W) * tile_valid_h(first_tile + t, tilesX, H) * nsamples;
+  const uint32_t tile = first_tile + t_end;
+  if (tile < tiles) n += tile_rays_before((k - t_end * nsamples) * 64u, nsamples, tile_valid_w(tile, tilesX, W), tile_valid_h(tile, tilesX, H));
+  return n;
+}
+
 }  // namespace pt

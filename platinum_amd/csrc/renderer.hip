@@ -107,7 +107,21 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
   const bool ad = mode == BATCH_RENDER && r->vtiles;
   const uint32_t* ad_list = ad ? r->ad_list[r->ad_cur].p : nullptr;
   const uint32_t* ad_count = ad ? r->ad_count.p + r->ad_cur : nullptr;
-  {
+  // A full-frame render batch with lists generates and traces its camera rays in one kernel (k_camera_primary), timed as bounce 0's closest-hit
+  // launch together with the walk for flagged pixels; the table pass alone is left in the raygen class.
+  const bool fused = mode == BATCH_RENDER && r->cam_lists && !ad && !r->no_fused_camera;
+  if (fused) {
+    const bool any_unlisted = r->cam_stats.pixels_walk != 0;
+    {
+      ScopedTimer t(r, K_CLOSEST);
+      launch_camera_primary(s, r->primary_grid, r->closest_grid, S, r->path_state(0), r->Lbuf.p, r->hit.p, seg, ctr, first, ns, r->spill.p,
+                            CameraLists{r->cam_entries.p, r->cam_count.p, r->cam_cap}, any_unlisted);
+    }
+    if (!any_unlisted) {
+      ScopedTimer t(r, K_RAYGEN);
+      launch_chunk_tables(s, seg, 0, ctr, 0, 0, false);
+    }
+  } else {
     ScopedTimer t(r, K_RAYGEN);
     if (ad) launch_raygen_adaptive(s, r->grid, S, r->path_state(0), r->Lbuf.p, seg, first, ns, r->rect, ad_list, ad_count);
     else launch_raygen(s, r->grid, S, r->path_state(0), r->Lbuf.p, seg, ctr, first, ns);
@@ -116,7 +130,7 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
   int cur = 0;
   const bool mis = S.integrator == PT_INTEGRATOR_MIS;
   for (uint32_t b = 0; b < S.max_bounces; b++) {
-    {
+    if (b != 0 || !fused) {
       ScopedTimer t(r, K_CLOSEST);
       // the camera rays of a render batch come from the per-pixel leaf lists when the render has them; the debug and measuring batches keep the walk
       // (the hit log and nodes_per_ray stay what they are)
@@ -301,6 +315,7 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   if (const char* e = getenv("PTAMD_BLOCKS_PER_CU")) r->blocks_per_cu = (uint32_t)std::max(1, std::min(8, atoi(e)));
   if (const char* e = getenv("PTAMD_CLOSEST_BLOCKS_PER_CU")) r->closest_blocks_per_cu = (uint32_t)std::max(1, std::min(8, atoi(e)));
   if (const char* e = getenv("PTAMD_NO_CAMERA_LISTS")) r->no_camera_lists = atoi(e) != 0;
+  if (const char* e = getenv("PTAMD_NO_FUSED_CAMERA")) r->no_fused_camera = atoi(e) != 0;
   if (const char* e = getenv("PTAMD_TEST_CAMLIST_CAP")) r->cam_cap_override = (uint32_t)std::max(1, std::min((int)kCamListMaxCapacity, atoi(e)));
   if (const char* e = getenv("PTAMD_SHADOW_BLOCKS_PER_CU")) r->shadow_blocks_per_cu = (uint32_t)std::max(1, std::min(8, atoi(e)));
   hipDeviceProp_t prop;
@@ -587,9 +602,10 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
   r->grid = (uint32_t)r->num_cu * r->blocks_per_cu;                 // raygen, hit records: 256-thread blocks
   r->shade_grid = (uint32_t)r->num_cu * shade_blocks_per_cu();     // as many blocks as k_shade's registers / LDS keep resident
   r->camera_grid = (uint32_t)r->num_cu * camera_blocks_per_cu();
+  r->primary_grid = (uint32_t)r->num_cu * primary_blocks_per_cu();
   r->closest_grid = (uint32_t)r->num_cu * (r->two_level ? trace_blocks_per_cu_two_level() : r->closest_blocks_per_cu);
   r->shadow_grid = (uint32_t)r->num_cu * (r->two_level ? trace_blocks_per_cu_two_level() : r->shadow_blocks_per_cu);
-  r->nstats = std::max(r->grid * (kBlock / 64), r->shade_grid * (shade_block_threads() / 64));
+  r->nstats = std::max(std::max(r->grid, r->primary_grid) * (kBlock / 64), r->shade_grid * (shade_block_threads() / 64));
   for (int k = 0; k < 2; k++) {
     PT_HIP(r->st_rayO[k].alloc(r->capacity)); PT_HIP(r->st_rayD[k].alloc(r->capacity));
     PT_HIP(r->st_att[k].alloc(r->capacity));

@@ -13,5 +13,5 @@ for u in denoise adaptive renderer; do
   /opt/rocm/bin/hipcc $F "$@" -c $u.hip -o /tmp/${u}_$tag.o
   objs="$objs /tmp/${u}_$tag.o"
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o libptamd_$tag.so $objs multi_device.o camera_lists.o lbvh.o scene_io.o scene_gltf.o scene_image.o scene_jpeg.o -lz -ldl -lpthread
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o libptamd_$tag.so $objs multi_device.o camera_lists.o exposure.o bloom.o math_probe.o lbvh.o scene_io.o scene_gltf.o scene_image.o scene_jpeg.o -lz -ldl -lpthread
 echo built libptamd_$tag.so
