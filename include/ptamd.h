@@ -613,6 +613,53 @@ typedef struct pt_camera_list_stats {
 /* PT_ERR_BAD_STATE before pt_start_render.  Does not block. */
 int pt_get_camera_list_stats(pt_renderer* r, pt_camera_list_stats* out);
 
+/* ---- ID mattes (NEW, an additive extension of ABI 5: new entry points and three new structs, no existing struct changed) ----
+ * A render started while `enabled` is set keeps, beside the accumulator, what each pixel's camera rays hit first: two layers of
+ * PT_MATTE_SLOTS slots {id, count} per pixel.
+ *   PT_MATTE_INSTANCE  id = the index of the hit instance in pt_scene_snapshot.instances
+ *   PT_MATTE_MATERIAL  id = the index of the hit triangle's material in the flattened material table:
+ *                      (sum of instance_materials[j].material_count over the instances j before the hit one) + the triangle's material slot
+ * A camera ray that hits nothing has the id PT_MATTE_NONE on both layers, and takes a slot like any other id.
+ * The fold: a pixel's samples are folded in sample order 0, 1, 2, ...  The slots are scanned 0 .. PT_MATTE_SLOTS - 1: the first slot with
+ * count != 0 and the sample's id gets count + 1; otherwise the first slot with count == 0 becomes {id, 1}; otherwise the sample goes to
+ * nothing.  Slots are first come, with no eviction; an empty slot is {PT_MATTE_NONE, 0}.  With n the pixel's sample count
+ * (pt_read_sample_counts), other = n - (the sum of the counts) is the number of samples that found no slot: 0 wherever at most
+ * PT_MATTE_SLOTS distinct ids were seen.  The slots are a function of the ordered sample sequence: the same bits for any samples_in_flight
+ * and any sequence of pt_render_step calls, for every acceleration structure and with or without the camera-ray leaf lists.
+ * Mattes work with GMoN, render regions (pixels outside the region keep empty slots), adaptive sampling (a tile's slots stop with the
+ * tile), thin-lens cameras and every acceleration structure; they are independent of the AOVs and the denoiser, and every other output of
+ * the render is the bits it is without them.  pt_trace_primary, pt_debug_sample and pt_measure_traversal never touch the slots.
+ * Memory: 8 B per path slot and 128 B per pixel, held only by a render that enabled mattes.  pt_plan_queues describes matte-off renders.
+ * Refused with PT_ERR_UNSUPPORTED: enabled = 1 on a device group (slot lists do not merge by a sum). */
+#define PT_MATTE_SLOTS 8
+#define PT_MATTE_NONE 0xFFFFFFFFu
+enum { PT_MATTE_INSTANCE = 0, PT_MATTE_MATERIAL = 1 };
+typedef struct pt_matte_options {
+  uint32_t enabled;         /* read at pt_start_render; default 0 */
+} pt_matte_options;
+typedef struct pt_matte_slot {
+  uint32_t id, count;
+} pt_matte_slot;
+void pt_default_matte_options(pt_matte_options* o);
+int pt_set_matte_options(pt_renderer* r, const pt_matte_options* o);
+/* The slots of one layer, W*H*PT_MATTE_SLOTS of them: pixel-major (row-major pixels), each pixel's slots in first-seen order.  Blocks like
+ * pt_read_accumulator.  PT_ERR_INVALID_ARGUMENT for a layer that does not exist; PT_ERR_BAD_STATE before pt_start_render and for a render
+ * started without mattes (pt_read_matte and pt_pick alike). */
+int pt_read_matte_slots(pt_renderer* r, uint32_t layer, pt_matte_slot* out);
+/* Coverage of the id set ids[0, id_count) (any order, duplicates allowed; PT_MATTE_NONE selects the background) per pixel, W*H floats:
+ * (float)(the sum of the counts of the pixel's slots whose id is in the set) / (float)n, one IEEE division; 0 where n = 0 and for the empty
+ * set.  One kernel over the slots; blocks.  PT_ERR_INVALID_ARGUMENT for a bad layer, or ids NULL with id_count > 0. */
+int pt_read_matte(pt_renderer* r, uint32_t layer, const uint32_t* ids, uint32_t id_count, float* coverage_out);
+typedef struct pt_pick_result {
+  uint32_t instance, instance_count;          /* the instance-layer slot with the largest count, ties to the lowest slot; PT_MATTE_NONE = background */
+  uint32_t material, material_count;          /* the same on the material layer */
+  uint32_t material_instance, material_slot;  /* `material` decoded into the caller's (instance, material slot); PT_MATTE_NONE for background */
+  uint32_t samples, _pad;                     /* the pixel's n */
+} pt_pick_result;
+/* What is under pixel (x, y), top-left origin: one 128-byte read-back after a stream sync, no kernel (an adaptive render reads its tile's
+ * sample count too).  PT_ERR_INVALID_ARGUMENT for x >= width or y >= height. */
+int pt_pick(pt_renderer* r, uint32_t x, uint32_t y, pt_pick_result* out);
+
 const char* pt_last_error(void);
 
 /* ---------------------------------------------------------------------------------------------------------- */

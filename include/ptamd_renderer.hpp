@@ -45,6 +45,9 @@
  *                                                                handed over at startRender
  *   (no counterpart)                                             pt_render_region& renderRegion() / setRenderRegion(...): sample only a pixel
  *                                                                rectangle of the frame (ptamd.h, ABI 5 extension); handed over at startRender
+ *   (no counterpart; the raster viewport's selection only)       pt_matte_options& matteOptions(), readbackMatteSlots(), readbackMatte(), pick():
+ *                                                                ID mattes, per-pixel instance and material coverage of the camera rays' first
+ *                                                                hits (ptamd.h, ABI 5 extension); handed over at startRender
  * Error behaviour as the reference's: nothing throws; a failing call prints "renderer_pt: <message>" to stderr (the
  * reference prints and asserts, renderer_pt.cpp:402, 1044) and leaves the object in Status_Blocked; lastError() keeps the text.
  * Threading as the reference's: one caller thread per Renderer.
@@ -120,6 +123,7 @@ public:
     if (!check(pt_set_denoise_options(m_pt, &m_denoise))) return;   // (`enabled` is read here)
     if (!check(pt_set_adaptive_options(m_pt, &m_adaptive))) return;  // (read here)
     if (!check(pt_set_render_region(m_pt, &m_region))) return;       // (read here)
+    if (!check(pt_set_matte_options(m_pt, &m_matte))) return;        // (read here)
     if (!check(pt_start_render(m_pt, &scene, &p))) return;
     m_size = uint2{p.width, p.height};
     m_started = true;
@@ -244,6 +248,28 @@ public:
   [[nodiscard]] constexpr pt_render_region& renderRegion() { return m_region; }
   void setRenderRegion(const pt_render_region& o) { m_region = o; }
   void setRenderRegion(uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) { m_region = pt_render_region{1u, x0, y0, x1, y1}; }
+  // ID mattes (ptamd.h, an additive extension of ABI 5): a render started with enabled set keeps, per pixel, which instances and materials
+  // its camera rays hit first.  Edited in place like adaptiveOptions(); read at startRender.
+  [[nodiscard]] constexpr pt_matte_options& matteOptions() { return m_matte; }
+  void setMatteOptions(const pt_matte_options& o) { m_matte = o; }
+  // The slots of one layer (PT_MATTE_INSTANCE / PT_MATTE_MATERIAL), W*H*PT_MATTE_SLOTS; empty for a render started without mattes.  Blocks.
+  [[nodiscard]] std::vector<pt_matte_slot> readbackMatteSlots(uint32_t layer) const {
+    std::vector<pt_matte_slot> out;
+    if (!m_pt || !m_started) return out;
+    out.resize((size_t)m_size.x * m_size.y * PT_MATTE_SLOTS);
+    if (!check(pt_read_matte_slots(m_pt, layer, out.data()))) out.clear();
+    return out;
+  }
+  // Coverage of a set of ids of one layer, W*H floats in [0, 1]: a selection mask (PT_MATTE_NONE selects the background).  Blocks.
+  [[nodiscard]] std::vector<float> readbackMatte(uint32_t layer, const std::vector<uint32_t>& ids) const {
+    std::vector<float> out;
+    if (!m_pt || !m_started) return out;
+    out.resize((size_t)m_size.x * m_size.y);
+    if (!check(pt_read_matte(m_pt, layer, ids.empty() ? nullptr : ids.data(), (uint32_t)ids.size(), out.data()))) out.clear();
+    return out;
+  }
+  // What is under pixel (x, y), top-left origin ("click to select"); false on failure.  Blocks until the enqueued samples are done.
+  [[nodiscard]] bool pick(uint32_t x, uint32_t y, pt_pick_result* out) const { return m_pt && m_started && out && check(pt_pick(m_pt, x, y, out)); }
   void wait() const { if (m_pt && m_started) check(pt_wait(m_pt)); }
   [[nodiscard]] bool ok() const { return m_pt != nullptr && m_lastError.empty(); }
   [[nodiscard]] const std::string& lastError() const { return m_lastError; }
@@ -260,6 +286,7 @@ private:
     pt_default_bloom_options(&m_bloom);
     pt_default_adaptive_options(&m_adaptive);
     pt_default_render_region(&m_region);
+    pt_default_matte_options(&m_matte);
     std::vector<int32_t> ord(devices, devices + count);
     pt_create_info ci{};
     ci.abi_version = PT_ABI_VERSION;
@@ -306,6 +333,7 @@ private:
   pt_bloom_options m_bloom{};
   pt_adaptive_options m_adaptive{};
   pt_render_region m_region{};
+  pt_matte_options m_matte{};
   mutable void* m_presentStream = nullptr;
   mutable std::string m_lastError;
 };

@@ -229,6 +229,29 @@ class CameraListStats(C.Structure):
                 ("entries", C.c_uint64), ("build_ms", C.c_double), ("length_histogram", C.c_uint32 * 65), ("_pad", C.c_uint32)]
 
 
+MATTE_SLOTS, MATTE_NONE = 8, 0xFFFFFFFF
+MATTE_INSTANCE, MATTE_MATERIAL = 0, 1
+
+
+class MatteOptions(C.Structure):
+    """pt_matte_options: ID mattes (per-pixel instance and material coverage of the camera rays' first hits); read at pt_start_render."""
+    _fields_ = [("enabled", C.c_uint32)]
+
+
+class MatteSlot(C.Structure):
+    """pt_matte_slot: one of a pixel's MATTE_SLOTS slots of a layer; empty = {MATTE_NONE, 0}."""
+    _fields_ = [("id", C.c_uint32), ("count", C.c_uint32)]
+
+
+MATTE_SLOT_DTYPE = [("id", "<u4"), ("count", "<u4")]
+
+
+class PickResult(C.Structure):
+    """pt_pick_result: the dominant instance and material under a pixel, the material decoded into (instance, slot), the pixel's samples."""
+    _fields_ = [("instance", C.c_uint32), ("instance_count", C.c_uint32), ("material", C.c_uint32), ("material_count", C.c_uint32),
+                ("material_instance", C.c_uint32), ("material_slot", C.c_uint32), ("samples", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class HitRecord(C.Structure):
     _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("instance", C.c_int32), ("primitive", C.c_int32)]
 
@@ -308,6 +331,11 @@ SYMBOLS = [
     ("pt_set_render_region", C.c_int, [C.c_void_p, C.POINTER(RenderRegion)]),
     ("pt_region_tiles", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(RenderRegion), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("pt_get_camera_list_stats", C.c_int, [C.c_void_p, C.POINTER(CameraListStats)]),
+    ("pt_default_matte_options", None, [C.POINTER(MatteOptions)]),
+    ("pt_set_matte_options", C.c_int, [C.c_void_p, C.POINTER(MatteOptions)]),
+    ("pt_read_matte_slots", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("pt_read_matte", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("pt_pick", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PickResult)]),
     ("pt_last_error", C.c_char_p, []),
     ("pt_get_constants", C.c_int, [C.c_void_p, C.POINTER(Constants)]),
     ("pt_get_lights", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),

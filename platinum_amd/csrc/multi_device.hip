@@ -801,6 +801,30 @@ int pt_read_sample_counts(pt_renderer* r, uint32_t* out) {
   return PT_OK;
 }
 
+// ID mattes are per device: slot lists in first-seen order do not merge by a sum, so a group does not keep them
+int pt_set_matte_options(pt_renderer* r, const pt_matte_options* o) {
+  if (!is_group(r)) return dev_set_matte_options(r, o);
+  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (o->enabled) return fail(PT_ERR_UNSUPPORTED, "pt_set_matte_options: a device group does not keep ID mattes");
+  for (auto* m : r->group->shards) { int rc = dev_set_matte_options(m, o); if (rc != PT_OK) return rc; }
+  return PT_OK;
+}
+
+int pt_read_matte_slots(pt_renderer* r, uint32_t layer, pt_matte_slot* out) {
+  if (!is_group(r)) return dev_read_matte_slots(r, layer, out);
+  return fail(PT_ERR_BAD_STATE, "pt_read_matte_slots: a device group does not keep ID mattes");
+}
+
+int pt_read_matte(pt_renderer* r, uint32_t layer, const uint32_t* ids, uint32_t id_count, float* coverage_out) {
+  if (!is_group(r)) return dev_read_matte(r, layer, ids, id_count, coverage_out);
+  return fail(PT_ERR_BAD_STATE, "pt_read_matte: a device group does not keep ID mattes");
+}
+
+int pt_pick(pt_renderer* r, uint32_t x, uint32_t y, pt_pick_result* out) {
+  if (!is_group(r)) return dev_pick(r, x, y, out);
+  return fail(PT_ERR_BAD_STATE, "pt_pick: a device group does not keep ID mattes");
+}
+
 int pt_get_stats(pt_renderer* r, pt_stats* out) {
   if (!r || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
   return is_group(r) ? group_get_stats(r, out) : dev_get_stats(r, out);

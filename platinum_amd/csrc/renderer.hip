@@ -142,6 +142,12 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
     }
     // first-hit AOVs of a render that keeps them (denoise.hip): the camera rays' hits, read from the queue before k_shade consumes it
     if (b == 0 && mode == BATCH_RENDER && r->aov) launch_aov(s, r->grid, r->scene_d.p, r->path_state(cur), r->hit.p, seg, r->Abuf.p);
+    // ID mattes of a render that keeps them (matte.hip): the same hits' instance and material, independent of the AOVs (timed with the
+    // accumulate class, where its other kernel is: pt_stats.ms_accumulate with mattes on minus off is what mattes cost)
+    if (b == 0 && mode == BATCH_RENDER && r->matte) {
+      ScopedTimer t(r, K_ACCUM);
+      launch_matte_ids(s, r->grid, r->scene_d.p, r->path_state(cur), r->hit.p, seg, r->Mbuf.p);
+    }
     {
       ScopedTimer t(r, K_SHADE);
       launch_shade(s, r->shade_grid, r->scene_d.p, r->path_state(cur), r->path_state(cur ^ 1), r->hit.p, r->shadow_queue(), r->Lbuf.p, seg, (uint32_t)cur, ctr, b);
@@ -178,6 +184,10 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
     else if (r->aov)
       launch_accumulate_aov(s, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * (size_t)npix, r->Abuf.p, r->Lbuf.p, S.width, S.height, ns, n0,
                             r->params.nonfinite_policy);
+    if (r->matte && ad)
+      launch_accumulate_matte_adaptive(s, r->matte_slots.p, r->Mbuf.p, S.width, S.height, ns, ad_list, ad_count, r->ad_tiles0, r->rect);
+    else if (r->matte)
+      launch_accumulate_matte(s, r->matte_slots.p, r->Mbuf.p, S.width, S.height, ns);
   }
   // a batch that ends at a checkpoint (flush_pending never lets one straddle it): test the active tiles, compact the list into the other
   // buffer, and send the new count to pinned host memory
@@ -307,6 +317,7 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   pt_default_bloom_options(&r->bloom);
   pt_default_adaptive_options(&r->adaptive_opts);
   pt_default_render_region(&r->region_opts);
+  pt_default_matte_options(&r->matte_opts);
   r->device = device_ordinal;
   if (const char* e = getenv("PTAMD_REFILL")) r->refill_threshold = (uint32_t)atoi(e);
   if (const char* e = getenv("PTAMD_TILES_PER_SEG")) r->tiles_per_seg_override = (uint32_t)std::max(0, atoi(e));  // tuning knobs
@@ -577,6 +588,8 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
   const uint64_t npix = (uint64_t)p->width * p->height;
   const bool aov = r->denoise.enabled != 0;
   if (!aov) { r->Abuf.release(); r->aov_img.release(); }  // (an AOV-off render holds nothing more than before)
+  const bool matte = r->matte_opts.enabled != 0;
+  if (!matte) { r->Mbuf.release(); r->matte_slots.release(); r->matte_ids.release(); r->matte_cov.release(); }   // (nor does a matte-off render)
   const bool adaptive = r->adaptive_opts.enabled != 0;
   const bool region = r->region_opts.enabled != 0;
   if (!adaptive) r->release_checkpoints();                  // (nor does an adaptive-off render;
@@ -587,7 +600,7 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
   // so every grid is sized for its own kernel's occupancy.
   {
     const uint64_t budget = queue_budget(free_device_bytes(), r->queue_bytes_held(), r->cam_entries.bytes_held() + r->cam_count.bytes_held(), aov,
-                                         r->Abuf.bytes_held());
+                                         r->Abuf.bytes_held(), matte, r->Mbuf.bytes_held());
     pt_queue_plan plan{};
     const char* why = "";
     const int rc = plan_queues(p->width, p->height, p->spp, p->samples_in_flight, budget, r->tiles_per_seg_override, r->seg_bands, &plan, &why);
@@ -641,6 +654,12 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
     PT_HIP(r->aov_img.alloc(3 * npix));
     PT_HIP(hipMemsetAsync(r->aov_img.p, 0, sizeof(vec4) * 3 * npix, r->stream));
   }
+  if (matte) {
+    PT_HIP(r->Mbuf.alloc(r->Lbuf.n));
+    PT_HIP(r->matte_slots.alloc((size_t)npix * kMattePixelVec4));
+    launch_matte_clear(r->stream, r->matte_slots.p, (size_t)npix);   // every slot {PT_MATTE_NONE, 0}
+    PT_HIP(hipGetLastError());
+  }
   if (adaptive || region) {  // every tile the rectangle touches starts active (the whole frame: [0, tiles)), ascending (adaptive.hip)
     const Rect rect = render_rect(r, p);
     const uint32_t tiles = tile_count(p->width, p->height);
@@ -678,6 +697,7 @@ void reset_progress(pt_renderer* r, const pt_render_params* p) {
   r->batch_done_valid = false;
   r->total = p->spp;
   r->aov = r->denoise.enabled != 0;
+  r->matte = r->matte_opts.enabled != 0;
   r->adaptive = r->adaptive_opts.enabled != 0;
   r->region = r->region_opts.enabled != 0;
   r->vtiles = r->adaptive || r->region;
@@ -713,6 +733,8 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   };
   HostScene hs;
   if ((rc = flatten_scene(r, scene, p, &hs)) != PT_OK) return rc;
+  r->material_base.resize(hs.instances.size());
+  for (size_t i = 0; i < hs.instances.size(); i++) r->material_base[i] = hs.instances[i].material_base;
   phase("host flatten + light table");
   if ((rc = upload_scene(r, p, &hs)) != PT_OK) return rc;
   phase("upload");
@@ -1241,6 +1263,93 @@ int dev_set_render_region(pt_renderer* r, const pt_render_region* o) {
     return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_render_region: the region is empty (x0 < x1 and y0 < y1 are required)");
   if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_render_region: null renderer");
   r->region_opts = *o;
+  return PT_OK;
+}
+
+// ---- ID mattes (matte.hip, pt_matte.h) ----------------------------------------------------------------------------------------------------
+extern "C" void pt_default_matte_options(pt_matte_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+}
+
+int dev_set_matte_options(pt_renderer* r, const pt_matte_options* o) {
+  if (!r || !o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  r->matte_opts = *o;
+  return PT_OK;
+}
+
+namespace {
+
+// what every matte read checks first, in this order: the arguments, then the render's state
+int matte_read_check(const pt_renderer* r, const void* out, uint32_t layer, const char* who) {
+  if (!r || !out) return fail(PT_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+  if (layer >= kMatteLayers) return fail(PT_ERR_INVALID_ARGUMENT, std::string(who) + ": no such layer");
+  if (!r->started || !r->matte) return fail(PT_ERR_BAD_STATE, std::string(who) + ": the render was not started with mattes enabled");
+  return PT_OK;
+}
+
+}  // namespace
+
+int dev_read_matte_slots(pt_renderer* r, uint32_t layer, pt_matte_slot* out) {
+  int rc = matte_read_check(r, out, layer, "pt_read_matte_slots");
+  if (rc != PT_OK) return rc;
+  if ((rc = dev_wait(r)) != PT_OK) return rc;
+  // one layer out of the [pixel][layer][slot] image: rows of 64 B, 128 B apart
+  const size_t npix = (size_t)r->S.width * r->S.height, row = kMattePixelBytes / kMatteLayers;
+  PT_HIP(hipMemcpy2D(out, row, (const uint8_t*)r->matte_slots.p + layer * row, kMattePixelBytes, row, npix, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+int dev_read_matte(pt_renderer* r, uint32_t layer, const uint32_t* ids, uint32_t id_count, float* coverage_out) {
+  int rc = matte_read_check(r, coverage_out, layer, "pt_read_matte");
+  if (rc == PT_ERR_INVALID_ARGUMENT) return rc;
+  if (id_count && !ids) return fail(PT_ERR_INVALID_ARGUMENT, "pt_read_matte: null id set");
+  if (rc != PT_OK) return rc;
+  if ((rc = dev_wait(r)) != PT_OK) return rc;
+  const std::vector<uint32_t> set = matte_id_set(ids, id_count);
+  const size_t npix = (size_t)r->S.width * r->S.height;
+  PT_HIP(r->matte_ids.alloc(std::max<size_t>(1, set.size())));
+  if (!set.empty()) PT_HIP(hipMemcpyAsync(r->matte_ids.p, set.data(), sizeof(uint32_t) * set.size(), hipMemcpyHostToDevice, r->stream));
+  PT_HIP(r->matte_cov.alloc(npix));
+  launch_matte_resolve(r->stream, r->matte_slots.p, layer, r->matte_ids.p, (uint32_t)set.size(), r->vtiles ? r->ad_tile_n.p : nullptr,
+                       (uint32_t)r->launched, r->rect, r->S.width, r->S.height, r->matte_cov.p);
+  PT_HIP(hipGetLastError());
+  PT_HIP(hipStreamSynchronize(r->stream));   // (`set` is read by the copy until here)
+  PT_HIP(hipMemcpy(coverage_out, r->matte_cov.p, sizeof(float) * npix, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+int dev_pick(pt_renderer* r, uint32_t x, uint32_t y, pt_pick_result* out) {
+  if (!r || !out) return fail(PT_ERR_INVALID_ARGUMENT, "pt_pick: null argument");
+  if (!r->started || !r->matte) return fail(PT_ERR_BAD_STATE, "pt_pick: the render was not started with mattes enabled");
+  if (x >= r->S.width || y >= r->S.height) return fail(PT_ERR_INVALID_ARGUMENT, "pt_pick: the pixel is outside the frame");
+  int rc = dev_wait(r);
+  if (rc != PT_OK) return rc;
+  pt_matte_slot px[kMatteLayers][kMatteSlots];
+  static_assert(sizeof(px) == kMattePixelBytes, "pt_pick reads one pixel of the slot image");
+  PT_HIP(hipMemcpy(px, (const uint8_t*)r->matte_slots.p + ((size_t)y * r->S.width + x) * kMattePixelBytes, sizeof(px), hipMemcpyDeviceToHost));
+  uint32_t n = rect_contains(r->rect, x, y) ? (uint32_t)r->launched : 0u;
+  if (n && r->adaptive)   // the tile's own count
+    PT_HIP(hipMemcpy(&n, r->ad_tile_n.p + tile_of_pixel(x, y, r->S.width), sizeof(n), hipMemcpyDeviceToHost));
+  uint32_t win[kMatteLayers][2];
+  for (uint32_t l = 0; l < kMatteLayers; l++) {
+    MatteSlots m;
+    for (uint32_t k = 0; k < kMatteSlots; k++) { m.id[k] = px[l][k].id; m.count[k] = px[l][k].count; }
+    const uint32_t b = matte_pick(m);
+    win[l][0] = m.id[b]; win[l][1] = m.count[b];
+  }
+  *out = pt_pick_result{};
+  out->instance = win[PT_MATTE_INSTANCE][0]; out->instance_count = win[PT_MATTE_INSTANCE][1];
+  out->material = win[PT_MATTE_MATERIAL][0]; out->material_count = win[PT_MATTE_MATERIAL][1];
+  out->material_instance = out->material_slot = PT_MATTE_NONE;
+  if (out->material != PT_MATTE_NONE && !r->material_base.empty()) {
+    // the last instance whose first material is at or before it (instances without materials share their successor's base)
+    const auto it = std::upper_bound(r->material_base.begin(), r->material_base.end(), out->material);
+    const size_t i = (size_t)(it - r->material_base.begin()) - (it == r->material_base.begin() ? 0u : 1u);
+    out->material_instance = (uint32_t)i;
+    out->material_slot = out->material - r->material_base[i];
+  }
+  out->samples = n;
   return PT_OK;
 }
 

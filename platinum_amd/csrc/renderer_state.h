@@ -15,6 +15,7 @@
 #include "denoise.h"
 #include "exposure.h"
 #include "math_probe.h"
+#include "matte.h"
 #include "pt_math_probe.h"
 #include "kernels.h"
 #include "pt_bvh.h"
@@ -136,6 +137,14 @@ struct pt_renderer {
   DevBuf<vec4> Abuf;                // 2 vec4 per Lbuf entry: {albedo, t}, {normal, hit}
   DevBuf<vec4> aov_img;             // [PT_AOV_*][pixel] running means
   DevBuf<vec4> dn_guide, dn_aux, dn_col[2], denoised;  // the filter's per-pixel buffers and its output
+  // ID mattes (matte.hip): only a render started with matte_opts.enabled allocates or launches any of it
+  pt_matte_options matte_opts{};
+  bool matte = false;               // this render keeps mattes
+  DevBuf<MatteIds> Mbuf;            // {instance, material} of the first hit per Lbuf entry
+  DevBuf<uint4> matte_slots;        // [pixel][layer][slot] {id, count}: kMattePixelVec4 uint4 per pixel
+  DevBuf<uint32_t> matte_ids;       // pt_read_matte: the caller's id set, sorted
+  DevBuf<float> matte_cov;          // pt_read_matte: the coverage image
+  std::vector<uint32_t> material_base;  // [instance] index of its first material in the flattened table (pt_pick decodes with it)
   // auto exposure (exposure.hip): nothing is allocated or launched until a target is read with exposure.enabled, or the
   // meter is read.  The record holds the previous ev, so it outlives pt_start_render like the other arrays.
   pt_exposure_options exposure{};
@@ -225,6 +234,7 @@ struct pt_renderer {
     acc = nullptr;
     started = false;
     aov = false;
+    matte = false;
     cam_lists = false;
     adaptive = false;
     region = false;
@@ -296,3 +306,7 @@ int dev_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o);
 int dev_read_sample_counts(pt_renderer* r, uint32_t* out);
 int dev_set_render_region(pt_renderer* r, const pt_render_region* o);
 int dev_get_camera_list_stats(pt_renderer* r, pt_camera_list_stats* out);
+int dev_set_matte_options(pt_renderer* r, const pt_matte_options* o);
+int dev_read_matte_slots(pt_renderer* r, uint32_t layer, pt_matte_slot* out);
+int dev_read_matte(pt_renderer* r, uint32_t layer, const uint32_t* ids, uint32_t id_count, float* coverage_out);
+int dev_pick(pt_renderer* r, uint32_t x, uint32_t y, pt_pick_result* out);

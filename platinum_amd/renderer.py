@@ -328,6 +328,47 @@ class Renderer:
         abi.check(self._lib, self._lib.pt_set_render_region(self._h, C.byref(o)))
         self._region = o
 
+    # ID mattes (include/ptamd.h, an additive extension of ABI 5): no reference counterpart
+    def matteOptions(self):
+        """The options in effect (pt_default_matte_options until setMatteOptions is called)."""
+        if getattr(self, "_matte", None) is None:
+            self._matte = abi.MatteOptions()
+            self._lib.pt_default_matte_options(C.byref(self._matte))
+        o = abi.MatteOptions()
+        C.memmove(C.byref(o), C.byref(self._matte), C.sizeof(o))
+        return o
+
+    def setMatteOptions(self, o=None, **fields):
+        """Sets `o` (default: the current options) with `fields` overriding it, e.g. setMatteOptions(enabled=1).
+        The options take effect at the next startRender."""
+        o = self.matteOptions() if o is None else o
+        for k, v in fields.items():
+            setattr(o, k, v)
+        abi.check(self._lib, self._lib.pt_set_matte_options(self._h, C.byref(o)))
+        self._matte = o
+
+    def readbackMatteSlots(self, layer):
+        """(H, W, abi.MATTE_SLOTS) records {id, count} of layer abi.MATTE_INSTANCE / MATTE_MATERIAL, each pixel's slots in first-seen order;
+        an empty slot is {abi.MATTE_NONE, 0}."""
+        w, h = self.size
+        out = np.empty((h, w, abi.MATTE_SLOTS), dtype=abi.MATTE_SLOT_DTYPE)
+        abi.check(self._lib, self._lib.pt_read_matte_slots(self._h, layer, out.ctypes.data))
+        return out
+
+    def readbackMatte(self, layer, ids):
+        """(H, W) float32 coverage of the ids (any iterable of instance or material indices; abi.MATTE_NONE selects the background)."""
+        w, h = self.size
+        ids = np.ascontiguousarray(np.asarray(list(ids), dtype=np.uint32).reshape(-1))
+        out = np.empty((h, w), dtype=np.float32)
+        abi.check(self._lib, self._lib.pt_read_matte(self._h, layer, ids.ctypes.data if ids.size else None, ids.size, out.ctypes.data))
+        return out
+
+    def pick(self, x, y):
+        """abi.PickResult of pixel (x, y), top-left origin: what most of its camera samples hit first."""
+        out = abi.PickResult()
+        abi.check(self._lib, self._lib.pt_pick(self._h, x, y, C.byref(out)))
+        return out
+
     def setGmonOptions(self, cap=1.0):
         """gmonOptions().cap (renderer_pt.hpp:71)."""
         o = abi.GmonOptions(cap)

@@ -10,11 +10,14 @@ tracing (GMoN optional), fused post-process + tonemap — to an 8-bit PNG.
     python tools/render_scene.py builtin:c5 out.png --size 960 540 --spp 32 --auto-exposure
     python tools/render_scene.py builtin:c5 out.png --size 960 540 --spp 32 --auto-exposure --bloom 0.1
     python tools/render_scene.py builtin:c3 corner.png --size 1920 1080 --spp 4096 --region 1200,600,1500,800
+    python tools/render_scene.py builtin:c3 out.png --size 960 540 --spp 32 --matte instance      (writes out.instance.png beside out.png)
 """
 import argparse, os, struct, sys, time, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from platinum_amd import Renderer, abi, scene_io, scenes
+import png
 
 
 def write_png_rgba8(path, img):
@@ -24,6 +27,17 @@ def write_png_rgba8(path, img):
         return struct.pack(">I", len(d)) + t + d + struct.pack(">I", zlib.crc32(t + d) & 0xFFFFFFFF)
     with open(path, "wb") as f:
         f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 6, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+
+
+def matte_false_colour(slots, n):
+    """(H, W, 3) float image of one matte layer: every slot's id hashed to a colour (the background, abi.MATTE_NONE, black), weighted by
+    count / n; samples that found no slot (more than abi.MATTE_SLOTS ids in a pixel) add nothing.  slots (H, W, MATTE_SLOTS), n (H, W)."""
+    ids = slots["id"].astype(np.uint64)
+    h = (ids * 2654435761 + 0x9E3779B9) & 0xFFFFFFFF          # Knuth's multiplicative hash: neighbouring ids get unrelated colours
+    rgb = np.stack([(h >> s) & 0xFF for s in (0, 8, 16)], axis=-1).astype(np.float32) / 255.0 * 0.85 + 0.15
+    rgb[slots["id"] == abi.MATTE_NONE] = 0.0
+    w = slots["count"].astype(np.float32) / np.maximum(n, 1).astype(np.float32)[..., None]
+    return (rgb * w[..., None]).sum(axis=2)
 
 
 def main():
@@ -48,6 +62,9 @@ def main():
                     help="tile-adaptive sampling: an 8x8 tile stops once every pixel's relative error is <= THRESHOLD (--spp is the maximum)")
     ap.add_argument("--region", default=None, metavar="X0,Y0,X1,Y1",
                     help="render region: sample only the pixels [X0, X1) x [Y0, Y1) (top-left origin); the rest of the image stays empty (alpha 0)")
+    ap.add_argument("--matte", choices=("instance", "material"), action="append", default=[],
+                    help="keep ID mattes and write a false-colour image of this layer beside the picture (OUTPUT.instance.png / OUTPUT.material.png): "
+                         "what every pixel's camera rays hit first, each id a colour, weighted by its share of the pixel's samples; may be given twice")
     a = ap.parse_args()
     if a.despeckle is not None and not a.denoise:
         ap.error("--despeckle is a stage of the denoiser: it needs --denoise")
@@ -90,6 +107,8 @@ def main():
         r.setAdaptiveOptions(enabled=1, threshold=a.adaptive)
     if region is not None:
         r.setRenderRegion(*region)
+    if a.matte:
+        r.setMatteOptions(enabled=1)
     flags = abi.FLAG_MULTISCATTER_GGX | (abi.FLAG_GMON if a.gmon > 1 else 0)
     r.startRender(sc, tuple(a.size), a.spp, gmonBuckets=max(1, a.gmon), flags=flags, max_bounces=a.bounces, nonfinite_policy=abi.NONFINITE_ZERO)
     t1 = time.time()
@@ -103,6 +122,16 @@ def main():
         m = r.readbackExposureMeter()   # (no smoothing: the ev a read resolves now is the one the image above got)
         print(f"auto exposure: {m.metered} pixels metered ({m.below} below, {m.above} above, {m.nonfinite} non-finite), mean log2 luminance {m.mean_log2:.3f}, "
               f"applied {m.ev:+.3f} EV (gain {m.gain:.4g})")
+    for layer in dict.fromkeys(a.matte):
+        slots = r.readbackMatteSlots(abi.MATTE_INSTANCE if layer == "instance" else abi.MATTE_MATERIAL)
+        n = r.readbackSampleCounts()
+        path = os.path.splitext(a.output)[0] + "." + layer + ".png"
+        # (png.write_png shows x / (1 + x) to the power 1 / 2.2: handed the inverse, the colours come out as computed)
+        c = np.clip(matte_false_colour(slots, n), 0.0, 0.999) ** 2.2
+        png.write_png(path, c / (1.0 - c))
+        other = int((n.astype(np.int64) - slots["count"].sum(axis=-1)).sum())
+        print(f"matte: wrote {path}; {np.unique(slots['id'][slots['count'] != 0]).size} distinct {layer} ids, "
+              f"{other} of {int(n.sum())} samples beyond the {abi.MATTE_SLOTS} slots of their pixel")
     st = r.stats()
     print(f"setup {t1 - t0:.2f} s (BVH {st.bvh_build_ms:.1f} ms), render {t2 - t1:.3f} s = {a.size[0] * a.size[1] * a.spp * a.bounces / (t2 - t1) / 1e6:.0f} Msamples/s, wrote {a.output}")
     if a.adaptive is not None:
