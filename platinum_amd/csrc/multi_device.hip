@@ -1,7 +1,7 @@
 // multi_device.hip — the extern "C" entry points of include/ptamd.h and the DEVICE GROUP behind them.
 //
 // independent-sample parallelism.  pt_create with a device list builds one single-device renderer
-// (renderer.hip) per entry — scene, BVH and queues replicated per device — each driven by its own host thread on its own
+// (renderer.hip, display.hip) per entry — scene, BVH and queues replicated per device — each driven by its own host thread on its own
 // stream.  pt_start_render deals the render's sample indices [first, first + spp) to the members in contiguous ranges
 // (`frameIdx` is the only seed of the reference's sampler, samplers.metal:154-156, so the union over the members is exactly
 // the sample set of one big render); nothing is exchanged while rendering.  The merge happens when the image is asked for
@@ -442,6 +442,44 @@ pt_renderer* first_started(DeviceGroup* grp) {
   return nullptr;
 }
 
+// ---- the shapes the entry points below share: set on every member, ask the first started member, the member that displays ----
+
+// What every member holds (options, switches): a single device's setter, applied to each member of a group.
+template <typename... P, typename... A>
+int on_members(pt_renderer* r, int (*set)(pt_renderer*, P...), A... args) {
+  if (!is_group(r)) return set(r, args...);
+  for (auto* m : r->group->shards) { const int rc = set(m, args...); if (rc != PT_OK) return rc; }
+  return PT_OK;
+}
+
+// The same for a feature a group does not have: `enabled` is refused with `why`, before anything is stored.
+template <typename Options>
+int set_unless_enabled(pt_renderer* r, int (*set)(pt_renderer*, const Options*), const Options* o, const char* why) {
+  if (is_group(r) && !o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (is_group(r) && o->enabled) return fail(PT_ERR_UNSUPPORTED, why);
+  return on_members(r, set, o);
+}
+
+// What every member holds alike (scene tables, debug batches): a group answers with its first started member.
+template <typename R, typename... P, typename... A>
+int on_first_started(R* r, int (*fn)(R*, P...), A... args) {
+  if (!is_group(r)) return fn(r, args...);
+  pt_renderer* m = first_started(r->group);
+  return m ? fn(m, args...) : fail(PT_ERR_BAD_STATE, "no render started");
+}
+
+// The member that displays a group's image (display.hip): the group is waited for, which merges the members' accumulators on the first
+// device; the first started member must sit there.  `before_start`: the caller's own message.
+int displaying_member(pt_renderer* front, const char* before_start, pt_renderer** m) {
+  DeviceGroup* grp = front->group;
+  if (!grp->started) return fail(PT_ERR_BAD_STATE, before_start);
+  const int rc = group_wait(front);
+  if (rc != PT_OK) return rc;
+  *m = first_started(grp);
+  if (!*m || (*m)->device != grp->shards[0]->device) return fail(PT_ERR_BAD_STATE, "device group: no member on the first device has samples");
+  return PT_OK;
+}
+
 }  // namespace
 
 // ---- the C ABI (include/ptamd.h) ---------------------------------------------------------------------------------------
@@ -584,46 +622,29 @@ int pt_read_accumulator(pt_renderer* r, float* rgba_out) {
   return PT_OK;
 }
 
-int pt_set_post_options(pt_renderer* r, const pt_post_options* o) {
-  if (!is_group(r)) return dev_set_post_options(r, o);
-  for (auto* m : r->group->shards) { int rc = dev_set_post_options(m, o); if (rc != PT_OK) return rc; }
-  return PT_OK;
-}
+int pt_set_post_options(pt_renderer* r, const pt_post_options* o) { return on_members(r, dev_set_post_options, o); }
 
-int pt_set_tonemap_options(pt_renderer* r, const pt_tonemap_options* o) {
-  if (!is_group(r)) return dev_set_tonemap_options(r, o);
-  for (auto* m : r->group->shards) { int rc = dev_set_tonemap_options(m, o); if (rc != PT_OK) return rc; }
-  return PT_OK;
-}
+int pt_set_tonemap_options(pt_renderer* r, const pt_tonemap_options* o) { return on_members(r, dev_set_tonemap_options, o); }
 
 int pt_read_render_target(pt_renderer* r, uint8_t* rgba8_out) {
-  if (!is_group(r)) return dev_read_render_target(r, rgba8_out);
+  if (!is_group(r)) return dev_read_render_target(r, nullptr, rgba8_out);
   if (!rgba8_out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-  DeviceGroup* grp = r->group;
-  if (!grp->started) return fail(PT_ERR_BAD_STATE, "pt_read_render_target before pt_start_render");
-  int rc = group_wait(r);
-  if (rc != PT_OK) return rc;
-  pt_renderer* m = first_started(grp);
-  if (!m || m->device != grp->shards[0]->device) return fail(PT_ERR_BAD_STATE, "device group: no member on the first device has samples");
-  return dev_postprocess_to_host(m, grp->merged, rgba8_out);
+  pt_renderer* m;
+  if (const int rc = displaying_member(r, "pt_read_render_target before pt_start_render", &m)) return rc;
+  return dev_read_render_target(m, r->group->merged, rgba8_out);
 }
 
 int pt_present_render_target(pt_renderer* r, void** device_rgba8_out, void** stream_out) {
   if (!is_group(r)) return dev_present(r, nullptr, device_rgba8_out, stream_out);
-  DeviceGroup* grp = r->group;
-  if (!grp->started) return fail(PT_ERR_BAD_STATE, "pt_present_render_target before pt_start_render");
-  int rc = group_wait(r);  // merges the members' accumulators
-  if (rc != PT_OK) return rc;
-  pt_renderer* m = first_started(grp);
-  if (!m || m->device != grp->shards[0]->device) return fail(PT_ERR_BAD_STATE, "device group: no member on the first device has samples");
-  return dev_present(m, grp->merged, device_rgba8_out, stream_out);
+  pt_renderer* m;
+  if (const int rc = displaying_member(r, "pt_present_render_target before pt_start_render", &m)) return rc;
+  return dev_present(m, r->group->merged, device_rgba8_out, stream_out);
 }
 
 int pt_set_gmon_options(pt_renderer* r, const pt_gmon_options* o) {
-  if (!is_group(r)) return dev_set_gmon_options(r, o);
-  for (auto* m : r->group->shards) { int rc = dev_set_gmon_options(m, o); if (rc != PT_OK) return rc; }
-  r->group->dirty = true;
-  return PT_OK;
+  const int rc = on_members(r, dev_set_gmon_options, o);
+  if (rc == PT_OK && is_group(r)) r->group->dirty = true;   // the cap acts in the merge's resolve
+  return rc;
 }
 
 int pt_read_gmon_bucket(pt_renderer* r, uint32_t bucket, float* rgba_out) {
@@ -641,66 +662,37 @@ void* pt_accumulator_device_ptr(pt_renderer* r) {
 }
 
 int pt_get_constants(const pt_renderer* r, pt_constants* out) {
-  if (!is_group(r)) return dev_get_constants(r, out);
-  pt_renderer* m = first_started(r->group);
-  if (!m) return fail(PT_ERR_BAD_STATE, "no render started");
-  int rc = dev_get_constants(m, out);
-  if (rc == PT_OK) out->spp = r->group->params.spp;
+  const int rc = on_first_started(r, dev_get_constants, out);
+  if (rc == PT_OK && is_group(r)) out->spp = r->group->params.spp;   // (the member's is its share)
   return rc;
 }
 
 int pt_get_lights(const pt_renderer* r, pt_area_light* out, uint32_t capacity, uint32_t* count) {
-  if (!is_group(r)) return dev_get_lights(r, out, capacity, count);
-  pt_renderer* m = first_started(r->group);
-  return m ? dev_get_lights(m, out, capacity, count) : fail(PT_ERR_BAD_STATE, "no render started");
+  return on_first_started(r, dev_get_lights, out, capacity, count);
 }
 
 int pt_get_env_alias(const pt_renderer* r, pt_alias_entry* out, uint64_t capacity, uint64_t* count) {
-  if (!is_group(r)) return dev_get_env_alias(r, out, capacity, count);
-  pt_renderer* m = first_started(r->group);
-  return m ? dev_get_env_alias(m, out, capacity, count) : fail(PT_ERR_BAD_STATE, "no render started");
+  return on_first_started(r, dev_get_env_alias, out, capacity, count);
 }
 
-int pt_trace_primary(pt_renderer* r, uint32_t sample_idx, pt_hit_record* out) {
-  if (!is_group(r)) return dev_trace_primary(r, sample_idx, out);
-  pt_renderer* m = first_started(r->group);
-  return m ? dev_trace_primary(m, sample_idx, out) : fail(PT_ERR_BAD_STATE, "no render started");
-}
+int pt_trace_primary(pt_renderer* r, uint32_t sample_idx, pt_hit_record* out) { return on_first_started(r, dev_trace_primary, sample_idx, out); }
 
 int pt_debug_sample(pt_renderer* r, uint32_t sample_idx, float* radiance_out, int32_t* hits_out) {
-  if (!is_group(r)) return dev_debug_sample(r, sample_idx, radiance_out, hits_out);
-  pt_renderer* m = first_started(r->group);
-  return m ? dev_debug_sample(m, sample_idx, radiance_out, hits_out) : fail(PT_ERR_BAD_STATE, "no render started");
+  return on_first_started(r, dev_debug_sample, sample_idx, radiance_out, hits_out);
 }
 
-int pt_measure_traversal(pt_renderer* r, uint32_t sample_idx) {
-  if (!is_group(r)) return dev_measure_traversal(r, sample_idx);
-  pt_renderer* m = first_started(r->group);
-  return m ? dev_measure_traversal(m, sample_idx) : fail(PT_ERR_BAD_STATE, "no render started");
-}
+int pt_measure_traversal(pt_renderer* r, uint32_t sample_idx) { return on_first_started(r, dev_measure_traversal, sample_idx); }
 
-int pt_set_profiling(pt_renderer* r, int enabled) {
-  if (!is_group(r)) return dev_set_profiling(r, enabled);
-  for (auto* m : r->group->shards) { int rc = dev_set_profiling(m, enabled); if (rc != PT_OK) return rc; }
-  return PT_OK;
-}
+int pt_set_profiling(pt_renderer* r, int enabled) { return on_members(r, dev_set_profiling, enabled); }
 
 // AOVs are per device; a group would have to merge them (one more all-reduce of 12 floats per pixel), which is not implemented
 int pt_set_denoise_options(pt_renderer* r, const pt_denoise_options* o) {
-  if (!is_group(r)) return dev_set_denoise_options(r, o);
-  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-  if (o->enabled) return fail(PT_ERR_UNSUPPORTED, "pt_set_denoise_options: a device group does not keep AOVs");
-  for (auto* m : r->group->shards) { int rc = dev_set_denoise_options(m, o); if (rc != PT_OK) return rc; }
-  return PT_OK;
+  return set_unless_enabled(r, dev_set_denoise_options, o, "pt_set_denoise_options: a device group does not keep AOVs");
 }
 
 // the clamp is a stage of the denoiser, which a group does not run
 int pt_set_despeckle_options(pt_renderer* r, const pt_despeckle_options* o) {
-  if (!is_group(r)) return dev_set_despeckle_options(r, o);
-  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-  if (o->enabled) return fail(PT_ERR_UNSUPPORTED, "pt_set_despeckle_options: a device group does not run the denoiser");
-  for (auto* m : r->group->shards) { int rc = dev_set_despeckle_options(m, o); if (rc != PT_OK) return rc; }
-  return PT_OK;
+  return set_unless_enabled(r, dev_set_despeckle_options, o, "pt_set_despeckle_options: a device group does not run the denoiser");
 }
 
 int pt_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out) {
@@ -713,30 +705,18 @@ int pt_read_denoised(pt_renderer* r, float* rgba_out) {
   return fail(PT_ERR_BAD_STATE, "pt_read_denoised: a device group does not keep AOVs");
 }
 
-// Auto exposure: a group post-processes its merged image on the first device, through that member's shared tail, so the members all
-// hold the options and the member that post-processes holds the meter's state.
-int pt_set_exposure_options(pt_renderer* r, const pt_exposure_options* o) {
-  if (!is_group(r)) return dev_set_exposure_options(r, o);
-  for (auto* m : r->group->shards) { int rc = dev_set_exposure_options(m, o); if (rc != PT_OK) return rc; }
-  return PT_OK;
-}
+// Auto exposure: a group shows its merged image on the first device, through that member's display chain, so the members all hold the
+// options and the member that displays holds the meter's state.
+int pt_set_exposure_options(pt_renderer* r, const pt_exposure_options* o) { return on_members(r, dev_set_exposure_options, o); }
 
-int pt_reset_exposure(pt_renderer* r) {
-  if (!is_group(r)) return dev_reset_exposure(r);
-  for (auto* m : r->group->shards) { int rc = dev_reset_exposure(m); if (rc != PT_OK) return rc; }
-  return PT_OK;
-}
+int pt_reset_exposure(pt_renderer* r) { return on_members(r, dev_reset_exposure); }
 
 int pt_read_exposure_meter(pt_renderer* r, pt_exposure_meter* out) {
   if (!is_group(r)) return dev_read_exposure_meter(r, nullptr, out);
   if (!out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-  DeviceGroup* grp = r->group;
-  if (!grp->started) return fail(PT_ERR_BAD_STATE, "pt_read_exposure_meter before pt_start_render");
-  int rc = group_wait(r);
-  if (rc != PT_OK) return rc;
-  pt_renderer* m = first_started(grp);
-  if (!m || m->device != grp->shards[0]->device) return fail(PT_ERR_BAD_STATE, "device group: no member on the first device has samples");
-  return dev_read_exposure_meter(m, grp->merged, out);
+  pt_renderer* m;
+  if (const int rc = displaying_member(r, "pt_read_exposure_meter before pt_start_render", &m)) return rc;
+  return dev_read_exposure_meter(m, r->group->merged, out);
 }
 
 int pt_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const uint32_t* rect, const pt_exposure_options* options,
@@ -748,12 +728,8 @@ int pt_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const 
   return dev_debug_math(is_group(r) ? r->group->shards[0] : r, fn, n, a, b, out0, out1);
 }
 
-// Bloom: as auto exposure, every member holds the options and the member that post-processes the merged image does the work.
-int pt_set_bloom_options(pt_renderer* r, const pt_bloom_options* o) {
-  if (!is_group(r)) return dev_set_bloom_options(r, o);
-  for (auto* m : r->group->shards) { int rc = dev_set_bloom_options(m, o); if (rc != PT_OK) return rc; }
-  return PT_OK;
-}
+// Bloom: as auto exposure, every member holds the options and the member that displays the merged image does the work.
+int pt_set_bloom_options(pt_renderer* r, const pt_bloom_options* o) { return on_members(r, dev_set_bloom_options, o); }
 
 int pt_debug_bloom(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const pt_bloom_options* options, float* out, float* pyramid_out) {
   return dev_debug_bloom(is_group(r) ? r->group->shards[0] : r, rgba, width, height, options, out, pyramid_out);
@@ -761,20 +737,12 @@ int pt_debug_bloom(pt_renderer* r, const float* rgba, uint32_t width, uint32_t h
 
 // Adaptive sampling is per device: a group would have to agree on each tile's verdict across its members, which is not implemented
 int pt_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o) {
-  if (!is_group(r)) return dev_set_adaptive_options(r, o);
-  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-  if (o->enabled) return fail(PT_ERR_UNSUPPORTED, "pt_set_adaptive_options: a device group does not sample adaptively");
-  for (auto* m : r->group->shards) { int rc = dev_set_adaptive_options(m, o); if (rc != PT_OK) return rc; }
-  return PT_OK;
+  return set_unless_enabled(r, dev_set_adaptive_options, o, "pt_set_adaptive_options: a device group does not sample adaptively");
 }
 
 // A render region is per device too: the members' accumulators are merged over the whole frame
 int pt_set_render_region(pt_renderer* r, const pt_render_region* o) {
-  if (!is_group(r)) return dev_set_render_region(r, o);
-  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-  if (o->enabled) return fail(PT_ERR_UNSUPPORTED, "pt_set_render_region: a device group does not render regions");
-  for (auto* m : r->group->shards) { int rc = dev_set_render_region(m, o); if (rc != PT_OK) return rc; }
-  return PT_OK;
+  return set_unless_enabled(r, dev_set_render_region, o, "pt_set_render_region: a device group does not render regions");
 }
 
 // every member of a group builds its own lists of the same camera and scene: the first started member's are reported
@@ -803,11 +771,7 @@ int pt_read_sample_counts(pt_renderer* r, uint32_t* out) {
 
 // ID mattes are per device: slot lists in first-seen order do not merge by a sum, so a group does not keep them
 int pt_set_matte_options(pt_renderer* r, const pt_matte_options* o) {
-  if (!is_group(r)) return dev_set_matte_options(r, o);
-  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-  if (o->enabled) return fail(PT_ERR_UNSUPPORTED, "pt_set_matte_options: a device group does not keep ID mattes");
-  for (auto* m : r->group->shards) { int rc = dev_set_matte_options(m, o); if (rc != PT_OK) return rc; }
-  return PT_OK;
+  return set_unless_enabled(r, dev_set_matte_options, o, "pt_set_matte_options: a device group does not keep ID mattes");
 }
 
 int pt_read_matte_slots(pt_renderer* r, uint32_t layer, pt_matte_slot* out) {

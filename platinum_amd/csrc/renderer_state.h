@@ -1,5 +1,6 @@
-// renderer_state.h — private state of one `pt_renderer` (shared by renderer.hip: the single-device driver behind the C ABI,
-// and multi_device.hip: the device group that shards samples over several of them).
+// renderer_state.h — private state of one `pt_renderer`, shared by renderer.hip (the single-device driver of the path tracer),
+// display.hip (everything between an HDR image and the RGBA8 render target) and multi_device.hip (the C ABI, and the device group that
+// shards samples over several renderers).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -262,23 +263,24 @@ struct pt_renderer {
 };
 
 
-// ---- the single-device driver (renderer.hip); the extern "C" entry points (multi_device.hip) dispatch here or to the group ----
+
+
+// The extern "C" entry points (multi_device.hip) dispatch to the functions below or to the group.
+
+// ---- the driver (renderer.hip): start, batches, waits, and the reads of what the render itself produces ----
 int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out);
 void dev_destroy(pt_renderer* r);
 int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_render_params* p);
 // what a start refuses for its parameters alone, a device group's (own_streams: a caller stream cannot drive it) and a single device's alike
 int validate_start_params(const pt_scene_snapshot* scene, const pt_render_params* p, bool own_streams);
 int dev_render_step(pt_renderer* r, uint32_t max_spp);
+// enqueues the samples accepted but pending; `all`: every one of them now; `sync_checkpoints`: wait for each adaptive checkpoint enqueued
+int flush_pending(pt_renderer* r, bool all, bool sync_checkpoints = false);
 int dev_wait(pt_renderer* r);
 int dev_status(const pt_renderer* r);
 int dev_progress(const pt_renderer* r, uint64_t* accumulated, uint64_t* total);
 uint64_t dev_render_time_ms(const pt_renderer* r);
 int dev_read_accumulator(pt_renderer* r, float* rgba_out);
-int dev_set_post_options(pt_renderer* r, const pt_post_options* o);
-int dev_set_tonemap_options(pt_renderer* r, const pt_tonemap_options* o);
-int dev_read_render_target(pt_renderer* r, uint8_t* rgba8_out);
-int dev_postprocess_to_host(pt_renderer* r, const vec4* acc_device, uint8_t* rgba8_out);  // the tail of read_render_target on a given image
-int dev_present(pt_renderer* r, const vec4* acc_device, void** device_rgba8_out, void** stream_out);  // enqueue only; acc_device NULL = own accumulator
 int dev_set_gmon_options(pt_renderer* r, const pt_gmon_options* o);
 int dev_read_gmon_bucket(pt_renderer* r, uint32_t bucket, float* rgba_out);
 void* dev_accumulator_device_ptr(pt_renderer* r);
@@ -290,18 +292,8 @@ int dev_debug_sample(pt_renderer* r, uint32_t sample_idx, float* radiance_out, i
 int dev_measure_traversal(pt_renderer* r, uint32_t sample_idx);
 int dev_set_profiling(pt_renderer* r, int enabled);
 int dev_get_stats(pt_renderer* r, pt_stats* out);
-int dev_set_denoise_options(pt_renderer* r, const pt_denoise_options* o);
 int dev_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out);
-int dev_read_denoised(pt_renderer* r, float* rgba_out);
-int dev_set_despeckle_options(pt_renderer* r, const pt_despeckle_options* o);
-int dev_set_exposure_options(pt_renderer* r, const pt_exposure_options* o);
-int dev_reset_exposure(pt_renderer* r);
-int dev_read_exposure_meter(pt_renderer* r, const vec4* acc_device, pt_exposure_meter* out);  // acc_device NULL = what dev_read_render_target shows
 int dev_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const void* b, void* out0, void* out1);
-int dev_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const uint32_t* rect, const pt_exposure_options* options,
-                       pt_exposure_meter* out, float* scaled_out);
-int dev_set_bloom_options(pt_renderer* r, const pt_bloom_options* o);
-int dev_debug_bloom(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const pt_bloom_options* options, float* out, float* pyramid_out);
 int dev_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o);
 int dev_read_sample_counts(pt_renderer* r, uint32_t* out);
 int dev_set_render_region(pt_renderer* r, const pt_render_region* o);
@@ -310,3 +302,20 @@ int dev_set_matte_options(pt_renderer* r, const pt_matte_options* o);
 int dev_read_matte_slots(pt_renderer* r, uint32_t layer, pt_matte_slot* out);
 int dev_read_matte(pt_renderer* r, uint32_t layer, const uint32_t* ids, uint32_t id_count, float* coverage_out);
 int dev_pick(pt_renderer* r, uint32_t x, uint32_t y, pt_pick_result* out);
+
+// ---- display (display.hip): the stages' options, and the chain from an HDR image to the RGBA8 target.  `merged`: a device group's merged
+//      image on this renderer's device, which the group has waited for; NULL = the renderer's own image ----
+int dev_set_post_options(pt_renderer* r, const pt_post_options* o);
+int dev_set_tonemap_options(pt_renderer* r, const pt_tonemap_options* o);
+int dev_set_denoise_options(pt_renderer* r, const pt_denoise_options* o);
+int dev_set_despeckle_options(pt_renderer* r, const pt_despeckle_options* o);
+int dev_set_exposure_options(pt_renderer* r, const pt_exposure_options* o);
+int dev_reset_exposure(pt_renderer* r);
+int dev_set_bloom_options(pt_renderer* r, const pt_bloom_options* o);
+int dev_read_denoised(pt_renderer* r, float* rgba_out);
+int dev_read_render_target(pt_renderer* r, const vec4* merged, uint8_t* rgba8_out);                // blocks
+int dev_present(pt_renderer* r, const vec4* merged, void** device_rgba8_out, void** stream_out);  // enqueues only
+int dev_read_exposure_meter(pt_renderer* r, const vec4* merged, pt_exposure_meter* out);           // blocks; what a target read would meter now
+int dev_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const uint32_t* rect, const pt_exposure_options* options,
+                       pt_exposure_meter* out, float* scaled_out);
+int dev_debug_bloom(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const pt_bloom_options* options, float* out, float* pyramid_out);
