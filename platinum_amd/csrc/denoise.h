@@ -9,14 +9,10 @@ namespace pt {
 
 // After k_trace_closest(bounce 0) of a batch: the first-hit AOVs of every camera ray -> Abuf (2 vec4 per pid, pid = the Lbuf index).
 void launch_aov(hipStream_t s, uint32_t grid, const DeviceScene* S_device, PathState st, const vec4* hit, Segments seg, vec4* Abuf);
-// After k_accumulate / k_gmon: Abuf and Lbuf of the batch folded into the three AOV images (n0 samples already in them).
+// After k_accumulate / k_gmon: Abuf and Lbuf of the batch folded into the three AOV images (n0 samples already in them); over `tiles`
+// (kernels.h TileSet: Abuf and Lbuf dense over virtual tiles) or, when null, over the whole frame.
 void launch_accumulate_aov(hipStream_t s, vec4* albedo, vec4* normal, vec4* moments, const vec4* Abuf, const vec4* Lbuf, uint32_t width,
-                           uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy);
-// The same over the active tiles of an adaptive or region render (kernels.h launch_raygen_adaptive: Abuf and Lbuf dense over virtual tiles;
-// max_active and rect as launch_accumulate_adaptive).
-void launch_accumulate_aov_adaptive(hipStream_t s, vec4* albedo, vec4* normal, vec4* moments, const vec4* Abuf, const vec4* Lbuf, uint32_t width,
-                                    uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy, const uint32_t* active,
-                                    const uint32_t* active_count, uint32_t max_active, const Rect& rect);
+                           uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy, const TileSet* tiles);
 // The filter over the rectangle `rect` of the current W x H image, as if the rectangle were the whole image (the whole frame: {0, 0, W, H}):
 // prep, `iterations` a-trous steps, the last one remodulated into `out` (W*H vec4; pixels outside rect are left as they are).
 // guide / aux / col0 / col1 are W*H vec4 of scratch each; nsamples = samples folded into the AOVs, or, with tile_n (an adaptive render),

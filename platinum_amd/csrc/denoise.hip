@@ -15,26 +15,22 @@
 
 #include "denoise.h"
 #include "pt_denoise.h"
+#include "pt_tilefold.h"
 
 namespace pt {
 
-// ---- k_aov: the bounce-0 queue (state buffer 0) -> Abuf.  Reads the queue only. ----------------------------------------------------
+// ---- k_aov: the bounce-0 queue (pt_tilefold.h walk_bounce0) -> Abuf.  Reads the queue only. ----------------------------------------
 // Abuf[2 * pid] = {albedo, t}, Abuf[2 * pid + 1] = {normal, 1} for a hit; {1, 1, 1, 0}, {0, 0, 0, 0} for a miss.
 __global__ void __launch_bounds__(256) k_aov(const DeviceScene* __restrict__ Sp, PathState st, const vec4* __restrict__ hit, Segments seg,
                                              vec4* __restrict__ Abuf) {
   const DeviceScene& S = *Sp;
-  const uint32_t lane = wave_lane();
-  const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = gridDim.x * (blockDim.x >> 6);
-  for (uint32_t sg = wave; sg < seg.nseg; sg += nwaves) {
-    const uint32_t n = seg.active[0][sg];
-    const uint32_t base = segment_lbuf_base(seg, sg);
-    for (uint32_t k = lane; k < n; k += 64) {
-      const uint32_t i = seg_slot(seg.nseg, sg, k);
+  const uint32_t lane = wave_lane(), wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = gridDim.x * (blockDim.x >> 6);
+  for (uint32_t sg = wave; sg < seg.nseg; sg += nwaves)
+    walk_bounce0(seg, st, hit, sg, lane, [&](uint32_t i, uint32_t pid, uint32_t hw) {
       const vec4 h4 = hit[i], d4 = st.rayD[i];
-      const uint32_t pid = base + (f2u(d4.w) >> kMetaPidShift);
       AovSample a = aov_miss();
       float hf = 0.0f;
-      if (f2u(h4.w) != kInvalidRef) {
+      if (!hit_word_miss(hw)) {
         const vec4 o4 = st.rayO[i];
         ShadeIn in;
         in.o = v3(o4.x, o4.y, o4.z);
@@ -45,58 +41,44 @@ __global__ void __launch_bounds__(256) k_aov(const DeviceScene* __restrict__ Sp,
         in.lastSpecular = false;
         in.offset = 0; in.dim = 0; in.bounce = 0;
         in.t = h4.x; in.u = h4.y; in.v = h4.z;
-        in.tri = f2u(h4.w) & kHitTriMask;
+        in.tri = hit_word_tri(hw);
         a = stage_aov(S, in);
         hf = 1.0f;
       }
       Abuf[2u * pid] = vec4{a.albedo.x, a.albedo.y, a.albedo.z, a.t};
       Abuf[2u * pid + 1u] = vec4{a.normal.x, a.normal.y, a.normal.z, hf};
-    }
-  }
+    });
 }
 
-// ---- k_accumulate_aov: one wave per 8x8 tile, k_accumulate's layout ---------------------------------------------------------------
-// Eight samples of the tile's 64 pixels are staged through LDS per round for each of the three streams (Lbuf and the two halves of
-// Abuf), fully coalesced; every lane then folds the eight samples of its pixel in sample order.  One wave per block: the three
-// staging areas take 27 KB.
-// ADAPTIVE (k_accumulate_aov_adaptive, tile-adaptive sampling): block v folds virtual tile v < *active_count into image tile active[v]
-// (kernels.hip k_accumulate_adaptive); Abuf and Lbuf are dense over virtual tiles.  It folds the pixels inside `rect`.
+// ---- k_accumulate_aov: one wave per 8x8 tile (pt_tilefold.h fold_tile / fold_stage) -----------------------------------------------
+// A round stages three streams (Lbuf and the two halves of Abuf); every lane then folds the samples of its pixel in sample order.  One
+// wave per block: the three staging areas take 27 KB.  ADAPTIVE: k_accumulate_aov_adaptive.
 template <bool ADAPTIVE>
 __device__ __forceinline__ void accumulate_aov_body(vec4* __restrict__ albedo, vec4* __restrict__ normal, vec4* __restrict__ moments,
                                                     const vec4* __restrict__ Abuf, const vec4* __restrict__ Lbuf, uint32_t width,
                                                     uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy,
                                                     const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count, Rect rect) {
-  constexpr uint32_t kRow = 9;
-  __shared__ vec4 stage[3][64 * kRow];
+  __shared__ vec4 stage[3][64 * kFoldRow];
   const uint32_t lane = wave_lane();
-  const uint32_t tilesX = tiles_x(width), tiles = ADAPTIVE ? *active_count : tilesX * tiles_y(height);
-  const uint32_t tile = blockIdx.x;
-  const bool live = tile < tiles;
-  const uint32_t itile = ADAPTIVE ? (live ? active[tile] : 0u) : tile;   // the image tile
-  const PixelXY q = tile_pixel(itile, lane, tilesX);
-  const bool inside = live && (ADAPTIVE ? rect_contains(rect, q.x, q.y) : q.x < width && q.y < height);
-  const size_t p = (size_t)q.y * width + q.x;
+  const FoldTile t = fold_tile<ADAPTIVE>(blockIdx.x, lane, width, height, active, active_count, rect);
+  const bool live = t.live, inside = t.inside;
+  const size_t p = (size_t)t.q.y * width + t.q.x;
   vec4 A = inside ? albedo[p] : vec4{0, 0, 0, 0}, N = inside ? normal[p] : vec4{0, 0, 0, 0}, M = inside ? moments[p] : vec4{0, 0, 0, 0};
   for (uint32_t s0 = 0; s0 < nsamples; s0 += 8u) {
     const uint32_t nb = nsamples - s0 < 8u ? nsamples - s0 : 8u;
     __syncthreads();
-    if (live) {
-#pragma unroll
-      for (uint32_t i = 0; i < 8u; i++) {
-        const uint32_t px = i * 8u + (lane >> 3), j = lane & 7u;   // (the staging order, as k_accumulate)
-        if (j < nb) {
-          const uint32_t pid = lbuf_index(tile, s0 + j, nsamples, px);
-          stage[0][px * kRow + j] = Lbuf[pid];
-          stage[1][px * kRow + j] = Abuf[2u * pid];
-          stage[2][px * kRow + j] = Abuf[2u * pid + 1u];
-        }
-      }
-    }
+    if (live)
+      fold_stage(t.tile, lane, s0, nb, nsamples, [&](uint32_t pid, uint32_t slot) {
+        stage[0][slot] = Lbuf[pid];
+        stage[1][slot] = Abuf[2u * pid];
+        stage[2][slot] = Abuf[2u * pid + 1u];
+      });
     __syncthreads();
     if (inside) {
       for (uint32_t j = 0; j < nb; j++) {
-        const vec4 l4 = stage[0][lane * kRow + j], a4 = stage[1][lane * kRow + j], n4 = stage[2][lane * kRow + j];
+        const vec4 l4 = stage[0][lane * kFoldRow + j], a4 = stage[1][lane * kFoldRow + j], n4 = stage[2][lane * kFoldRow + j];
         vec3 L = v3(l4.x, l4.y, l4.z);
+        // (not_finite(L), pt_shade.h, written out: behind the call the test compiles branch-free here, a kernel 44 bytes shorter and not the parent's)
         if (!(fabsf(L.x) <= 3.0e38f && fabsf(L.y) <= 3.0e38f && fabsf(L.z) <= 3.0e38f) && nonfinite_policy == PT_NONFINITE_ZERO) L = v3(0.0f);
         const float lum = dn_lum(L);
         const uint32_t n = n0 + s0 + j;
@@ -174,18 +156,14 @@ void launch_aov(hipStream_t s, uint32_t grid, const DeviceScene* S_device, PathS
 }
 
 void launch_accumulate_aov(hipStream_t s, vec4* albedo, vec4* normal, vec4* moments, const vec4* Abuf, const vec4* Lbuf, uint32_t width,
-                           uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy) {
-  const uint32_t tiles = tile_count(width, height);
-  hipLaunchKernelGGL(k_accumulate_aov, dim3(tiles), dim3(64), 0, s, albedo, normal, moments, Abuf, Lbuf, width, height, nsamples, n0,
-                     nonfinite_policy);
-}
-
-void launch_accumulate_aov_adaptive(hipStream_t s, vec4* albedo, vec4* normal, vec4* moments, const vec4* Abuf, const vec4* Lbuf, uint32_t width,
-                                    uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy, const uint32_t* active,
-                                    const uint32_t* active_count, uint32_t max_active, const Rect& rect) {
-  // one block per tile that may still be active
-  hipLaunchKernelGGL(k_accumulate_aov_adaptive, dim3(max_active), dim3(64), 0, s, albedo, normal, moments, Abuf, Lbuf, width, height, nsamples, n0,
-                     nonfinite_policy, active, active_count, rect);
+                           uint32_t height, uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy, const TileSet* tiles) {
+  // one block per tile of the image, or per tile that may still be active
+  if (tiles)
+    hipLaunchKernelGGL(k_accumulate_aov_adaptive, dim3(tiles->max_active), dim3(64), 0, s, albedo, normal, moments, Abuf, Lbuf, width, height, nsamples,
+                       n0, nonfinite_policy, tiles->active, tiles->active_count, tiles->rect);
+  else
+    hipLaunchKernelGGL(k_accumulate_aov, dim3(tile_count(width, height)), dim3(64), 0, s, albedo, normal, moments, Abuf, Lbuf, width, height, nsamples,
+                       n0, nonfinite_policy);
 }
 
 void launch_denoise(hipStream_t s, const vec4* acc, const vec4* albedo, const vec4* normal, const vec4* moments, uint32_t W, uint32_t H,

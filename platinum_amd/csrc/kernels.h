@@ -35,15 +35,18 @@ struct Segments {
 };
 PT_HD uint32_t segment_first_tile(const Segments& seg, uint32_t sg) { return segment_first_tile(seg.nseg, seg.bands, seg.tiles_per_seg, sg); }
 PT_HD uint32_t segment_lbuf_base(const Segments& seg, uint32_t sg) { return segment_lbuf_base(seg.nseg, seg.bands, seg.tiles_per_seg, seg.nsamples, sg); }
-// lane of the wave (wave64)
+// lane of the wave (wave64); physical wave id / count of the launch (blockDim.x is a multiple of 64)
 __device__ __forceinline__ uint32_t wave_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+__device__ __forceinline__ uint32_t wave_index() { return blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); }
+__device__ __forceinline__ uint32_t wave_count() { return gridDim.x * (blockDim.x >> 6); }
+
+// The tiles a batch of an adaptive or region render covers (pt_renderer::tile_set): virtual tile v < *active_count is image tile active[v],
+// only the pixels inside `rect` are sampled and folded; max_active >= *active_count (the first list's length) sizes a fold kernel's grid.
+// A launcher that takes a `const TileSet*` runs the full-frame kernel when it is null, else the _adaptive one (pt_tilefold.h fold_tile<true>).
+struct TileSet { const uint32_t* active; const uint32_t* active_count; uint32_t max_active; Rect rect; };
 
 void launch_raygen(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState st, vec4* Lbuf, Segments seg, BatchCounters* ctr,
-                   uint32_t first_sample, uint32_t nsamples);
-// Tile-adaptive sampling and render regions: k_raygen over the virtual tiles 0 .. *active_count - 1, virtual tile v being image tile
-// active[v]; only the pixels inside `rect` start a path.
-void launch_raygen_adaptive(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState st, vec4* Lbuf, Segments seg,
-                            uint32_t first_sample, uint32_t nsamples, const Rect& rect, const uint32_t* active, const uint32_t* active_count);
+                   uint32_t first_sample, uint32_t nsamples, const TileSet* tiles);
 // After a producer: list the non-empty chunks of the closest-hit queue (state buffer `cur`, consumed at bounce
 // `bounce_closest`) and, if do_shadow, of the shadow queue consumed at `bounce_shadow`.
 void launch_chunk_tables(hipStream_t s, Segments seg, uint32_t cur, BatchCounters* ctr, uint32_t bounce_closest,
@@ -72,14 +75,10 @@ void launch_shade(hipStream_t s, uint32_t grid, const DeviceScene* S_device, Pat
                   ShadowQueue sq, vec4* Lbuf, Segments seg, uint32_t cur, BatchCounters* ctr, uint32_t bounce);
 void launch_trace_shadow(hipStream_t s, uint32_t grid, const DeviceScene& S, ShadowQueue sq, vec4* Lbuf, Segments seg,
                          BatchCounters* ctr, uint32_t bounce, uint32_t* spill, bool count);
+// Over a tile set it also folds the per-pixel running means of (lum, lum^2) into `mom` (unless null) and writes n0 + nsamples to
+// tile_n[image tile]; a full-frame batch reads neither.
 void launch_accumulate(hipStream_t s, vec4* acc, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
-                       uint32_t nonfinite_policy, BatchCounters* ctr);
-// k_accumulate over the active tiles (the virtual tiles of launch_raygen_adaptive); also folds the per-pixel running means of (lum, lum^2)
-// into `mom` (unless null) and writes n0 + nsamples to tile_n[image tile].  max_active: an upper bound of *active_count (the first list's
-// length); only the pixels inside `rect` are folded.
-void launch_accumulate_adaptive(hipStream_t s, vec4* acc, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
-                                uint32_t nonfinite_policy, BatchCounters* ctr, const uint32_t* active, const uint32_t* active_count,
-                                uint32_t max_active, vec2* mom, uint32_t* tile_n, const Rect& rect);
+                       uint32_t nonfinite_policy, BatchCounters* ctr, const TileSet* tiles, vec2* mom, uint32_t* tile_n);
 void launch_accumulate_gmon(hipStream_t s, vec4* buckets, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
                             uint32_t samples_per_bucket, uint32_t gmon_buckets, uint32_t bucket_base, uint32_t nonfinite_policy, BatchCounters* ctr);
 // out[p] = (first ? 0 : out[p]) + w * in[p]  — merging the accumulators of a device group's members (alpha is set to 1 by the last call)

@@ -32,6 +32,7 @@
 #include "pt_denoise.h"
 #include "pt_post.h"
 #include "pt_shade.h"
+#include "pt_tilefold.h"
 #include "queue_plan.h"
 
 namespace pt {
@@ -51,7 +52,7 @@ __device__ __forceinline__ void st_stream(vec4* p, vec4 v) {
 }
 __device__ __forceinline__ void st_stream(uint32_t* p, uint32_t v) { __builtin_nontemporal_store(v, p); }
 
-// ---- wave helpers (wave64; wave_lane is in kernels.h) --------------------------------------------------------------
+// ---- wave helpers (wave64; wave_lane, wave_index and wave_count are in kernels.h) ------------------------------------
 __device__ __forceinline__ uint32_t wave_prefix(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
@@ -59,9 +60,6 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
-// physical wave id / count of the launch (blockDim.x is a multiple of 64)
-__device__ __forceinline__ uint32_t wave_index() { return blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); }
-__device__ __forceinline__ uint32_t wave_count() { return gridDim.x * (blockDim.x >> 6); }
 #ifdef PT_TAIL_PROBE
 #define PT_TAIL_BEGIN const unsigned long long tail_t0 = wall_clock64(); unsigned long long tail_take = 0, tail_setup = 0, tail_ta = 0;
 #define PT_TAIL_T(acc) { const unsigned long long tb_ = wall_clock64(); acc += tb_ - tail_ta; tail_ta = tb_; }
@@ -431,7 +429,7 @@ __device__ __forceinline__ void trace_closest_body(const DeviceScene& S, PathSta
     if (ts.dbg) printf("dbg finish: t %.9g u %.9g v %.9g tri %u gid %u\n", h.t, h.u, h.v, h.tri, h.gid >> 2);
     ts.dbg = false;
 #endif
-    hit[ray] = vec4{h.t, h.u, h.v, u2f(h.tri == kInvalidRef ? kInvalidRef : (h.tri | ((h.gid & 3u) << 28)))};
+    hit[ray] = vec4{h.t, h.u, h.v, u2f(hit_word(h))};
     if (hitlog) {
       // (the hit log is only kept for one-sample batches)
       const uint32_t pixel = pixel_of_pid_1spp(segment_lbuf_base(seg, slot_segment(seg.nseg, ray)) + (f2u(st.rayD[ray].w) >> kMetaPidShift), S.width);
@@ -523,7 +521,7 @@ k_trace_camera(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments seg
         (void)trav_init(S, ts, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), 1e-3f, kInf, ir, TraversalStack{}, false, nullptr);   // (lists exist only over a tree whose root is a node)
         cam_trace_ray(S, ts, nodes, cl.entries + (size_t)q * cl.cap, len);   // (pt_camlist.h: shared with k_camera_primary and tests/emu)
         const RayHit& h = ts.best;
-        hit[ray] = vec4{h.t, h.u, h.v, u2f(h.tri == kInvalidRef ? kInvalidRef : (h.tri | ((h.gid & 3u) << 28)))};
+        hit[ray] = vec4{h.t, h.u, h.v, u2f(hit_word(h))};
       }
     }
   }
@@ -665,7 +663,7 @@ k_camera_primary(DeviceScene S, PathState st, vec4* __restrict__ Lbuf, vec4* __r
         cam_trace_wave(S, ts, valid, nodes, cl_entries + (size_t)qs * cl_cap, len);
         if (valid) {
           const RayHit& h = ts.best;
-          hit[j] = vec4{h.t, h.u, h.v, u2f(h.tri == kInvalidRef ? kInvalidRef : (h.tri | ((h.gid & 3u) << 28)))};
+          hit[j] = vec4{h.t, h.u, h.v, u2f(hit_word(h))};
         }
       } else if (valid) {
         const uint32_t qs = tile * 64u + pl;
@@ -677,7 +675,7 @@ k_camera_primary(DeviceScene S, PathState st, vec4* __restrict__ Lbuf, vec4* __r
           (void)trav_init(S, ts, rg.o, rg.d, 1e-3f, kInf, ir, TraversalStack{}, false, nullptr);
           cam_trace_ray(S, ts, nodes, cl_entries + (size_t)qs * cl_cap, len);
           const RayHit& h = ts.best;
-          hit[j] = vec4{h.t, h.u, h.v, u2f(h.tri == kInvalidRef ? kInvalidRef : (h.tri | ((h.gid & 3u) << 28)))};
+          hit[j] = vec4{h.t, h.u, h.v, u2f(hit_word(h))};
         }
       }
     }
@@ -784,15 +782,15 @@ k_shade(const DeviceScene* __restrict__ Sp, PathState sin, PathState sout, const
         uint32_t w = 0;
         if (k < n) {
           w = f2u(hit[seg_slot(seg.nseg, sg, k)].w);
-          cls = w == kInvalidRef ? 4u : (w >> 28) & 3u;
+          cls = hit_word_miss(w) ? 4u : hit_word_class(w);
           // a miss without an environment adds attenuation * backgroundColor = attenuation * 0 (kernel.metal:311 / :541, defs.metal:21):
           // nothing — unless the BSDF has driven the throughput to an infinity or a NaN (a zero pdf), when the reference's sum turns NaN
           // (one in ~1e8 paths: the segment's flag says whether the throughputs of its misses have to be looked at at all)
-          if (w == kInvalidRef && S.env_texture < 0) {
+          if (hit_word_miss(w) && S.env_texture < 0) {
             if (!seg_poisoned) cls = 5u;
             else {
               const vec4 a4 = sin.att[seg_slot(seg.nseg, sg, k)];
-              if (!att_poisoned(v3(a4.x, a4.y, a4.z))) cls = 5u;
+              if (!not_finite(v3(a4.x, a4.y, a4.z))) cls = 5u;
             }
           }
         }
@@ -802,7 +800,7 @@ k_shade(const DeviceScene* __restrict__ Sp, PathState sin, PathState sout, const
           const uint32_t at = cls == 0 ? cnt0 + wave_prefix(m0) : cls == 1 ? cnt1 + wave_prefix(m1) : cls == 2 ? cnt2 + wave_prefix(m2)
                             : cls == 3 ? cnt3 + wave_prefix(m3) : cnt4 + wave_prefix(m4);
           bin[cls * kBinCap + at] = (uint16_t)k;
-          bin_tri[cls * kBinCap + at] = w & kHitTriMask;
+          bin_tri[cls * kBinCap + at] = hit_word_tri(w);
         }
         cnt0 += (uint32_t)__popcll(m0); cnt1 += (uint32_t)__popcll(m1); cnt2 += (uint32_t)__popcll(m2);
         cnt3 += (uint32_t)__popcll(m3); cnt4 += (uint32_t)__popcll(m4);
@@ -898,7 +896,7 @@ k_shade(const DeviceScene* __restrict__ Sp, PathState sin, PathState sout, const
           Lbuf[pid] = L;
         }
         const unsigned long long m = __ballot(bo.alive);
-        poisoned_now |= __ballot(bo.alive && att_poisoned(bo.next_att));
+        poisoned_now |= __ballot(bo.alive && not_finite(bo.next_att));
         if (bo.alive) {
           const uint32_t j = seg_slot(seg.nseg, sg, n_out + wave_prefix(m));
           st_stream(&sout.rayO[j], vec4{g.hitPos.x, g.hitPos.y, g.hitPos.z, bo.next_pdf});
@@ -1007,27 +1005,20 @@ k_trace_shadow(DeviceScene S, ShadowQueue sq, vec4* __restrict__ Lbuf, Segments 
 }
 
 // ---- accumulate (kernel.metal:672-684): running mean, one sample at a time, in sample order --------------------------
-// One wave per 8x8 tile.  A tile's entries of Lbuf are [pixel][sample]: eight samples of eight pixels are 8 x 128 contiguous bytes, so the
-// wave loads blocks of 64 pixels x 8 samples fully coalesced (eight lanes per 128-byte line), turns them through LDS, and every lane then
-// folds the eight samples of ITS pixel in sample order — the running mean is a sequential recurrence per pixel (kernel.metal:672-684).
-// ADAPTIVE (k_accumulate_adaptive): wave w folds virtual tile w < *active_count into image tile active[w], and also folds the running means
-// of (lum, lum^2) into `mom` with aov_fold / dn_lum (the bits of PT_AOV_MOMENTS .g / .b) and sets the tile's sample count.  It folds the
-// pixels inside `rect` (the whole frame or the render region, as k_raygen_adaptive); `mom` is null when no checkpoint will read it.
+// One wave per 8x8 tile (pt_tilefold.h: fold_tile places it, fold_stage turns eight samples of its 64 pixels through LDS per round); every
+// lane then folds the samples of ITS pixel in sample order — the running mean is a sequential recurrence per pixel (kernel.metal:672-684).
+// ADAPTIVE (k_accumulate_adaptive) also folds the running means of (lum, lum^2) into `mom` with aov_fold / dn_lum (the bits of
+// PT_AOV_MOMENTS .g / .b) and sets the tile's sample count; `mom` is null when no checkpoint will read it.
 template <bool ADAPTIVE>
 __device__ __forceinline__ void accumulate_body(vec4* __restrict__ acc, const vec4* __restrict__ Lbuf, uint32_t npixels, uint32_t width,
                                                 uint32_t nsamples, uint32_t n0, uint32_t nonfinite_policy, BatchCounters* __restrict__ ctr,
                                                 const uint32_t* __restrict__ active, const uint32_t* __restrict__ active_count,
                                                 vec2* __restrict__ mom, uint32_t* __restrict__ tile_n, Rect rect) {
-  constexpr uint32_t kRow = 9;  // vec4 per pixel row in LDS (8 samples + 1 of padding against bank conflicts)
-  __shared__ vec4 stage[kBlock / 64][64 * kRow];
-  const uint32_t lane = wave_lane(), w = threadIdx.x >> 6;
-  const uint32_t height = npixels / width, tilesX = tiles_x(width), tiles = ADAPTIVE ? *active_count : tilesX * tiles_y(height);
-  const uint32_t tile = blockIdx.x * (kBlock / 64) + w;   // (every wave of the block runs the same number of rounds: the barriers are uniform)
-  const bool live = tile < tiles;
-  const uint32_t itile = ADAPTIVE ? (live ? active[tile] : 0u) : tile;   // the image tile
-  const PixelXY q = tile_pixel(itile, lane, tilesX);
-  const bool inside = live && (ADAPTIVE ? rect_contains(rect, q.x, q.y) : q.x < width && q.y < height);
-  const uint32_t p = q.y * width + q.x;
+  __shared__ vec4 stage[kBlock / 64][64 * kFoldRow];
+  const uint32_t lane = wave_lane(), w = threadIdx.x >> 6;   // (every wave of the block runs the same number of rounds: uniform barriers)
+  const FoldTile t = fold_tile<ADAPTIVE>(blockIdx.x * (kBlock / 64) + w, lane, width, npixels / width, active, active_count, rect);
+  const bool live = t.live, inside = t.inside;
+  const uint32_t p = t.q.y * width + t.q.x;
   vec4 a = inside ? acc[p] : vec4{0.0f, 0.0f, 0.0f, 0.0f};
   vec2 m = ADAPTIVE && inside && mom ? mom[p] : vec2{0.0f, 0.0f};
   for (uint32_t s0 = 0; s0 < nsamples; s0 += 8u) {
@@ -1035,17 +1026,17 @@ __device__ __forceinline__ void accumulate_body(vec4* __restrict__ acc, const ve
     __syncthreads();
     if (live) {
 #pragma unroll
-      for (uint32_t i = 0; i < 8u; i++) {
-        const uint32_t px = i * 8u + (lane >> 3), j = lane & 7u;   // (the staging order: eight lanes per pixel, one per sample)
-        if (j < nb) stage[w][px * kRow + j] = ld_stream(&Lbuf[lbuf_index(tile, s0 + j, nsamples, px)]);
+      for (uint32_t i = 0; i < 8u; i++) {   // fold_stage, written out: through the call this kernel takes 6 more VGPRs (one LDS address per step)
+        const uint32_t px = i * 8u + (lane >> 3), j = lane & 7u;
+        if (j < nb) stage[w][px * kFoldRow + j] = ld_stream(&Lbuf[lbuf_index(t.tile, s0 + j, nsamples, px)]);
       }
     }
     __syncthreads();
     if (inside) {
       for (uint32_t j = 0; j < nb; j++) {
-        const vec4 v = stage[w][lane * kRow + j];
+        const vec4 v = stage[w][lane * kFoldRow + j];
         vec3 L = v3(v.x, v.y, v.z);
-        if (!(fabsf(L.x) <= 3.0e38f && fabsf(L.y) <= 3.0e38f && fabsf(L.z) <= 3.0e38f)) {  // NaN or inf
+        if (not_finite(L)) {
           atomicAdd(&ctr->nonfinite, 1u);
           if (nonfinite_policy == PT_NONFINITE_ZERO) L = v3(0.0f);
         }
@@ -1065,7 +1056,7 @@ __device__ __forceinline__ void accumulate_body(vec4* __restrict__ acc, const ve
   if (inside) acc[p] = a;
   if (ADAPTIVE) {
     if (inside && mom) mom[p] = m;
-    if (live && lane == 0) tile_n[itile] = n0 + nsamples;
+    if (live && lane == 0) tile_n[t.itile] = n0 + nsamples;
   }
 }
 
@@ -1106,7 +1097,7 @@ __global__ void __launch_bounds__(kBlock) k_accumulate_gmon(vec4* __restrict__ b
 #pragma unroll
     for (uint32_t j = 1; j < kGroup; j++) if (s % kGroup == j) L4 = v[j];
     vec3 L = v3(L4.x, L4.y, L4.z);
-    if (!(fabsf(L.x) <= 3.0e38f && fabsf(L.y) <= 3.0e38f && fabsf(L.z) <= 3.0e38f)) {
+    if (not_finite(L)) {
       atomicAdd(&ctr->nonfinite, 1u);
       if (nonfinite_policy == PT_NONFINITE_ZERO) L = v3(0.0f);
     }
@@ -1234,11 +1225,10 @@ __global__ void __launch_bounds__(kBlock) k_hit_records(DeviceScene S, PathState
     for (uint32_t k = lane; k < n; k += 64) {
       const uint32_t i = seg_slot(seg.nseg, sg, k);
       const vec4 h = hit[i];
-      const uint32_t tri = f2u(h.w) == kInvalidRef ? kInvalidRef : (f2u(h.w) & kHitTriMask);
       pt_hit_record r;
-      if (tri != kInvalidRef) {
+      if (!hit_word_miss(f2u(h.w))) {
         r.t = h.x; r.u = h.y; r.v = h.z;
-        triangle_ids(S, tri, &r.instance, &r.primitive);
+        triangle_ids(S, hit_word_tri(f2u(h.w)), &r.instance, &r.primitive);
       } else {
         r.t = 0.0f; r.u = 0.0f; r.v = 0.0f; r.instance = -1; r.primitive = -1;
       }
@@ -1249,13 +1239,12 @@ __global__ void __launch_bounds__(kBlock) k_hit_records(DeviceScene S, PathState
 
 // ---- launchers (host) ---------------------------------------------------------------------------------------------------
 void launch_raygen(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState st, vec4* Lbuf, Segments seg, BatchCounters* ctr,
-                   uint32_t first_sample, uint32_t nsamples) {
-  hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, seg, ctr, first_sample, nsamples, tiles_x(S.width), tiles_y(S.height));
-}
-void launch_raygen_adaptive(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState st, vec4* Lbuf, Segments seg,
-                            uint32_t first_sample, uint32_t nsamples, const Rect& rect, const uint32_t* active, const uint32_t* active_count) {
-  hipLaunchKernelGGL(k_raygen_adaptive, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, seg, first_sample, nsamples, tiles_x(S.width), rect, active,
-                     active_count);
+                   uint32_t first_sample, uint32_t nsamples, const TileSet* tiles) {
+  if (tiles)
+    hipLaunchKernelGGL(k_raygen_adaptive, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, seg, first_sample, nsamples, tiles_x(S.width), tiles->rect,
+                       tiles->active, tiles->active_count);
+  else
+    hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, seg, ctr, first_sample, nsamples, tiles_x(S.width), tiles_y(S.height));
 }
 void launch_chunk_tables(hipStream_t s, Segments seg, uint32_t cur, BatchCounters* ctr, uint32_t bounce_closest,
                          uint32_t bounce_shadow, bool do_shadow) {
@@ -1328,17 +1317,14 @@ void launch_trace_shadow(hipStream_t s, uint32_t grid, const DeviceScene& S, Sha
   else hipLaunchKernelGGL((k_trace_shadow<false, false>), dim3(grid), dim3(kBlock), 0, s, S, sq, Lbuf, seg, ctr, bounce, spill);
 }
 void launch_accumulate(hipStream_t s, vec4* acc, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
-                       uint32_t nonfinite_policy, BatchCounters* ctr) {
-  const uint32_t tiles = tile_count(width, npixels / width);   // one wave per 8x8 tile
-  hipLaunchKernelGGL(k_accumulate, dim3((tiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, s, acc, Lbuf, npixels, width, nsamples, n0,
-                     nonfinite_policy, ctr);
-}
-void launch_accumulate_adaptive(hipStream_t s, vec4* acc, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
-                                uint32_t nonfinite_policy, BatchCounters* ctr, const uint32_t* active, const uint32_t* active_count,
-                                uint32_t max_active, vec2* mom, uint32_t* tile_n, const Rect& rect) {
-  const uint32_t tiles = max_active;   // one wave per tile that may still be active
-  hipLaunchKernelGGL(k_accumulate_adaptive, dim3((tiles + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, s, acc, Lbuf, npixels, width, nsamples,
-                     n0, nonfinite_policy, ctr, active, active_count, mom, tile_n, rect);
+                       uint32_t nonfinite_policy, BatchCounters* ctr, const TileSet* tiles, vec2* mom, uint32_t* tile_n) {
+  // one wave per 8x8 tile of the image, or per tile that may still be active
+  const dim3 grid(((tiles ? tiles->max_active : tile_count(width, npixels / width)) + kBlock / 64 - 1) / (kBlock / 64));
+  if (tiles)
+    hipLaunchKernelGGL(k_accumulate_adaptive, grid, dim3(kBlock), 0, s, acc, Lbuf, npixels, width, nsamples, n0, nonfinite_policy, ctr, tiles->active,
+                       tiles->active_count, mom, tile_n, tiles->rect);
+  else
+    hipLaunchKernelGGL(k_accumulate, grid, dim3(kBlock), 0, s, acc, Lbuf, npixels, width, nsamples, n0, nonfinite_policy, ctr);
 }
 void launch_accumulate_gmon(hipStream_t s, vec4* buckets, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
                             uint32_t samples_per_bucket, uint32_t gmon_buckets, uint32_t bucket_base, uint32_t nonfinite_policy, BatchCounters* ctr) {

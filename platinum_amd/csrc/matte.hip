@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "matte.h"
+#include "pt_tilefold.h"
 
 namespace pt {
 
@@ -36,66 +37,47 @@ __global__ void __launch_bounds__(256) k_matte_clear(uint4* __restrict__ slots, 
   if (i < n) slots[i] = uint4{kMatteNone, 0u, kMatteNone, 0u};
 }
 
-// ---- k_matte_ids: the bounce-0 queue (state buffer 0) -> Mbuf.  Reads the queue only: word 3 of the hit record and of rayD. -------------
+// ---- k_matte_ids: the bounce-0 queue (pt_tilefold.h walk_bounce0) -> Mbuf.  Reads the queue only: word 3 of the hit record and of rayD. ----
 __global__ void __launch_bounds__(256) k_matte_ids(const DeviceScene* __restrict__ Sp, PathState st, const vec4* __restrict__ hit, Segments seg,
                                                    MatteIds* __restrict__ Mbuf) {
   const ShadeRec* __restrict__ recs = Sp->shade_recs;
-  const uint32_t lane = wave_lane();
-  const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = gridDim.x * (blockDim.x >> 6);
-  for (uint32_t sg = wave; sg < seg.nseg; sg += nwaves) {
-    const uint32_t n = seg.active[0][sg];
-    const uint32_t base = segment_lbuf_base(seg, sg);
-    for (uint32_t k = lane; k < n; k += 64) {
-      const uint32_t i = seg_slot(seg.nseg, sg, k);
-      const uint32_t hw = f2u(hit[i].w);
-      const uint32_t pid = base + (f2u(st.rayD[i].w) >> kMetaPidShift);
+  const uint32_t lane = wave_lane(), wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = gridDim.x * (blockDim.x >> 6);
+  for (uint32_t sg = wave; sg < seg.nseg; sg += nwaves)
+    walk_bounce0(seg, st, hit, sg, lane, [&](uint32_t, uint32_t pid, uint32_t hw) {
       MatteIds m{kMatteNone, kMatteNone};
-      if (hw != kInvalidRef) {
-        const uint32_t tri = hw & kHitTriMask;
+      if (!hit_word_miss(hw)) {
+        const uint32_t tri = hit_word_tri(hw);
         m.inst = ldg(&recs[tri].inst);
         m.material = ldg(&recs[tri].material);
       }
       Mbuf[pid] = m;
-    }
-  }
+    });
 }
 
-// ---- k_accumulate_matte: one wave per 8x8 tile, k_accumulate's layout ---------------------------------------------------------------------
-// Eight samples of the tile's 64 pixels are staged through LDS per round (coalesced 8-B reads of Mbuf, 4.6 KB); every lane then folds the
-// eight samples of its pixel in sample order into the 16 slots it holds in registers across the batch, and stores them once.
-// ADAPTIVE (k_accumulate_matte_adaptive): block v folds virtual tile v < *active_count into image tile active[v], the pixels inside `rect`;
-// Mbuf is dense over virtual tiles (denoise.hip k_accumulate_aov_adaptive).
+// ---- k_accumulate_matte: one wave per 8x8 tile (pt_tilefold.h fold_tile / fold_stage) ------------------------------------------------------
+// A round stages 8-B entries of Mbuf (4.6 KB of LDS); every lane then folds the samples of its pixel in sample order into the 16 slots it
+// holds in registers across the batch, and stores them once.  ADAPTIVE: k_accumulate_matte_adaptive.
 template <bool ADAPTIVE>
 __device__ __forceinline__ void accumulate_matte_body(uint4* __restrict__ slots, const MatteIds* __restrict__ Mbuf, uint32_t width, uint32_t height,
                                                       uint32_t nsamples, const uint32_t* __restrict__ active,
                                                       const uint32_t* __restrict__ active_count, Rect rect) {
-  constexpr uint32_t kRow = 9;
-  __shared__ MatteIds stage[64 * kRow];
+  __shared__ MatteIds stage[64 * kFoldRow];
   const uint32_t lane = wave_lane();
-  const uint32_t tilesX = tiles_x(width), tiles = ADAPTIVE ? *active_count : tilesX * tiles_y(height);
-  const uint32_t tile = blockIdx.x;
-  const bool live = tile < tiles;
-  const uint32_t itile = ADAPTIVE ? (live ? active[tile] : 0u) : tile;   // the image tile
-  const PixelXY q = tile_pixel(itile, lane, tilesX);
-  const bool inside = live && (ADAPTIVE ? rect_contains(rect, q.x, q.y) : q.x < width && q.y < height);
-  uint4* __restrict__ px = slots + ((size_t)q.y * width + q.x) * kMattePixelVec4;
+  const FoldTile t = fold_tile<ADAPTIVE>(blockIdx.x, lane, width, height, active, active_count, rect);
+  const bool live = t.live, inside = t.inside;
+  uint4* __restrict__ px = slots + ((size_t)t.q.y * width + t.q.x) * kMattePixelVec4;
   MatteSlots I, M;
   matte_clear(I); matte_clear(M);
   if (inside) { load_slots(px, I); load_slots(px + kMatteSlots / 2u, M); }
   for (uint32_t s0 = 0; s0 < nsamples; s0 += 8u) {
     const uint32_t nb = nsamples - s0 < 8u ? nsamples - s0 : 8u;
     __syncthreads();
-    if (live) {
-#pragma unroll 4   // (four loads in flight per lane: all eight cost 8 more VGPRs than the 64 of 8 waves per SIMD)
-      for (uint32_t i = 0; i < 8u; i++) {
-        const uint32_t p = i * 8u + (lane >> 3), j = lane & 7u;   // (the staging order, as k_accumulate)
-        if (j < nb) stage[p * kRow + j] = Mbuf[lbuf_index(tile, s0 + j, nsamples, p)];
-      }
-    }
+    // (four loads in flight per lane: all eight cost 8 more VGPRs than the 64 of 8 waves per SIMD)
+    if (live) fold_stage<4>(t.tile, lane, s0, nb, nsamples, [&](uint32_t pid, uint32_t slot) { stage[slot] = Mbuf[pid]; });
     __syncthreads();
     if (inside) {
       for (uint32_t j = 0; j < nb; j++) {
-        const MatteIds m = stage[lane * kRow + j];
+        const MatteIds m = stage[lane * kFoldRow + j];
         matte_fold(I, m.inst);
         matte_fold(M, m.material);
       }
@@ -137,14 +119,14 @@ void launch_matte_ids(hipStream_t s, uint32_t grid, const DeviceScene* S_device,
   hipLaunchKernelGGL(k_matte_ids, dim3(grid), dim3(256), 0, s, S_device, st, hit, seg, Mbuf);
 }
 
-void launch_accumulate_matte(hipStream_t s, uint4* slots, const MatteIds* Mbuf, uint32_t width, uint32_t height, uint32_t nsamples) {
-  hipLaunchKernelGGL(k_accumulate_matte, dim3(tile_count(width, height)), dim3(64), 0, s, slots, Mbuf, width, height, nsamples);
-}
-
-void launch_accumulate_matte_adaptive(hipStream_t s, uint4* slots, const MatteIds* Mbuf, uint32_t width, uint32_t height, uint32_t nsamples,
-                                      const uint32_t* active, const uint32_t* active_count, uint32_t max_active, const Rect& rect) {
-  // one block per tile that may still be active
-  hipLaunchKernelGGL(k_accumulate_matte_adaptive, dim3(max_active), dim3(64), 0, s, slots, Mbuf, width, height, nsamples, active, active_count, rect);
+void launch_accumulate_matte(hipStream_t s, uint4* slots, const MatteIds* Mbuf, uint32_t width, uint32_t height, uint32_t nsamples,
+                             const TileSet* tiles) {
+  // one block per tile of the image, or per tile that may still be active
+  if (tiles)
+    hipLaunchKernelGGL(k_accumulate_matte_adaptive, dim3(tiles->max_active), dim3(64), 0, s, slots, Mbuf, width, height, nsamples, tiles->active,
+                       tiles->active_count, tiles->rect);
+  else
+    hipLaunchKernelGGL(k_accumulate_matte, dim3(tile_count(width, height)), dim3(64), 0, s, slots, Mbuf, width, height, nsamples);
 }
 
 void launch_matte_resolve(hipStream_t s, const uint4* slots, uint32_t layer, const uint32_t* ids, uint32_t id_count, const uint32_t* tile_n,

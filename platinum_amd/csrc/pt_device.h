@@ -53,8 +53,13 @@ constexpr uint32_t kSlotInstBits = 26, kSlotInstMask = (1u << kSlotInstBits) - 1
 // A triangle is named by 2 * slot + half (half 1 = triangle B) wherever one is referred to: RayHit::tri, the hit record, shade_recs[].
 // Hit record word 3: triangle index (28 bits) | material class << 28; kInvalidRef = miss.  The class (which BSDF lobes the
 // material can take: see material_class) lets k_shade put hits of one kind into one wave.
+constexpr uint32_t kInvalidRef = 0xffffffffu;
 constexpr uint32_t kHitTriMask = 0x0fffffffu;
 constexpr uint32_t kShadeClasses = 4;
+template <class Hit> PT_HD uint32_t hit_word(const Hit& h) { return h.tri == kInvalidRef ? kInvalidRef : (h.tri | ((h.gid & 3u) << 28)); }  // (Hit: RayHit)
+PT_HD bool hit_word_miss(uint32_t w) { return w == kInvalidRef; }
+PT_HD uint32_t hit_word_tri(uint32_t w) { return w & kHitTriMask; }        // (of a hit)
+PT_HD uint32_t hit_word_class(uint32_t w) { return (w >> 28) & 3u; }      // (of a hit)
 
 // What shading needs to know about a hit triangle, resolved once per render (k_shade_records) and indexed like tris[]:
 // absolute vertex indices, the absolute index of its MaterialGPU, its instance, and the world-space geometric normal
@@ -114,8 +119,7 @@ struct alignas(16) BvhNode6 {
 };
 static_assert(sizeof(BvhNode6) == 64, "BvhNode6");
 constexpr uint32_t kMaxWide6Triangles = 1u << 26;
-constexpr uint32_t kLeafBit = 0x80000000u;
-constexpr uint32_t kInvalidRef = 0xffffffffu;
+constexpr uint32_t kLeafBit = 0x80000000u;   // (kInvalidRef: above, with the hit record)
 
 // ---- two-level structure (instanced scenes; replaces the reference's BLAS per mesh + TLAS over instances,
 //      renderer_pt.cpp:653-749, for scenes that repeat a mesh many times) --------------------------------------------

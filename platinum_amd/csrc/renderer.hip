@@ -105,11 +105,11 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
     }
   }
 #endif
-  // an adaptive or region render's batch covers the active tiles only: the three kernels that place a tile in the image read the current
-  // list, and take the render's rectangle as their validity test
+  // an adaptive or region render's batch covers the active tiles only: the kernels that place a tile in the image read the current list,
+  // and take the render's rectangle as their validity test (null: the full-frame kernels)
   const bool ad = mode == BATCH_RENDER && r->vtiles;
-  const uint32_t* ad_list = ad ? r->ad_list[r->ad_cur].p : nullptr;
-  const uint32_t* ad_count = ad ? r->ad_count.p + r->ad_cur : nullptr;
+  const TileSet tile_set = r->tile_set();
+  const TileSet* tiles = ad ? &tile_set : nullptr;
   // A full-frame render batch with lists generates and traces its camera rays in one kernel (k_camera_primary), timed as bounce 0's closest-hit
   // launch together with the walk for flagged pixels; the table pass alone is left in the raygen class.
   const bool fused = mode == BATCH_RENDER && r->cam_lists && !ad && !r->no_fused_camera;
@@ -126,8 +126,7 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
     }
   } else {
     ScopedTimer t(r, K_RAYGEN);
-    if (ad) launch_raygen_adaptive(s, r->grid, S, r->path_state(0), r->Lbuf.p, seg, first, ns, r->rect, ad_list, ad_count);
-    else launch_raygen(s, r->grid, S, r->path_state(0), r->Lbuf.p, seg, ctr, first, ns);
+    launch_raygen(s, r->grid, S, r->path_state(0), r->Lbuf.p, seg, ctr, first, ns, tiles);
     launch_chunk_tables(s, seg, 0, ctr, 0, 0, false);
   }
   int cur = 0;
@@ -175,29 +174,21 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
       // the reference resolves after every frame with fullBuckets = gmonIdx + 1 (renderer_pt.cpp:164-179); only the last
       // resolve of a batch is observable
       launch_gmon(s, r->acc, r->gmon_buckets_d.p, npix, (f0 + ns - 1) / spb + 1 - r->gmon_bucket_base, r->gmon_cap);
-    } else if (ad) {
-      launch_accumulate_adaptive(s, r->acc, r->Lbuf.p, npix, S.width, ns, n0, r->params.nonfinite_policy, ctr, ad_list, ad_count, r->ad_tiles0,
-                                 r->adaptive ? r->ad_mom.p : nullptr, r->ad_tile_n.p, r->rect);
     } else {
-      launch_accumulate(s, r->acc, r->Lbuf.p, npix, S.width, ns, n0, r->params.nonfinite_policy, ctr);
+      launch_accumulate(s, r->acc, r->Lbuf.p, npix, S.width, ns, n0, r->params.nonfinite_policy, ctr, tiles, r->adaptive ? r->ad_mom.p : nullptr,
+                        r->ad_tile_n.p);
     }
-    if (r->aov && ad)
-      launch_accumulate_aov_adaptive(s, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * (size_t)npix, r->Abuf.p, r->Lbuf.p, S.width, S.height, ns,
-                                     n0, r->params.nonfinite_policy, ad_list, ad_count, r->ad_tiles0, r->rect);
-    else if (r->aov)
+    if (r->aov)
       launch_accumulate_aov(s, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * (size_t)npix, r->Abuf.p, r->Lbuf.p, S.width, S.height, ns, n0,
-                            r->params.nonfinite_policy);
-    if (r->matte && ad)
-      launch_accumulate_matte_adaptive(s, r->matte_slots.p, r->Mbuf.p, S.width, S.height, ns, ad_list, ad_count, r->ad_tiles0, r->rect);
-    else if (r->matte)
-      launch_accumulate_matte(s, r->matte_slots.p, r->Mbuf.p, S.width, S.height, ns);
+                            r->params.nonfinite_policy, tiles);
+    if (r->matte) launch_accumulate_matte(s, r->matte_slots.p, r->Mbuf.p, S.width, S.height, ns, tiles);
   }
   // a batch that ends at a checkpoint (flush_pending never lets one straddle it): test the active tiles, compact the list into the other
   // buffer, and send the new count to pinned host memory
   if (ad && r->adaptive && r->ad_next < r->total && n0 + ns == r->ad_next) {
     {
       ScopedTimer t(r, K_ACCUM);
-      PT_HIP(launch_adaptive_check(s, ad_list, ad_count, r->ad_list[r->ad_cur ^ 1].p, r->ad_count.p + (r->ad_cur ^ 1), r->ad_mom.p, S.width, r->rect,
+      PT_HIP(launch_adaptive_check(s, tiles->active, tiles->active_count, r->ad_list[r->ad_cur ^ 1].p, r->ad_count.p + (r->ad_cur ^ 1), r->ad_mom.p, S.width, r->rect,
                                    r->ad_tiles0, r->ad_next, r->adaptive_opts.threshold, r->ad_flags.p, r->ad_scratch.p, r->ad_scratch.n,
                                    r->ad_host_count));
     }
@@ -1172,7 +1163,7 @@ int dev_trace_primary(pt_renderer* r, uint32_t sample_idx, pt_hit_record* out) {
   PT_HIP(hipMemsetAsync(r->ctr.p, 0, sizeof(BatchCounters), s));
   Segments seg = r->segments();
   seg.nsamples = 1;
-  launch_raygen(s, r->grid, r->S, r->path_state(0), r->Lbuf.p, seg, r->ctr.p, sample_idx, 1);
+  launch_raygen(s, r->grid, r->S, r->path_state(0), r->Lbuf.p, seg, r->ctr.p, sample_idx, 1, nullptr);
   launch_chunk_tables(s, seg, 0, r->ctr.p, 0, 0, false);
   launch_trace_closest(s, r->closest_grid, r->S, r->path_state(0), r->hit.p, seg, 0, r->ctr.p, 0, r->spill.p, nullptr, npix, false);
   launch_hit_records(s, r->grid, r->S, r->path_state(0), r->hit.p, seg, rec.p);

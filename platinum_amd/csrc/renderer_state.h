@@ -221,6 +221,7 @@ struct pt_renderer {
   uint64_t launches[K_CLASSES] = {0, 0, 0, 0, 0};
   double upload_ms = 0, bvh_ms = 0;
 
+  TileSet tile_set() { return TileSet{ad_list[ad_cur].p, ad_count.p + ad_cur, ad_tiles0, rect}; }   // of a render with `vtiles`: the current list
   PathState path_state(int k) { return PathState{st_rayO[k].p, st_rayD[k].p, st_att[k].p}; }
   ShadowQueue shadow_queue() { return ShadowQueue{sq_o.p, sq_d.p, sq_c.p}; }
   Segments segments() { return Segments{{seg_active[0].p, seg_active[1].p}, seg_shadow.p, seg_poison.p, wave_stats.p, chunk_table[0].p, chunk_table[1].p, shade_order.p, shade_cost.p, seg_cap, nseg, tiles_per_seg, /*nsamples: set per batch*/ 0u, seg_bands, nstats, refill_threshold}; }

@@ -5,6 +5,7 @@
 #ifndef PTAMD_TESTS_EMU_ADAPTIVE_EMU
 #define PTAMD_TESTS_EMU_ADAPTIVE_EMU
 #include "../../platinum_amd/csrc/pt_adaptive.h"
+#include "../../platinum_amd/csrc/pt_tilefold.h"
 
 extern "C" {
 
@@ -35,10 +36,9 @@ void ad_host_filter_counts(const float* acc, const float* albedo, const float* n
     for (size_t p = 0; p < npix; p++) o[p] = vec4{a[p].x, a[p].y, a[p].z, 1.0f};
     return;
   }
-  const uint32_t tilesX = tiles_x(W);
   std::vector<uint32_t> tile_n(tile_count(W, H));
-  for (uint32_t t = 0; t < tile_n.size(); t++) {   // every pixel of a tile holds the same count: take its first
-    const PixelXY p = tile_pixel(t, 0, tilesX);
+  for (uint32_t t = 0; t < tile_n.size(); t++) {   // every pixel of a tile holds the same count: take its first (lane 0 is inside the image)
+    const PixelXY p = fold_tile<false>(t, 0, W, H, nullptr, nullptr, Rect{}).q;
     tile_n[t] = counts[(size_t)p.y * W + p.x];
   }
   std::vector<vec4> guide(npix), aux(npix), col0(npix), col1(npix);

@@ -98,7 +98,7 @@ uint64_t dn_host_render(void* h, uint32_t first, uint32_t ns, uint32_t n0, float
       for (uint32_t x = 0; x < W; x++) {
         const size_t p = (size_t)y * W + x;
         vec3 L = emu_path<false>(e, x, y, first + s, scratch);
-        if (!(fabsf(L.x) <= 3.0e38f && fabsf(L.y) <= 3.0e38f && fabsf(L.z) <= 3.0e38f)) {  // NaN or inf
+        if (not_finite(L)) {
           nonfinite++;
           if (nonfinite_px) nonfinite_px[p]++;
           if (zero) L = v3(0.0f);

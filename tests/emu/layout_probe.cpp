@@ -1,10 +1,11 @@
-// TEST HARNESS ONLY (tests/emu) — the host build of the index maps of platinum_amd/csrc/pt_layout.h and of plan_queues (queue_plan.h), one
-// table per map, for tests/test_layout_host.py.  Not part of libptamd.so, never loaded by platinum_amd, not a fallback.
+// TEST HARNESS ONLY (tests/emu) — the host build of the index maps of platinum_amd/csrc/pt_layout.h, of the tile folds' addressing
+// (pt_tilefold.h) and of plan_queues (queue_plan.h), one table per map, for tests/test_layout_host.py.  Not part of libptamd.so, never loaded by platinum_amd, not a fallback.
 // Fifth part of tests/emu/host_harness.cpp; not compiled alone.
 #ifndef PTAMD_TESTS_EMU_LAYOUT_PROBE
 #define PTAMD_TESTS_EMU_LAYOUT_PROBE
 #include "../../platinum_amd/csrc/pt_device.h"
 #include "../../platinum_amd/csrc/pt_layout.h"
+#include "../../platinum_amd/csrc/pt_tilefold.h"
 #include "../../platinum_amd/csrc/queue_plan.h"
 
 using namespace pt;
@@ -60,6 +61,27 @@ void lp_tile_pixels(uint32_t W, uint32_t H, uint32_t* xy) {
       *xy++ = q.y;
     }
 }
+
+// fold_tile of every (tile < ntiles, lane): out[(tile * 64 + lane) * 5] = {itile, live, inside, q.x, q.y}.  active == null: the full-frame
+// form (rect unused); else virtual tiles over the list active[0, *active_count), with rect = {x0, y0, x1, y1}.
+void lp_fold_tiles(uint32_t W, uint32_t H, uint32_t ntiles, const uint32_t* active, const uint32_t* active_count, const uint32_t* rect,
+                   uint32_t* out) {
+  const Rect r = rect ? Rect{rect[0], rect[1], rect[2], rect[3]} : Rect{};
+  for (uint32_t t = 0; t < ntiles; t++)
+    for (uint32_t l = 0; l < 64; l++) {
+      const FoldTile f = active ? fold_tile<true>(t, l, W, H, active, active_count, r) : fold_tile<false>(t, l, W, H, nullptr, nullptr, r);
+      *out++ = f.itile; *out++ = f.live; *out++ = f.inside; *out++ = f.q.x; *out++ = f.q.y;
+    }
+}
+// the (pid, slot) pairs of one staging round of `tile` (samples s0 .. s0 + nb - 1 of nsamples), lane by lane in fold_stage's order; returns
+// their number (<= 512 pairs)
+uint32_t lp_fold_stage(uint32_t tile, uint32_t s0, uint32_t nb, uint32_t nsamples, uint32_t* out) {
+  uint32_t n = 0;
+  for (uint32_t l = 0; l < 64; l++)
+    fold_stage(tile, l, s0, nb, nsamples, [&](uint32_t pid, uint32_t slot) { out[2 * n] = pid; out[2 * n + 1] = slot; n++; });
+  return n;
+}
+uint32_t lp_fold_row() { return kFoldRow; }
 
 }  // extern "C"
 
