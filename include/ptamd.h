@@ -660,6 +660,46 @@ typedef struct pt_pick_result {
  * sample count too).  PT_ERR_INVALID_ARGUMENT for x >= width or y >= height. */
 int pt_pick(pt_renderer* r, uint32_t x, uint32_t y, pt_pick_result* out);
 
+/* ---- selection overlay (NEW, an additive extension of ABI 5: new entry points and one new struct, no existing struct changed) ----
+ * With `enabled` set, every pt_read_render_target and pt_present_render_target of a render that keeps ID mattes draws, as the last step of
+ * the display chain (after the post-process, on the RGBA8 target, on the device), an antialiased outline around the pixels covered by the
+ * ids of pt_set_selection on `layer`, and a tint over them.  The colours are UI colours in the target's own encoding: they do not go
+ * through auto exposure, bloom, the post-process or the tonemapper.
+ * Per pixel p, with m(p) the coverage pt_read_matte gives for the set (0 outside a render region and where no sample was taken) and c a
+ * channel's byte / 255:
+ *   lim = width + 0.5, R = ceil(lim) - 1, k(dx, dy) = min(max(lim - sqrt(dx^2 + dy^2), 0), 1)
+ *   D(p) = max over |dx|, |dy| <= R with p + (dx, dy) inside the frame of m(p + (dx, dy)) * k(dx, dy)          (>= m(p): k(0, 0) = 1)
+ *   af = m * fill_rgba[3], ao = (D - m) * outline_rgba[3]
+ *   c1 = c * (1 - af) + fill * af, c2 = c1 * (1 - ao) + outline * ao, byte = c2 clamped to [0, 1], * 255 + 0.5, truncated
+ * in fp32, one IEEE operation each.  The band lies outside the silhouette, `width` pixels wide and soft where the coverage is fractional;
+ * alpha 0 keeps a byte, alpha 1 gives exactly the colour's byte, a pixel with af = ao = 0 keeps its four bytes and the alpha byte is never
+ * changed.  The options and the set are read by every target read and present: no restart is needed.
+ * Nothing is drawn, allocated or launched, silently, when enabled = 0, when the set is empty, when the render was started without mattes,
+ * and on a device group (which keeps no mattes).  The accumulator, the AOVs, the slots, the exposure meter and pt_read_exposure_meter are
+ * unaffected either way.
+ * PT_ERR_INVALID_ARGUMENT (checked before the renderer): a layer that does not exist, width not in [1, 16], a colour component not in
+ * [0, 1] (NaN included).  PT_ERR_UNSUPPORTED: enabled = 1 on a device group. */
+typedef struct pt_selection_options {
+  uint32_t enabled;         /* default 0 */
+  uint32_t layer;           /* PT_MATTE_INSTANCE (default) or PT_MATTE_MATERIAL: what the ids of pt_set_selection are */
+  float width;              /* outline width in pixels, 1 .. 16; default 2 */
+  float _pad;
+  float outline_rgba[4];    /* default (1, 0.55, 0, 1) */
+  float fill_rgba[4];       /* default (1, 0.55, 0, 0): no tint */
+} pt_selection_options;
+void pt_default_selection_options(pt_selection_options* o);
+int pt_set_selection_options(pt_renderer* r, const pt_selection_options* o);
+/* The selected ids: any order, duplicates allowed, PT_MATTE_NONE selects the background; id_count = 0 clears the selection.  The set is kept
+ * sorted and without duplicates, and survives pt_start_render.  Its upload is ordered on the renderer's stream (a present enqueued before the
+ * call draws the earlier set) and waited for.  PT_ERR_INVALID_ARGUMENT for ids NULL with id_count > 0. */
+int pt_set_selection(pt_renderer* r, const uint32_t* ids, uint32_t id_count);
+/* Copies up to `capacity` ids of the stored set (ascending); returns their number in *count.  ids_out may be NULL with capacity 0. */
+int pt_get_selection(const pt_renderer* r, uint32_t* ids_out, uint32_t capacity, uint32_t* count);
+/* The overlay kernel on an uploaded target (width*height RGBA8 pixels) and coverage image (width*height floats) with buffers of its own:
+ * needs no render and leaves the renderer's state alone; `enabled` is not looked at.  1 .. 2^28 pixels. */
+int pt_debug_selection_overlay(pt_renderer* r, const uint8_t* rgba8_in, const float* coverage, uint32_t width, uint32_t height,
+                               const pt_selection_options* options, uint8_t* rgba8_out);
+
 const char* pt_last_error(void);
 
 /* ---------------------------------------------------------------------------------------------------------- */

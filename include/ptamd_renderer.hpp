@@ -48,6 +48,10 @@
  *   (no counterpart; the raster viewport's selection only)       pt_matte_options& matteOptions(), readbackMatteSlots(), readbackMatte(), pick():
  *                                                                ID mattes, per-pixel instance and material coverage of the camera rays' first
  *                                                                hits (ptamd.h, ABI 5 extension); handed over at startRender
+ *   (no counterpart; the raster viewport's selection outline)    pt_selection_options& selectionOptions(), setSelection(ids), selection(): an outline
+ *                                                                around and a tint over the selected ids, drawn onto the target after the
+ *                                                                post-process (ptamd.h, ABI 5 extension); the options are handed over whenever a
+ *                                                                target is asked for, the ids at once
  * Error behaviour as the reference's: nothing throws; a failing call prints "renderer_pt: <message>" to stderr (the
  * reference prints and asserts, renderer_pt.cpp:402, 1044) and leaves the object in Status_Blocked; lastError() keeps the text.
  * Threading as the reference's: one caller thread per Renderer.
@@ -270,6 +274,22 @@ public:
   }
   // What is under pixel (x, y), top-left origin ("click to select"); false on failure.  Blocks until the enqueued samples are done.
   [[nodiscard]] bool pick(uint32_t x, uint32_t y, pt_pick_result* out) const { return m_pt && m_started && out && check(pt_pick(m_pt, x, y, out)); }
+  // Selection overlay (ptamd.h, an additive extension of ABI 5): with enabled set, presentRenderTarget / readbackRenderTarget of a render
+  // that keeps mattes draw an outline around the pixels covered by the selected ids of `layer`, and a tint over them, after the post-process
+  // (UI colours in the target's encoding).  A render without mattes and a device group silently show no overlay.  Edited in place like
+  // bloomOptions(); read whenever a target is asked for, no restart needed.
+  [[nodiscard]] constexpr pt_selection_options& selectionOptions() { return m_selection; }
+  // The selected ids (any order, duplicates allowed, PT_MATTE_NONE = the background; empty clears); kept across startRender.  false on failure.
+  bool setSelection(const std::vector<uint32_t>& ids) { return m_pt && check(pt_set_selection(m_pt, ids.empty() ? nullptr : ids.data(), (uint32_t)ids.size())); }
+  // The stored selection: ascending, without duplicates.
+  [[nodiscard]] std::vector<uint32_t> selection() const {
+    std::vector<uint32_t> out;
+    uint32_t n = 0;
+    if (!m_pt || !check(pt_get_selection(m_pt, nullptr, 0, &n))) return out;
+    out.resize(n);
+    if (n && !check(pt_get_selection(m_pt, out.data(), n, &n))) out.clear();
+    return out;
+  }
   void wait() const { if (m_pt && m_started) check(pt_wait(m_pt)); }
   [[nodiscard]] bool ok() const { return m_pt != nullptr && m_lastError.empty(); }
   [[nodiscard]] const std::string& lastError() const { return m_lastError; }
@@ -287,6 +307,7 @@ private:
     pt_default_adaptive_options(&m_adaptive);
     pt_default_render_region(&m_region);
     pt_default_matte_options(&m_matte);
+    pt_default_selection_options(&m_selection);
     std::vector<int32_t> ord(devices, devices + count);
     pt_create_info ci{};
     ci.abi_version = PT_ABI_VERSION;
@@ -310,7 +331,8 @@ private:
     postprocess::flatten(m_tonemap, m_outputSpace, &tonemap);
     return check(pt_set_gmon_options(m_pt, &m_gmonOptions)) && check(pt_set_post_options(m_pt, &post)) && check(pt_set_tonemap_options(m_pt, &tonemap)) &&
            check(pt_set_denoise_options(m_pt, &m_denoise)) && check(pt_set_despeckle_options(m_pt, &m_despeckle)) &&
-           check(pt_set_exposure_options(m_pt, &m_autoExposure)) && check(pt_set_bloom_options(m_pt, &m_bloom));
+           check(pt_set_exposure_options(m_pt, &m_autoExposure)) && check(pt_set_bloom_options(m_pt, &m_bloom)) &&
+           check(pt_set_selection_options(m_pt, &m_selection));
   }
 
   pt_renderer* m_pt = nullptr;
@@ -334,6 +356,7 @@ private:
   pt_adaptive_options m_adaptive{};
   pt_render_region m_region{};
   pt_matte_options m_matte{};
+  pt_selection_options m_selection{};
   mutable void* m_presentStream = nullptr;
   mutable std::string m_lastError;
 };

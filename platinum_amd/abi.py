@@ -252,6 +252,12 @@ class PickResult(C.Structure):
                 ("material_instance", C.c_uint32), ("material_slot", C.c_uint32), ("samples", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class SelectionOptions(C.Structure):
+    """pt_selection_options: the outline and tint the display chain draws over the pixels covered by the ids of pt_set_selection."""
+    _fields_ = [("enabled", C.c_uint32), ("layer", C.c_uint32), ("width", C.c_float), ("_pad", C.c_float),
+                ("outline_rgba", C.c_float * 4), ("fill_rgba", C.c_float * 4)]
+
+
 class HitRecord(C.Structure):
     _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("instance", C.c_int32), ("primitive", C.c_int32)]
 
@@ -336,6 +342,11 @@ SYMBOLS = [
     ("pt_read_matte_slots", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     ("pt_read_matte", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     ("pt_pick", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PickResult)]),
+    ("pt_default_selection_options", None, [C.POINTER(SelectionOptions)]),
+    ("pt_set_selection_options", C.c_int, [C.c_void_p, C.POINTER(SelectionOptions)]),
+    ("pt_set_selection", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    ("pt_get_selection", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("pt_debug_selection_overlay", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(SelectionOptions), C.c_void_p]),
     ("pt_last_error", C.c_char_p, []),
     ("pt_get_constants", C.c_int, [C.c_void_p, C.POINTER(Constants)]),
     ("pt_get_lights", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),

@@ -1,9 +1,11 @@
 // display.hip — everything between an HDR image and the RGBA8 render target: the options of the post-process, the tonemapper, the denoiser,
-// the firefly clamp, auto exposure and bloom, and the display chain that runs them (enqueue_display at the end of this file):
-// source (merged | denoised | accumulator), auto exposure, bloom, k_postprocess.  No kernel lives here: the launches are those of kernels.hip,
-// denoise.hip, exposure.hip and bloom.hip, and the path tracer's driver (renderer.hip) is reached through flush_pending and dev_wait.
+// the firefly clamp, auto exposure, bloom and the selection overlay, and the display chain that runs them (enqueue_display at the end of this
+// file): source (merged | denoised | accumulator), auto exposure, bloom, k_postprocess, selection overlay.  No kernel lives here:
+// the launches are those of kernels.hip, denoise.hip, exposure.hip, bloom.hip, matte.hip and selection.hip, and the path tracer's driver
+// (renderer.hip) is reached through flush_pending and dev_wait.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -256,6 +258,86 @@ int dev_debug_bloom(pt_renderer* r, const float* rgba, uint32_t width, uint32_t 
   return PT_OK;
 }
 
+// ---- the selection overlay (selection.hip) ----
+extern "C" void pt_default_selection_options(pt_selection_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->layer = PT_MATTE_INSTANCE;
+  o->width = 2.0f;
+  o->outline_rgba[0] = 1.0f; o->outline_rgba[1] = 0.55f; o->outline_rgba[2] = 0.0f; o->outline_rgba[3] = 1.0f;
+  o->fill_rgba[0] = 1.0f; o->fill_rgba[1] = 0.55f; o->fill_rgba[2] = 0.0f; o->fill_rgba[3] = 0.0f;
+}
+
+// (the options are checked before the renderer, as dev_set_bloom_options)
+int dev_set_selection_options(pt_renderer* r, const pt_selection_options* o) {
+  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (const char* why = selection_options_error(*o)) return fail(PT_ERR_INVALID_ARGUMENT, std::string("pt_set_selection_options: ") + why);
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_selection_options: null renderer");
+  r->selection = *o;
+  return PT_OK;
+}
+
+// The set goes to the overlay's own device array behind everything enqueued so far (a present enqueued earlier draws the earlier set) and
+// the copy is waited for, as dev_read_matte waits for its own: the host array it reads is the renderer's.
+int dev_set_selection(pt_renderer* r, const uint32_t* ids, uint32_t id_count) {
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_selection: null renderer");
+  if (id_count && !ids) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_selection: null id set");
+  std::vector<uint32_t> set = matte_id_set(ids, id_count);
+  if (!set.empty()) {
+    PT_HIP(hipSetDevice(r->device));
+    if (set.size() > r->sel_ids.cap) PT_HIP(hipStreamSynchronize(r->stream));   // (the array is replaced: nothing enqueued may still read it)
+    PT_HIP(r->sel_ids.alloc(set.size()));
+    PT_HIP(hipMemcpyAsync(r->sel_ids.p, set.data(), sizeof(uint32_t) * set.size(), hipMemcpyHostToDevice, r->stream));
+    PT_HIP(hipStreamSynchronize(r->stream));
+  }
+  r->sel_set.swap(set);
+  return PT_OK;
+}
+
+int dev_get_selection(const pt_renderer* r, uint32_t* ids_out, uint32_t capacity, uint32_t* count) {
+  if (!r || !count || (capacity && !ids_out)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_get_selection: null argument");
+  *count = (uint32_t)r->sel_set.size();
+  const size_t n = std::min<size_t>(capacity, r->sel_set.size());
+  if (n) memcpy(ids_out, r->sel_set.data(), sizeof(uint32_t) * n);
+  return PT_OK;
+}
+
+// Is there an overlay to draw on this render's target?
+static bool selection_drawn(const pt_renderer* r) { return r->selection.enabled && r->matte && !r->sel_set.empty(); }
+
+// The overlay after the post-process, enqueued on the renderer's stream: the set's coverage resolved as dev_read_matte resolves it, into
+// the overlay's own image, then drawn onto r->render_target in place.
+static int enqueue_selection(pt_renderer* r) {
+  PT_HIP(r->sel_cov.alloc((size_t)r->S.width * r->S.height));
+  launch_matte_resolve(r->stream, r->matte_slots.p, r->selection.layer, r->sel_ids.p, (uint32_t)r->sel_set.size(), r->vtiles ? r->ad_tile_n.p : nullptr,
+                       (uint32_t)r->launched, r->rect, r->S.width, r->S.height, r->sel_cov.p);
+  launch_selection_overlay(r->stream, r->render_target.p, r->sel_cov.p, r->S.width, r->S.height, r->selection, !r->sel_no_early_out);
+  PT_HIP(hipGetLastError());
+  return PT_OK;
+}
+
+// the overlay kernel on an uploaded target and coverage image, with buffers of its own; the renderer's own state is untouched
+int dev_debug_selection_overlay(pt_renderer* r, const uint8_t* rgba8_in, const float* coverage, uint32_t width, uint32_t height,
+                                const pt_selection_options* options, uint8_t* rgba8_out) {
+  if (!options || !rgba8_in || !coverage || !rgba8_out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (const char* why = selection_options_error(*options)) return fail(PT_ERR_INVALID_ARGUMENT, std::string("pt_debug_selection_overlay: ") + why);
+  if (width == 0 || height == 0 || (uint64_t)width * height > (1ull << 28))
+    return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_selection_overlay: the image must hold 1..2^28 pixels");
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_selection_overlay: null renderer");
+  PT_HIP(hipSetDevice(r->device));
+  const size_t npix = (size_t)width * height;
+  DevBuf<uint32_t> target;
+  DevBuf<float> cov;
+  PT_HIP(target.alloc(npix)); PT_HIP(cov.alloc(npix));
+  PT_HIP(hipMemcpyAsync(target.p, rgba8_in, 4 * npix, hipMemcpyHostToDevice, r->stream));
+  PT_HIP(hipMemcpyAsync(cov.p, coverage, sizeof(float) * npix, hipMemcpyHostToDevice, r->stream));
+  launch_selection_overlay(r->stream, target.p, cov.p, width, height, *options, !r->sel_no_early_out);
+  PT_HIP(hipGetLastError());
+  PT_HIP(hipStreamSynchronize(r->stream));
+  PT_HIP(hipMemcpy(rgba8_out, target.p, 4 * npix, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
 // ---- the display chain.  Everything is enqueued on r->stream; the callers below decide what is waited for. ----
 
 // The image the chain starts from: a group's merged image when one is given, else the denoised image (its filter enqueued here) of a
@@ -268,8 +350,8 @@ static int display_source(pt_renderer* r, const vec4* merged, const vec4** src) 
   return rc;
 }
 
-// Source, auto exposure, bloom, post-process into r->render_target: one step of the exposure smoothing state per call, and nothing
-// allocated or launched for a stage that is disabled.
+// Source, auto exposure, bloom, post-process into r->render_target, selection overlay onto it: one step of the exposure smoothing state
+// per call, and nothing allocated or launched for a stage that is disabled.  (A group's merged image gets no overlay: a group keeps no mattes.)
 static int enqueue_display(pt_renderer* r, const vec4* merged) {
   const vec4* src;
   if (const int rc = display_source(r, merged, &src)) return rc;
@@ -284,6 +366,7 @@ static int enqueue_display(pt_renderer* r, const vec4* merged) {
   pc.odt = PPMat3{odt.c0, odt.c1, odt.c2};
   launch_postprocess(r->stream, src, r->render_target.p, r->S.width, r->S.height, pc);
   PT_HIP(hipGetLastError());
+  if (!merged && selection_drawn(r)) { const int rc = enqueue_selection(r); if (rc != PT_OK) return rc; }
   return PT_OK;
 }
 

@@ -789,6 +789,25 @@ int pt_pick(pt_renderer* r, uint32_t x, uint32_t y, pt_pick_result* out) {
   return fail(PT_ERR_BAD_STATE, "pt_pick: a device group does not keep ID mattes");
 }
 
+// The selection overlay draws from the ID mattes, which a group does not keep: its merged path shows no overlay.  The options go to every
+// member (never enabled); the set is held by the first member.
+int pt_set_selection_options(pt_renderer* r, const pt_selection_options* o) {
+  return set_unless_enabled(r, dev_set_selection_options, o, "pt_set_selection_options: a device group does not keep ID mattes");
+}
+
+int pt_set_selection(pt_renderer* r, const uint32_t* ids, uint32_t id_count) {
+  return dev_set_selection(is_group(r) ? r->group->shards[0] : r, ids, id_count);
+}
+
+int pt_get_selection(const pt_renderer* r, uint32_t* ids_out, uint32_t capacity, uint32_t* count) {
+  return dev_get_selection(is_group(r) ? r->group->shards[0] : r, ids_out, capacity, count);
+}
+
+int pt_debug_selection_overlay(pt_renderer* r, const uint8_t* rgba8_in, const float* coverage, uint32_t width, uint32_t height,
+                               const pt_selection_options* options, uint8_t* rgba8_out) {
+  return dev_debug_selection_overlay(is_group(r) ? r->group->shards[0] : r, rgba8_in, coverage, width, height, options, rgba8_out);
+}
+
 int pt_get_stats(pt_renderer* r, pt_stats* out) {
   if (!r || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
   return is_group(r) ? group_get_stats(r, out) : dev_get_stats(r, out);

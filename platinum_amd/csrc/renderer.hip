@@ -312,6 +312,7 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   pt_default_adaptive_options(&r->adaptive_opts);
   pt_default_render_region(&r->region_opts);
   pt_default_matte_options(&r->matte_opts);
+  pt_default_selection_options(&r->selection);
   r->device = device_ordinal;
   if (const char* e = getenv("PTAMD_REFILL")) r->refill_threshold = (uint32_t)atoi(e);
   if (const char* e = getenv("PTAMD_TILES_PER_SEG")) r->tiles_per_seg_override = (uint32_t)std::max(0, atoi(e));  // tuning knobs
@@ -321,6 +322,7 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   if (const char* e = getenv("PTAMD_CLOSEST_BLOCKS_PER_CU")) r->closest_blocks_per_cu = (uint32_t)std::max(1, std::min(8, atoi(e)));
   if (const char* e = getenv("PTAMD_NO_CAMERA_LISTS")) r->no_camera_lists = atoi(e) != 0;
   if (const char* e = getenv("PTAMD_NO_FUSED_CAMERA")) r->no_fused_camera = atoi(e) != 0;
+  if (const char* e = getenv("PTAMD_NO_SELECTION_EARLY_OUT")) r->sel_no_early_out = atoi(e) != 0;
   if (const char* e = getenv("PTAMD_TEST_CAMLIST_CAP")) r->cam_cap_override = (uint32_t)std::max(1, std::min((int)kCamListMaxCapacity, atoi(e)));
   if (const char* e = getenv("PTAMD_SHADOW_BLOCKS_PER_CU")) r->shadow_blocks_per_cu = (uint32_t)std::max(1, std::min(8, atoi(e)));
   hipDeviceProp_t prop;

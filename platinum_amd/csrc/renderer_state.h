@@ -18,6 +18,7 @@
 #include "math_probe.h"
 #include "matte.h"
 #include "pt_math_probe.h"
+#include "selection.h"
 #include "kernels.h"
 #include "pt_bvh.h"
 
@@ -146,6 +147,14 @@ struct pt_renderer {
   DevBuf<uint32_t> matte_ids;       // pt_read_matte: the caller's id set, sorted
   DevBuf<float> matte_cov;          // pt_read_matte: the coverage image
   std::vector<uint32_t> material_base;  // [instance] index of its first material in the flattened table (pt_pick decodes with it)
+  // selection overlay (selection.hip): nothing is allocated or launched until a target of a render that keeps mattes is read
+  // with selection.enabled and a set that is not empty.  The set and both arrays outlive pt_start_render; the arrays are the overlay's own
+  // (not matte_ids / matte_cov), so a pt_read_matte between a present and its consumption cannot disturb what the present draws.
+  pt_selection_options selection{};
+  std::vector<uint32_t> sel_set;    // pt_set_selection: the ids, sorted and without duplicates
+  DevBuf<uint32_t> sel_ids;         // sel_set on the device
+  DevBuf<float> sel_cov;            // the set's coverage image: what k_selection_overlay reads
+  bool sel_no_early_out = false;    // $PTAMD_NO_SELECTION_EARLY_OUT: blocks that see no coverage run on (the A/B switch; the same bytes)
   // auto exposure (exposure.hip): nothing is allocated or launched until a target is read with exposure.enabled, or the
   // meter is read.  The record holds the previous ev, so it outlives pt_start_render like the other arrays.
   pt_exposure_options exposure{};
@@ -320,3 +329,8 @@ int dev_read_exposure_meter(pt_renderer* r, const vec4* merged, pt_exposure_mete
 int dev_debug_exposure(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const uint32_t* rect, const pt_exposure_options* options,
                        pt_exposure_meter* out, float* scaled_out);
 int dev_debug_bloom(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const pt_bloom_options* options, float* out, float* pyramid_out);
+int dev_set_selection_options(pt_renderer* r, const pt_selection_options* o);
+int dev_set_selection(pt_renderer* r, const uint32_t* ids, uint32_t id_count);
+int dev_get_selection(const pt_renderer* r, uint32_t* ids_out, uint32_t capacity, uint32_t* count);
+int dev_debug_selection_overlay(pt_renderer* r, const uint8_t* rgba8_in, const float* coverage, uint32_t width, uint32_t height,
+                                const pt_selection_options* options, uint8_t* rgba8_out);

@@ -369,6 +369,50 @@ class Renderer:
         abi.check(self._lib, self._lib.pt_pick(self._h, x, y, C.byref(out)))
         return out
 
+    # selection overlay (include/ptamd.h, an additive extension of ABI 5): no counterpart in the reference's path tracer
+    def selectionOptions(self):
+        """The options in effect (pt_default_selection_options until setSelectionOptions is called)."""
+        if getattr(self, "_selection", None) is None:
+            self._selection = abi.SelectionOptions()
+            self._lib.pt_default_selection_options(C.byref(self._selection))
+        o = abi.SelectionOptions()
+        C.memmove(C.byref(o), C.byref(self._selection), C.sizeof(o))
+        return o
+
+    def setSelectionOptions(self, o=None, **fields):
+        """Sets `o` (default: the current options) with `fields` overriding it, e.g. setSelectionOptions(enabled=1, width=3.0,
+        outline_rgba=(0, 1, 1, 1)).  The options take effect at the next readbackRenderTarget / presentRenderTarget; no restart is needed."""
+        o = self.selectionOptions() if o is None else o
+        for k, v in fields.items():
+            setattr(o, k, (C.c_float * 4)(*v) if k in ("outline_rgba", "fill_rgba") else v)
+        abi.check(self._lib, self._lib.pt_set_selection_options(self._h, C.byref(o)))
+        self._selection = o
+
+    def setSelection(self, ids):
+        """The selected ids of selectionOptions().layer (any iterable; abi.MATTE_NONE selects the background; empty clears the selection)."""
+        ids = np.ascontiguousarray(np.asarray(list(ids), dtype=np.uint32).reshape(-1))
+        abi.check(self._lib, self._lib.pt_set_selection(self._h, ids.ctypes.data if ids.size else None, ids.size))
+
+    def selection(self):
+        """The stored selection: uint32 ids, ascending, without duplicates."""
+        n = C.c_uint32()
+        abi.check(self._lib, self._lib.pt_get_selection(self._h, None, 0, C.byref(n)))
+        out = np.empty(n.value, np.uint32)
+        abi.check(self._lib, self._lib.pt_get_selection(self._h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out
+
+    def debugSelectionOverlay(self, rgba8, coverage, options=None):
+        """The overlay kernel on a host (H, W, 4) uint8 target and an (H, W) float32 coverage image with `options` (default: the current
+        ones; `enabled` is not looked at): the target with the outline and the tint drawn."""
+        img = np.ascontiguousarray(rgba8, dtype=np.uint8)
+        h, w = img.shape[:2]
+        cov = np.ascontiguousarray(coverage, dtype=np.float32)
+        assert img.shape == (h, w, 4) and cov.shape == (h, w)
+        o = self.selectionOptions() if options is None else options
+        out = np.empty((h, w, 4), np.uint8)
+        abi.check(self._lib, self._lib.pt_debug_selection_overlay(self._h, img.ctypes.data, cov.ctypes.data, w, h, C.byref(o), out.ctypes.data))
+        return out
+
     def setGmonOptions(self, cap=1.0):
         """gmonOptions().cap (renderer_pt.hpp:71)."""
         o = abi.GmonOptions(cap)

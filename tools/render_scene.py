@@ -11,6 +11,7 @@ tracing (GMoN optional), fused post-process + tonemap — to an 8-bit PNG.
     python tools/render_scene.py builtin:c5 out.png --size 960 540 --spp 32 --auto-exposure --bloom 0.1
     python tools/render_scene.py builtin:c3 corner.png --size 1920 1080 --spp 4096 --region 1200,600,1500,800
     python tools/render_scene.py builtin:c3 out.png --size 960 540 --spp 32 --matte instance      (writes out.instance.png beside out.png)
+    python tools/render_scene.py builtin:c3 out.png --size 960 540 --spp 32 --select 497,498,530 --outline-width 3
 """
 import argparse, os, struct, sys, time, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -65,7 +66,19 @@ def main():
     ap.add_argument("--matte", choices=("instance", "material"), action="append", default=[],
                     help="keep ID mattes and write a false-colour image of this layer beside the picture (OUTPUT.instance.png / OUTPUT.material.png): "
                          "what every pixel's camera rays hit first, each id a colour, weighted by its share of the pixel's samples; may be given twice")
+    ap.add_argument("--select", default=None, metavar="ID[,ID...]",
+                    help="keep ID mattes and draw the selection overlay, an outline around these ids, onto the picture after the post-process")
+    ap.add_argument("--select-layer", choices=("instance", "material"), default="instance", help="what the ids of --select are")
+    ap.add_argument("--outline-width", type=float, default=2.0, metavar="W", help="width of the outline in pixels, 1 .. 16")
     a = ap.parse_args()
+    select = None
+    if a.select is not None:
+        try:
+            select = [int(v, 0) for v in a.select.split(",")]
+        except ValueError:
+            select = []
+        if not select or min(select) < 0 or max(select) > 0xFFFFFFFF or not 1.0 <= a.outline_width <= 16.0:
+            ap.error("--select takes ID[,ID...] (0xFFFFFFFF = the background) and --outline-width a width from 1 to 16")
     if a.despeckle is not None and not a.denoise:
         ap.error("--despeckle is a stage of the denoiser: it needs --denoise")
     region = None
@@ -107,8 +120,11 @@ def main():
         r.setAdaptiveOptions(enabled=1, threshold=a.adaptive)
     if region is not None:
         r.setRenderRegion(*region)
-    if a.matte:
+    if a.matte or select:
         r.setMatteOptions(enabled=1)
+    if select:
+        r.setSelectionOptions(enabled=1, layer=abi.MATTE_INSTANCE if a.select_layer == "instance" else abi.MATTE_MATERIAL, width=a.outline_width)
+        r.setSelection(select)
     flags = abi.FLAG_MULTISCATTER_GGX | (abi.FLAG_GMON if a.gmon > 1 else 0)
     r.startRender(sc, tuple(a.size), a.spp, gmonBuckets=max(1, a.gmon), flags=flags, max_bounces=a.bounces, nonfinite_policy=abi.NONFINITE_ZERO)
     t1 = time.time()
@@ -122,6 +138,9 @@ def main():
         m = r.readbackExposureMeter()   # (no smoothing: the ev a read resolves now is the one the image above got)
         print(f"auto exposure: {m.metered} pixels metered ({m.below} below, {m.above} above, {m.nonfinite} non-finite), mean log2 luminance {m.mean_log2:.3f}, "
               f"applied {m.ev:+.3f} EV (gain {m.gain:.4g})")
+    if select:
+        cov = r.readbackMatte(r.selectionOptions().layer, select)
+        print(f"selection: {len(r.selection())} {a.select_layer} ids cover {int((cov > 0).sum())} pixels ({float(cov.sum()):.1f} in all), outline {a.outline_width:g} px")
     for layer in dict.fromkeys(a.matte):
         slots = r.readbackMatteSlots(abi.MATTE_INSTANCE if layer == "instance" else abi.MATTE_MATERIAL)
         n = r.readbackSampleCounts()
