@@ -700,6 +700,42 @@ int pt_get_selection(const pt_renderer* r, uint32_t* ids_out, uint32_t capacity,
 int pt_debug_selection_overlay(pt_renderer* r, const uint8_t* rgba8_in, const float* coverage, uint32_t width, uint32_t height,
                                const pt_selection_options* options, uint8_t* rgba8_out);
 
+/* ---- transparent film (NEW, an additive extension of ABI 5: new entry points and one new struct, no existing struct changed) ----
+ * A render started while `enabled` is set keeps, beside the accumulator, one more W*H RGBA32F image, the FILM: per pixel the running mean
+ * (the accumulator's recurrence, in sample order, one IEEE fp32 operation each) of
+ *   x_s = the camera ray of sample s hit geometry ? {L_s.r, L_s.g, L_s.b, 1} : {0, 0, 0, 0}
+ * with L_s the sample's radiance after the non-finite policy (what the accumulator folds).  A ray that passes a stochastic alpha cut-out
+ * and then leaves the scene is a miss.  The miss case is a select: a NaN sample that missed contributes 0.  So film.rgb is the
+ * premultiplied foreground and film.a the coverage; at a pixel every sample of which hit, film.rgb is the accumulator's rgb bit for bit
+ * (without GMoN; under PT_FLAG_GMON the film is a plain running mean, as the AOVs are).  The bits do not depend on samples_in_flight or on
+ * the sequence of pt_render_step calls.  A region render leaves the film {0, 0, 0, 0} outside the rectangle; an adaptive render's tile
+ * holds the film of its own sample count.  Every other output of the render is the bits it is without the film.
+ * `backdrop` and `backdrop_rgb` are read by every pt_read_render_target / pt_present_render_target / pt_read_exposure_meter of a render
+ * that keeps a film (no restart is needed); they choose the image the display chain starts from, with a = film.a and base = film.rgb (with
+ * denoise.apply_to_target on a render that also keeps AOVs: the a-trous filter run over film.rgb in place of the accumulator; the
+ * luminance moments that drive it still describe the full radiance):
+ *   PT_BACKDROP_SCENE        the accumulator (or its denoised image): the chain of a render without a film, bit for bit
+ *   PT_BACKDROP_COLOR        base.c + backdrop_rgb.c * (1 - a) per channel; the target's alpha byte stays 255
+ *   PT_BACKDROP_TRANSPARENT  a > 0 ? base.c / a : 0, the unpremultiplied foreground; after the post-process the target's alpha byte is
+ *                            a quantised as the colour bytes are (<= 0 or NaN: 0, >= 1: 255, else (uint32)(a * 255 + 0.5)): straight alpha
+ * Outside a render region the composed source is 0 (alpha byte 0 when transparent).  Auto exposure, bloom and the exposure meter take the
+ * composed source.  The selection overlay draws after the alpha byte is written and never changes it.  backdrop_rgb is scene-linear, in
+ * the render's working space.  A backdrop other than SCENE on a render without a film, and on a device group, silently shows the accumulator.
+ * Memory: 4 B per path slot and 16 B per pixel, held only by a render that enabled the film (plus 16 B per pixel once a backdrop is shown).
+ * PT_ERR_INVALID_ARGUMENT (checked before the renderer): an unknown backdrop, a colour component that is negative or not finite.
+ * PT_ERR_UNSUPPORTED: enabled = 1 on a device group. */
+enum { PT_BACKDROP_SCENE = 0, PT_BACKDROP_COLOR = 1, PT_BACKDROP_TRANSPARENT = 2 };
+typedef struct pt_film_options {
+  uint32_t enabled;        /* keep the film for renders started from now on (read at pt_start_render); default 0 */
+  uint32_t backdrop;       /* default PT_BACKDROP_SCENE; read by every target read / present */
+  float backdrop_rgb[3];   /* finite and >= 0; default 0 */
+} pt_film_options;
+void pt_default_film_options(pt_film_options* o);
+int pt_set_film_options(pt_renderer* r, const pt_film_options* o);
+/* The film, W*H*4 floats {premultiplied foreground rgb, coverage}.  Blocks like pt_read_aov.  PT_ERR_BAD_STATE before pt_start_render and
+ * for a render started without the film. */
+int pt_read_film(pt_renderer* r, float* rgba_out);
+
 const char* pt_last_error(void);
 
 /* ---------------------------------------------------------------------------------------------------------- */

@@ -52,6 +52,9 @@
  *                                                                around and a tint over the selected ids, drawn onto the target after the
  *                                                                post-process (ptamd.h, ABI 5 extension); the options are handed over whenever a
  *                                                                target is asked for, the ids at once
+ *   (no counterpart; "film transparent" of other path tracers)   pt_film_options& filmOptions() / setFilmOptions(...), readbackFilm(): the foreground
+ *                                                                with alpha, and the backdrop a target shows behind it (ptamd.h, ABI 5 extension);
+ *                                                                `enabled` is handed over at startRender, the backdrop whenever a target is asked for
  * Error behaviour as the reference's: nothing throws; a failing call prints "renderer_pt: <message>" to stderr (the
  * reference prints and asserts, renderer_pt.cpp:402, 1044) and leaves the object in Status_Blocked; lastError() keeps the text.
  * Threading as the reference's: one caller thread per Renderer.
@@ -128,6 +131,7 @@ public:
     if (!check(pt_set_adaptive_options(m_pt, &m_adaptive))) return;  // (read here)
     if (!check(pt_set_render_region(m_pt, &m_region))) return;       // (read here)
     if (!check(pt_set_matte_options(m_pt, &m_matte))) return;        // (read here)
+    if (!check(pt_set_film_options(m_pt, &m_film))) return;          // (`enabled` is read here)
     if (!check(pt_start_render(m_pt, &scene, &p))) return;
     m_size = uint2{p.width, p.height};
     m_started = true;
@@ -290,6 +294,20 @@ public:
     if (n && !check(pt_get_selection(m_pt, out.data(), n, &n))) out.clear();
     return out;
   }
+  // Transparent film (ptamd.h, an additive extension of ABI 5): a render started with enabled set keeps the foreground's premultiplied
+  // radiance and its coverage beside the accumulator; `backdrop` chooses what presentRenderTarget / readbackRenderTarget of such a render
+  // show behind it (PT_BACKDROP_SCENE: the accumulator as ever, _COLOR: backdrop_rgb, _TRANSPARENT: nothing, with a straight-alpha target).
+  // Edited in place like bloomOptions(); `enabled` is read at startRender, the backdrop whenever a target is asked for.
+  [[nodiscard]] constexpr pt_film_options& filmOptions() { return m_film; }
+  void setFilmOptions(const pt_film_options& o) { m_film = o; }
+  // The film, W*H*4 floats {premultiplied foreground rgb, coverage}; empty for a render started without it.  Blocks.
+  [[nodiscard]] std::vector<float> readbackFilm() const {
+    std::vector<float> out;
+    if (!m_pt || !m_started) return out;
+    out.resize((size_t)m_size.x * m_size.y * 4);
+    if (!check(pt_read_film(m_pt, out.data()))) out.clear();
+    return out;
+  }
   void wait() const { if (m_pt && m_started) check(pt_wait(m_pt)); }
   [[nodiscard]] bool ok() const { return m_pt != nullptr && m_lastError.empty(); }
   [[nodiscard]] const std::string& lastError() const { return m_lastError; }
@@ -308,6 +326,7 @@ private:
     pt_default_render_region(&m_region);
     pt_default_matte_options(&m_matte);
     pt_default_selection_options(&m_selection);
+    pt_default_film_options(&m_film);
     std::vector<int32_t> ord(devices, devices + count);
     pt_create_info ci{};
     ci.abi_version = PT_ABI_VERSION;
@@ -332,7 +351,7 @@ private:
     return check(pt_set_gmon_options(m_pt, &m_gmonOptions)) && check(pt_set_post_options(m_pt, &post)) && check(pt_set_tonemap_options(m_pt, &tonemap)) &&
            check(pt_set_denoise_options(m_pt, &m_denoise)) && check(pt_set_despeckle_options(m_pt, &m_despeckle)) &&
            check(pt_set_exposure_options(m_pt, &m_autoExposure)) && check(pt_set_bloom_options(m_pt, &m_bloom)) &&
-           check(pt_set_selection_options(m_pt, &m_selection));
+           check(pt_set_selection_options(m_pt, &m_selection)) && check(pt_set_film_options(m_pt, &m_film));
   }
 
   pt_renderer* m_pt = nullptr;
@@ -357,6 +376,7 @@ private:
   pt_render_region m_region{};
   pt_matte_options m_matte{};
   pt_selection_options m_selection{};
+  pt_film_options m_film{};
   mutable void* m_presentStream = nullptr;
   mutable std::string m_lastError;
 };

@@ -258,6 +258,14 @@ class SelectionOptions(C.Structure):
                 ("outline_rgba", C.c_float * 4), ("fill_rgba", C.c_float * 4)]
 
 
+BACKDROP_SCENE, BACKDROP_COLOR, BACKDROP_TRANSPARENT = 0, 1, 2
+
+
+class FilmOptions(C.Structure):
+    """pt_film_options: the transparent film (`enabled`, read at pt_start_render) and the backdrop every target read puts behind it."""
+    _fields_ = [("enabled", C.c_uint32), ("backdrop", C.c_uint32), ("backdrop_rgb", C.c_float * 3)]
+
+
 class HitRecord(C.Structure):
     _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("instance", C.c_int32), ("primitive", C.c_int32)]
 
@@ -342,6 +350,9 @@ SYMBOLS = [
     ("pt_read_matte_slots", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     ("pt_read_matte", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     ("pt_pick", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PickResult)]),
+    ("pt_default_film_options", None, [C.POINTER(FilmOptions)]),
+    ("pt_set_film_options", C.c_int, [C.c_void_p, C.POINTER(FilmOptions)]),
+    ("pt_read_film", C.c_int, [C.c_void_p, C.c_void_p]),
     ("pt_default_selection_options", None, [C.POINTER(SelectionOptions)]),
     ("pt_set_selection_options", C.c_int, [C.c_void_p, C.POINTER(SelectionOptions)]),
     ("pt_set_selection", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),

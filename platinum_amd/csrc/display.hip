@@ -1,7 +1,8 @@
 // display.hip — everything between an HDR image and the RGBA8 render target: the options of the post-process, the tonemapper, the denoiser,
 // the firefly clamp, auto exposure, bloom and the selection overlay, and the display chain that runs them (enqueue_display at the end of this
-// file): source (merged | denoised | accumulator), auto exposure, bloom, k_postprocess, selection overlay.  No kernel lives here:
-// the launches are those of kernels.hip, denoise.hip, exposure.hip, bloom.hip, matte.hip and selection.hip, and the path tracer's driver
+// file): source (merged | film over a backdrop | denoised | accumulator), auto exposure, bloom, k_postprocess, the film's alpha
+// byte, selection overlay.  No kernel lives here:
+// the launches are those of kernels.hip, denoise.hip, exposure.hip, bloom.hip, matte.hip, selection.hip and film.hip, and the path tracer's driver
 // (renderer.hip) is reached through flush_pending and dev_wait.
 #include <hip/hip_runtime.h>
 
@@ -91,8 +92,9 @@ int dev_set_despeckle_options(pt_renderer* r, const pt_despeckle_options* o) {
   return PT_OK;
 }
 
-// The filter over the current image into r->denoised, enqueued on the renderer's stream (denoise.hip).  Samples pending are enqueued first.
-static int enqueue_denoise(pt_renderer* r) {
+// The filter over `colour` (the accumulator, or the film in its place: the guides, counts, region, options and firefly clamp are the same)
+// into r->denoised, enqueued on the renderer's stream (denoise.hip).  Samples pending are enqueued first.
+static int enqueue_denoise(pt_renderer* r, const vec4* colour) {
   { const int rc = flush_pending(r, true); if (rc != PT_OK) return rc; }
   const size_t npix = (size_t)r->S.width * r->S.height;
   PT_HIP(r->denoised.alloc(npix));
@@ -104,7 +106,7 @@ static int enqueue_denoise(pt_renderer* r) {
   DenoiseParams P;
   P.W = r->S.width; P.H = r->S.height;
   P.sigma_l = r->denoise.sigma_luminance; P.sigma_n = fminf(r->denoise.sigma_normal, kDnSigmaNormalMax); P.sigma_z = r->denoise.sigma_depth;
-  launch_denoise(r->stream, r->acc, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * npix, P.W, P.H, (uint32_t)r->launched, P,
+  launch_denoise(r->stream, colour, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * npix, P.W, P.H, (uint32_t)r->launched, P,
                  r->denoise.iterations, r->dn_guide.p, r->dn_aux.p, r->dn_col[0].p, r->dn_col[1].p, r->denoised.p,
                  r->adaptive ? r->ad_tile_n.p : nullptr,   // an adaptive render: each pixel's own sample count
                  r->rect,                                    // a region render: the region as an image of its own
@@ -119,7 +121,7 @@ int dev_read_denoised(pt_renderer* r, float* rgba_out) {
   if (!r->started || !r->aov) return fail(PT_ERR_BAD_STATE, "pt_read_denoised: the render was not started with AOVs enabled");
   int rc = dev_wait(r);
   if (rc != PT_OK) return rc;
-  if ((rc = enqueue_denoise(r)) != PT_OK) return rc;
+  if ((rc = enqueue_denoise(r, r->acc)) != PT_OK) return rc;
   PT_HIP(hipStreamSynchronize(r->stream));
   PT_HIP(hipMemcpy(rgba_out, r->denoised.p, sizeof(vec4) * (size_t)r->S.width * r->S.height, hipMemcpyDeviceToHost));
   return PT_OK;
@@ -338,19 +340,47 @@ int dev_debug_selection_overlay(pt_renderer* r, const uint8_t* rgba8_in, const f
   return PT_OK;
 }
 
+// ---- the film's options (film.hip; the film itself is the driver's, renderer.hip) ----
+extern "C" void pt_default_film_options(pt_film_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->backdrop = PT_BACKDROP_SCENE;
+}
+
+// (the options are checked before the renderer, as dev_set_selection_options)
+int dev_set_film_options(pt_renderer* r, const pt_film_options* o) {
+  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (const char* why = film_options_error(*o)) return fail(PT_ERR_INVALID_ARGUMENT, std::string("pt_set_film_options: ") + why);
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_film_options: null renderer");
+  r->film_opts = *o;
+  return PT_OK;
+}
+
 // ---- the display chain.  Everything is enqueued on r->stream; the callers below decide what is waited for. ----
 
 // The image the chain starts from: a group's merged image when one is given, else the denoised image (its filter enqueued here) of a
 // render that keeps AOVs and applies it to the target, else the accumulator.
+// Under a backdrop other than PT_BACKDROP_SCENE a render that keeps a film (never a group's merged image) starts from the film composed
+// over the backdrop instead (k_film_compose into r->film_src): base = film.rgb, or the same filter run over the film.
+static bool backdrop_shown(const pt_renderer* r, const vec4* merged) { return !merged && r->film && r->film_opts.backdrop != PT_BACKDROP_SCENE; }
+
 static int display_source(pt_renderer* r, const vec4* merged, const vec4** src) {
   *src = merged ? merged : r->acc;
-  if (merged || !r->aov || !r->denoise.apply_to_target) return PT_OK;
-  const int rc = enqueue_denoise(r);
-  *src = r->denoised.p;
-  return rc;
+  const bool backdrop = backdrop_shown(r, merged);
+  const vec4* base = backdrop ? r->film_img.p : r->acc;
+  if (!merged && r->aov && r->denoise.apply_to_target) {
+    if (const int rc = enqueue_denoise(r, base)) return rc;
+    *src = base = r->denoised.p;
+  }
+  if (!backdrop) return PT_OK;
+  PT_HIP(r->film_src.alloc((size_t)r->S.width * r->S.height));
+  launch_film_compose(r->stream, base, r->film_img.p, r->film_src.p, r->S.width, r->S.height, r->rect, r->film_opts);
+  PT_HIP(hipGetLastError());
+  *src = r->film_src.p;
+  return PT_OK;
 }
 
-// Source, auto exposure, bloom, post-process into r->render_target, selection overlay onto it: one step of the exposure smoothing state
+// Source, auto exposure, bloom, post-process into r->render_target, the film's alpha byte and the selection overlay onto it: one step of the exposure smoothing state
 // per call, and nothing allocated or launched for a stage that is disabled.  (A group's merged image gets no overlay: a group keeps no mattes.)
 static int enqueue_display(pt_renderer* r, const vec4* merged) {
   const vec4* src;
@@ -366,6 +396,11 @@ static int enqueue_display(pt_renderer* r, const vec4* merged) {
   pc.odt = PPMat3{odt.c0, odt.c1, odt.c2};
   launch_postprocess(r->stream, src, r->render_target.p, r->S.width, r->S.height, pc);
   PT_HIP(hipGetLastError());
+  // transparent film: the alpha byte from the composed source, before the overlay (which leaves alpha alone)
+  if (backdrop_shown(r, merged) && r->film_opts.backdrop == PT_BACKDROP_TRANSPARENT) {
+    launch_film_alpha(r->stream, r->render_target.p, r->film_src.p, (uint32_t)npix);
+    PT_HIP(hipGetLastError());
+  }
   if (!merged && selection_drawn(r)) { const int rc = enqueue_selection(r); if (rc != PT_OK) return rc; }
   return PT_OK;
 }

@@ -789,6 +789,16 @@ int pt_pick(pt_renderer* r, uint32_t x, uint32_t y, pt_pick_result* out) {
   return fail(PT_ERR_BAD_STATE, "pt_pick: a device group does not keep ID mattes");
 }
 
+// The film is per device too: a group merges accumulators, and its merged image is shown without a backdrop
+int pt_set_film_options(pt_renderer* r, const pt_film_options* o) {
+  return set_unless_enabled(r, dev_set_film_options, o, "pt_set_film_options: a device group does not keep a film");
+}
+
+int pt_read_film(pt_renderer* r, float* rgba_out) {
+  if (!is_group(r)) return dev_read_film(r, rgba_out);
+  return fail(PT_ERR_BAD_STATE, "pt_read_film: a device group does not keep a film");
+}
+
 // The selection overlay draws from the ID mattes, which a group does not keep: its merged path shows no overlay.  The options go to every
 // member (never enabled); the set is held by the first member.
 int pt_set_selection_options(pt_renderer* r, const pt_selection_options* o) {

@@ -1,6 +1,6 @@
 // pt_tilefold.h — what every per-sample side channel of a batch shares, defined ONCE (DESIGN.md §3 "Tile folds and queue walks"): how a
 // fold kernel places its tile in the image, the order in which a round of eight samples goes through LDS, and the walk over a segment of the
-// bounce-0 queue that fills a side channel.  kernels.hip (Lbuf), denoise.hip (Abuf) and matte.hip (Mbuf) call it; a new side channel starts
+// bounce-0 queue that fills a side channel.  kernels.hip (Lbuf), denoise.hip (Abuf), matte.hip (Mbuf) and film.hip (Fbuf) call it; a new side channel starts
 // here.  The first two are plain integer functions (PT_HD) that tests/emu also compiles for the host; the walk is device code.
 #pragma once
 #include "pt_device.h"

@@ -150,6 +150,11 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
       ScopedTimer t(r, K_ACCUM);
       launch_matte_ids(s, r->grid, r->scene_d.p, r->path_state(cur), r->hit.p, seg, r->Mbuf.p);
     }
+    // the film of a render that keeps one (film.hip): which of the same camera rays hit anything (timed with the accumulate class, as the mattes)
+    if (b == 0 && mode == BATCH_RENDER && r->film) {
+      ScopedTimer t(r, K_ACCUM);
+      launch_film_flags(s, r->grid, r->path_state(cur), r->hit.p, seg, r->Fbuf.p);
+    }
     {
       ScopedTimer t(r, K_SHADE);
       launch_shade(s, r->shade_grid, r->scene_d.p, r->path_state(cur), r->path_state(cur ^ 1), r->hit.p, r->shadow_queue(), r->Lbuf.p, seg, (uint32_t)cur, ctr, b);
@@ -182,6 +187,7 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
       launch_accumulate_aov(s, r->aov_img.p, r->aov_img.p + npix, r->aov_img.p + 2 * (size_t)npix, r->Abuf.p, r->Lbuf.p, S.width, S.height, ns, n0,
                             r->params.nonfinite_policy, tiles);
     if (r->matte) launch_accumulate_matte(s, r->matte_slots.p, r->Mbuf.p, S.width, S.height, ns, tiles);
+    if (r->film) launch_accumulate_film(s, r->film_img.p, r->Lbuf.p, r->Fbuf.p, S.width, S.height, ns, n0, r->params.nonfinite_policy, tiles);
   }
   // a batch that ends at a checkpoint (flush_pending never lets one straddle it): test the active tiles, compact the list into the other
   // buffer, and send the new count to pinned host memory
@@ -313,6 +319,7 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   pt_default_render_region(&r->region_opts);
   pt_default_matte_options(&r->matte_opts);
   pt_default_selection_options(&r->selection);
+  pt_default_film_options(&r->film_opts);
   r->device = device_ordinal;
   if (const char* e = getenv("PTAMD_REFILL")) r->refill_threshold = (uint32_t)atoi(e);
   if (const char* e = getenv("PTAMD_TILES_PER_SEG")) r->tiles_per_seg_override = (uint32_t)std::max(0, atoi(e));  // tuning knobs
@@ -586,6 +593,8 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
   if (!aov) { r->Abuf.release(); r->aov_img.release(); }  // (an AOV-off render holds nothing more than before)
   const bool matte = r->matte_opts.enabled != 0;
   if (!matte) { r->Mbuf.release(); r->matte_slots.release(); r->matte_ids.release(); r->matte_cov.release(); }   // (nor does a matte-off render)
+  const bool film = r->film_opts.enabled != 0;
+  if (!film) { r->Fbuf.release(); r->film_img.release(); r->film_src.release(); }   // (nor a film-off render)
   const bool adaptive = r->adaptive_opts.enabled != 0;
   const bool region = r->region_opts.enabled != 0;
   if (!adaptive) r->release_checkpoints();                  // (nor does an adaptive-off render;
@@ -596,7 +605,7 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
   // so every grid is sized for its own kernel's occupancy.
   {
     const uint64_t budget = queue_budget(free_device_bytes(), r->queue_bytes_held(), r->cam_entries.bytes_held() + r->cam_count.bytes_held(), aov,
-                                         r->Abuf.bytes_held(), matte, r->Mbuf.bytes_held());
+                                         r->Abuf.bytes_held(), matte, r->Mbuf.bytes_held(), film, r->Fbuf.bytes_held());
     pt_queue_plan plan{};
     const char* why = "";
     const int rc = plan_queues(p->width, p->height, p->spp, p->samples_in_flight, budget, r->tiles_per_seg_override, r->seg_bands, &plan, &why);
@@ -656,6 +665,11 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
     launch_matte_clear(r->stream, r->matte_slots.p, (size_t)npix);   // every slot {PT_MATTE_NONE, 0}
     PT_HIP(hipGetLastError());
   }
+  if (film) {
+    PT_HIP(r->Fbuf.alloc(r->Lbuf.n));
+    PT_HIP(r->film_img.alloc(npix));
+    PT_HIP(hipMemsetAsync(r->film_img.p, 0, sizeof(vec4) * npix, r->stream));
+  }
   if (adaptive || region) {  // every tile the rectangle touches starts active (the whole frame: [0, tiles)), ascending (adaptive.hip)
     const Rect rect = render_rect(r, p);
     const uint32_t tiles = tile_count(p->width, p->height);
@@ -694,6 +708,7 @@ void reset_progress(pt_renderer* r, const pt_render_params* p) {
   r->total = p->spp;
   r->aov = r->denoise.enabled != 0;
   r->matte = r->matte_opts.enabled != 0;
+  r->film = r->film_opts.enabled != 0;
   r->adaptive = r->adaptive_opts.enabled != 0;
   r->region = r->region_opts.enabled != 0;
   r->vtiles = r->adaptive || r->region;
@@ -917,6 +932,16 @@ int dev_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out) {
   if (rc != PT_OK) return rc;
   const size_t npix = (size_t)r->S.width * r->S.height;
   PT_HIP(hipMemcpy(rgba_out, r->aov_img.p + aov * npix, sizeof(vec4) * npix, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+// ---- the film (film.hip, pt_film.h; its options and its place in the display chain: display.hip) ------------------------------------------
+int dev_read_film(pt_renderer* r, float* rgba_out) {
+  if (!r || !rgba_out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (!r->started || !r->film) return fail(PT_ERR_BAD_STATE, "pt_read_film: the render was not started with the film enabled");
+  int rc = dev_wait(r);
+  if (rc != PT_OK) return rc;
+  PT_HIP(hipMemcpy(rgba_out, r->film_img.p, sizeof(vec4) * (size_t)r->S.width * r->S.height, hipMemcpyDeviceToHost));
   return PT_OK;
 }
 

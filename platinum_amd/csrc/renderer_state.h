@@ -16,6 +16,7 @@
 #include "denoise.h"
 #include "exposure.h"
 #include "math_probe.h"
+#include "film.h"
 #include "matte.h"
 #include "pt_math_probe.h"
 #include "selection.h"
@@ -155,6 +156,13 @@ struct pt_renderer {
   DevBuf<uint32_t> sel_ids;         // sel_set on the device
   DevBuf<float> sel_cov;            // the set's coverage image: what k_selection_overlay reads
   bool sel_no_early_out = false;    // $PTAMD_NO_SELECTION_EARLY_OUT: blocks that see no coverage run on (the A/B switch; the same bytes)
+  // transparent film (film.hip): only a render started with film_opts.enabled allocates or launches any of it; the composed
+  // source only once a target of such a render is read under a backdrop other than PT_BACKDROP_SCENE
+  pt_film_options film_opts{};
+  bool film = false;                // this render keeps a film
+  DevBuf<uint32_t> Fbuf;            // 1: the camera ray hit, 0: it missed, per Lbuf entry
+  DevBuf<vec4> film_img;            // [pixel] {premultiplied foreground, coverage} running means
+  DevBuf<vec4> film_src;            // the film over the backdrop: what the display chain starts from
   // auto exposure (exposure.hip): nothing is allocated or launched until a target is read with exposure.enabled, or the
   // meter is read.  The record holds the previous ev, so it outlives pt_start_render like the other arrays.
   pt_exposure_options exposure{};
@@ -246,6 +254,7 @@ struct pt_renderer {
     started = false;
     aov = false;
     matte = false;
+    film = false;
     cam_lists = false;
     adaptive = false;
     region = false;
@@ -312,6 +321,7 @@ int dev_set_matte_options(pt_renderer* r, const pt_matte_options* o);
 int dev_read_matte_slots(pt_renderer* r, uint32_t layer, pt_matte_slot* out);
 int dev_read_matte(pt_renderer* r, uint32_t layer, const uint32_t* ids, uint32_t id_count, float* coverage_out);
 int dev_pick(pt_renderer* r, uint32_t x, uint32_t y, pt_pick_result* out);
+int dev_read_film(pt_renderer* r, float* rgba_out);
 
 // ---- display (display.hip): the stages' options, and the chain from an HDR image to the RGBA8 target.  `merged`: a device group's merged
 //      image on this renderer's device, which the group has waited for; NULL = the renderer's own image ----
@@ -322,6 +332,7 @@ int dev_set_despeckle_options(pt_renderer* r, const pt_despeckle_options* o);
 int dev_set_exposure_options(pt_renderer* r, const pt_exposure_options* o);
 int dev_reset_exposure(pt_renderer* r);
 int dev_set_bloom_options(pt_renderer* r, const pt_bloom_options* o);
+int dev_set_film_options(pt_renderer* r, const pt_film_options* o);
 int dev_read_denoised(pt_renderer* r, float* rgba_out);
 int dev_read_render_target(pt_renderer* r, const vec4* merged, uint8_t* rgba8_out);                // blocks
 int dev_present(pt_renderer* r, const vec4* merged, void** device_rgba8_out, void** stream_out);  // enqueues only

@@ -413,6 +413,33 @@ class Renderer:
         abi.check(self._lib, self._lib.pt_debug_selection_overlay(self._h, img.ctypes.data, cov.ctypes.data, w, h, C.byref(o), out.ctypes.data))
         return out
 
+    # transparent film (include/ptamd.h, an additive extension of ABI 5): no counterpart in the reference's path tracer
+    def filmOptions(self):
+        """The options in effect (pt_default_film_options until setFilmOptions is called)."""
+        if getattr(self, "_film", None) is None:
+            self._film = abi.FilmOptions()
+            self._lib.pt_default_film_options(C.byref(self._film))
+        o = abi.FilmOptions()
+        C.memmove(C.byref(o), C.byref(self._film), C.sizeof(o))
+        return o
+
+    def setFilmOptions(self, o=None, **fields):
+        """Sets `o` (default: the current options) with `fields` overriding it, e.g. setFilmOptions(enabled=1,
+        backdrop=abi.BACKDROP_COLOR, backdrop_rgb=(0.2, 0.2, 0.2)).  `enabled` takes effect at the next startRender; the backdrop at the
+        next readbackRenderTarget / presentRenderTarget, without a restart."""
+        o = self.filmOptions() if o is None else o
+        for k, v in fields.items():
+            setattr(o, k, (C.c_float * 3)(*v) if k == "backdrop_rgb" else v)
+        abi.check(self._lib, self._lib.pt_set_film_options(self._h, C.byref(o)))
+        self._film = o
+
+    def readbackFilm(self):
+        """(H, W, 4) float32 {premultiplied foreground rgb, coverage} of a render started with the film enabled."""
+        w, h = self.size
+        out = np.empty((h, w, 4), dtype=np.float32)
+        abi.check(self._lib, self._lib.pt_read_film(self._h, out.ctypes.data))
+        return out
+
     def setGmonOptions(self, cap=1.0):
         """gmonOptions().cap (renderer_pt.hpp:71)."""
         o = abi.GmonOptions(cap)

@@ -12,6 +12,8 @@ tracing (GMoN optional), fused post-process + tonemap — to an 8-bit PNG.
     python tools/render_scene.py builtin:c3 corner.png --size 1920 1080 --spp 4096 --region 1200,600,1500,800
     python tools/render_scene.py builtin:c3 out.png --size 960 540 --spp 32 --matte instance      (writes out.instance.png beside out.png)
     python tools/render_scene.py builtin:c3 out.png --size 960 540 --spp 32 --select 497,498,530 --outline-width 3
+    python tools/render_scene.py builtin:c5 cutout.png --size 960 540 --spp 64 --film transparent     (an RGBA PNG with straight alpha)
+    python tools/render_scene.py builtin:c5 studio.png --size 960 540 --spp 64 --film 0.18,0.18,0.18  (the objects over a flat colour)
 """
 import argparse, os, struct, sys, time, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -70,7 +72,18 @@ def main():
                     help="keep ID mattes and draw the selection overlay, an outline around these ids, onto the picture after the post-process")
     ap.add_argument("--select-layer", choices=("instance", "material"), default="instance", help="what the ids of --select are")
     ap.add_argument("--outline-width", type=float, default=2.0, metavar="W", help="width of the outline in pixels, 1 .. 16")
+    ap.add_argument("--film", default=None, metavar="transparent|R,G,B",
+                    help="keep the transparent film and show the objects without the environment behind them: 'transparent' writes straight alpha "
+                         "into the PNG, R,G,B (scene-linear, >= 0) puts that flat colour behind them; the environment still lights the scene")
     a = ap.parse_args()
+    backdrop = None
+    if a.film is not None and a.film != "transparent":
+        try:
+            backdrop = tuple(float(v) for v in a.film.split(","))
+        except ValueError:
+            backdrop = ()
+        if len(backdrop) != 3 or not all(0.0 <= v < float("inf") for v in backdrop):
+            ap.error("--film takes 'transparent' or R,G,B with finite components >= 0")
     select = None
     if a.select is not None:
         try:
@@ -125,6 +138,8 @@ def main():
     if select:
         r.setSelectionOptions(enabled=1, layer=abi.MATTE_INSTANCE if a.select_layer == "instance" else abi.MATTE_MATERIAL, width=a.outline_width)
         r.setSelection(select)
+    if a.film is not None:
+        r.setFilmOptions(enabled=1, backdrop=abi.BACKDROP_TRANSPARENT if backdrop is None else abi.BACKDROP_COLOR, backdrop_rgb=backdrop or (0.0, 0.0, 0.0))
     flags = abi.FLAG_MULTISCATTER_GGX | (abi.FLAG_GMON if a.gmon > 1 else 0)
     r.startRender(sc, tuple(a.size), a.spp, gmonBuckets=max(1, a.gmon), flags=flags, max_bounces=a.bounces, nonfinite_policy=abi.NONFINITE_ZERO)
     t1 = time.time()
@@ -138,6 +153,10 @@ def main():
         m = r.readbackExposureMeter()   # (no smoothing: the ev a read resolves now is the one the image above got)
         print(f"auto exposure: {m.metered} pixels metered ({m.below} below, {m.above} above, {m.nonfinite} non-finite), mean log2 luminance {m.mean_log2:.3f}, "
               f"applied {m.ev:+.3f} EV (gain {m.gain:.4g})")
+    if a.film is not None:
+        alpha = r.readbackFilm()[..., 3]
+        print(f"film: coverage 1 on {int((alpha == 1).sum())} pixels, 0 on {int((alpha == 0).sum())}, fractional on {int(((alpha > 0) & (alpha < 1)).sum())}; "
+              + ("straight alpha written" if backdrop is None else "backdrop %g, %g, %g" % backdrop))
     if select:
         cov = r.readbackMatte(r.selectionOptions().layer, select)
         print(f"selection: {len(r.selection())} {a.select_layer} ids cover {int((cov > 0).sum())} pixels ({float(cov.sum()):.1f} in all), outline {a.outline_width:g} px")
