@@ -736,6 +736,76 @@ int pt_set_film_options(pt_renderer* r, const pt_film_options* o);
  * for a render started without the film. */
 int pt_read_film(pt_renderer* r, float* rgba_out);
 
+/* ---- pass views (NEW, an additive extension of ABI 5: new entry points and new structs, no existing struct changed) ----
+ * A view selector for the render target: what pt_read_render_target / pt_present_render_target show of the data the render keeps beside the
+ * accumulator.  The options are read by every target read and present (no restart); under the default, PT_VIEW_BEAUTY, nothing is allocated
+ * or launched and every output keeps its bits.
+ *   PT_VIEW_BEAUTY   the display chain as it is
+ *   PT_VIEW_ALBEDO   the albedo AOV (a scene-linear colour in the working space) in place of the chain's source; auto exposure and bloom are
+ *                    skipped (the exposure smoothing state does not advance), the post-process and the tonemapper run as ever
+ * Every other view is a DATA view: one kernel writes the target directly with alpha byte 255, in place of source, exposure, bloom,
+ * post-process and the film's alpha byte; nothing of the colour pipeline touches data.  With n the pixel's sample count as
+ * pt_read_sample_counts gives it, a pixel with n = 0 is (0, 0, 0, 255); every step is one IEEE fp32 operation and the bytes are quantised as
+ * the post-process quantises them (<= 0 or NaN: 0, >= 1: 255, else (uint32)(c * 255 + 0.5)):
+ *   PT_VIEW_NORMAL   c = N.c * 0.5 + 0.5 of the normal AOV's rgb (a miss-only pixel is mid grey)
+ *   PT_VIEW_DEPTH    with h the normal AOV's alpha and r the moments AOV's .r, a pixel is valid when n > 0, h > 0 and d = r / h is finite and
+ *                    >= 0.  auto_range: z0, z1 = the min and max of d over the valid pixels of the render's rectangle, found on the device
+ *                    (0, 0 when there is none); else z0, z1 = depth_min, depth_max.  t = z1 > z0 ? (d - z0) / (z1 - z0) : 0 clamped to [0, 1],
+ *                    v = 1 - t (near is bright), colour = ramp(v); an invalid pixel is black
+ *   PT_VIEW_ALPHA    v = film.a, grey
+ *   PT_VIEW_MATTE    colour = the sum over the slots k = 0 .. 7 of `layer`, in order from 0, of w_k * col(id_k), w_k = (float)count_k / (float)n
+ *                    (a slot with count 0 is skipped); col(PT_MATTE_NONE) = 0, else with x = id hashed by x ^= x >> 16, x *= 0x7feb352d,
+ *                    x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16: col.c = (float)byte_c(x) / 255 * 0.75 + 0.25 for bytes 0, 1, 2 = r, g, b.
+ *                    Samples that found no slot darken the pixel.
+ *   PT_VIEW_SAMPLES  v = min((float)n / (float)spp, 1), colour = ramp(v): the heat map of an adaptive or region render
+ *   PT_VIEW_NOISE    err = the relative standard error of adaptive sampling's criterion from the luminance moments m1, m2 (PT_AOV_MOMENTS .g, .b,
+ *                    the same bits as the adaptive moments); v = 1 when n < 2 or err is NaN, else min(err / noise_max, 1); colour = ramp(v)
+ *   ramp             PT_RAMP_GREY: (v, v, v).  PT_RAMP_HEAT: s = v * 4, k = min((int)s, 3), f = s - k, c = a_k + (a_(k+1) - a_k) * f over the
+ *                    stops blue (0,0,1), cyan (0,1,1), green (0,1,0), yellow (1,1,0), red (1,0,0).  A NaN v is drawn as v = 1.
+ * Availability: ALBEDO, NORMAL and DEPTH need a render that keeps AOVs, ALPHA the film, MATTE the ID mattes, NOISE AOVs or adaptive sampling;
+ * SAMPLES is always available.  A view whose data the render does not keep, and any view on a device group's merged image, silently shows
+ * BEAUTY (as a film backdrop does on a render without a film); pt_view_stats.shown says which view the target shows.
+ * The selection overlay still draws on top of every view.  Present never blocks: the depth range lives in a 16-byte device record the view
+ * kernel reads.  pt_read_exposure_meter ignores the view.
+ * PT_ERR_INVALID_ARGUMENT (checked before the renderer): view >= PT_VIEW_COUNT, a layer or ramp that does not exist, auto_range > 1, with
+ * auto_range = 0 a depth_min or depth_max that is not finite, depth_min < 0 or depth_min >= depth_max, a noise_max that is not finite or <= 0.
+ * Never refused on a device group: the options go to every member. */
+enum { PT_VIEW_BEAUTY = 0, PT_VIEW_ALBEDO = 1, PT_VIEW_NORMAL = 2, PT_VIEW_DEPTH = 3,
+       PT_VIEW_ALPHA = 4, PT_VIEW_MATTE = 5, PT_VIEW_SAMPLES = 6, PT_VIEW_NOISE = 7, PT_VIEW_COUNT = 8 };
+enum { PT_RAMP_GREY = 0, PT_RAMP_HEAT = 1 };
+typedef struct pt_view_options {
+  uint32_t view;        /* default PT_VIEW_BEAUTY; read by every target read / present, no restart */
+  uint32_t layer;       /* PT_VIEW_MATTE: PT_MATTE_INSTANCE (default) or PT_MATTE_MATERIAL */
+  uint32_t ramp;        /* DEPTH, SAMPLES, NOISE: PT_RAMP_GREY (default) or PT_RAMP_HEAT */
+  uint32_t auto_range;  /* DEPTH: 1 (default) = range from the frame's own nearest / farthest hit, found on the device */
+  float depth_min, depth_max;   /* DEPTH with auto_range = 0; defaults 0, 1 */
+  float noise_max;      /* NOISE: the relative error drawn as full scale; default 0.1 */
+  uint32_t _pad;
+} pt_view_options;
+void pt_default_view_options(pt_view_options* o);
+int pt_set_view_options(pt_renderer* r, const pt_view_options* o);
+
+typedef struct pt_view_stats {
+  uint32_t shown;          /* the view the target shows now (BEAUTY when the asked one is not available) */
+  uint32_t depth_pixels;   /* DEPTH: pixels that entered the range */
+  float depth_min, depth_max;   /* DEPTH: z0, z1 as used */
+} pt_view_stats;
+/* Blocks; runs the range pass when DEPTH is shown (0, 0, 0 under any other view) and draws nothing.  PT_ERR_BAD_STATE before pt_start_render. */
+int pt_read_view_stats(pt_renderer* r, pt_view_stats* out);
+
+typedef struct pt_view_inputs {   /* any pointer the view does not read may be NULL */
+  const float *albedo, *normal, *moments, *film;   /* W*H*4 floats each, as pt_read_aov / pt_read_film give them */
+  const pt_matte_slot* slots;                        /* W*H*PT_MATTE_SLOTS of one layer, as pt_read_matte_slots */
+  const uint32_t* counts;                            /* W*H, as pt_read_sample_counts */
+  uint32_t spp;                                      /* SAMPLES: the render's spp */
+} pt_view_inputs;
+/* The data-view kernels on uploaded inputs with buffers of their own: needs no render and leaves the renderer's state alone.  `rect`
+ * {x0, y0, x1, y1} (NULL = the whole image) is the rectangle the depth range is taken over.  1 .. 2^28 pixels.  PT_ERR_INVALID_ARGUMENT also
+ * for BEAUTY and ALBEDO (they go through the post-process), for a NULL input the view reads (counts always), and for SAMPLES with spp = 0.
+ * stats_out may be NULL. */
+int pt_debug_view(pt_renderer* r, const pt_view_inputs* in, uint32_t width, uint32_t height, const uint32_t* rect,
+                  const pt_view_options* options, uint8_t* rgba8_out, pt_view_stats* stats_out);
+
 const char* pt_last_error(void);
 
 /* ---------------------------------------------------------------------------------------------------------- */

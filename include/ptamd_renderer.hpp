@@ -55,6 +55,9 @@
  *   (no counterpart; "film transparent" of other path tracers)   pt_film_options& filmOptions() / setFilmOptions(...), readbackFilm(): the foreground
  *                                                                with alpha, and the backdrop a target shows behind it (ptamd.h, ABI 5 extension);
  *                                                                `enabled` is handed over at startRender, the backdrop whenever a target is asked for
+ *   (no counterpart; the "render pass" drop-down of a viewport)    pt_view_options& viewOptions(), viewStats(): what the target shows of the AOVs, the
+ *                                                                mattes, the film's alpha and the sampling (ptamd.h, ABI 5 extension); handed
+ *                                                                over whenever a target is asked for
  * Error behaviour as the reference's: nothing throws; a failing call prints "renderer_pt: <message>" to stderr (the
  * reference prints and asserts, renderer_pt.cpp:402, 1044) and leaves the object in Status_Blocked; lastError() keeps the text.
  * Threading as the reference's: one caller thread per Renderer.
@@ -308,6 +311,17 @@ public:
     if (!check(pt_read_film(m_pt, out.data()))) out.clear();
     return out;
   }
+  // Pass views (ptamd.h, an additive extension of ABI 5): `view` chooses what presentRenderTarget / readbackRenderTarget show: the beauty,
+  // or the albedo, the normals, the depth, the film's alpha, the ID mattes, the sample counts or the noise estimate the render keeps.  A view
+  // whose data the render does not keep silently shows the beauty.  Edited in place like bloomOptions(); read whenever a target is asked for.
+  [[nodiscard]] constexpr pt_view_options& viewOptions() { return m_view; }
+  // The view the target shows now and, under PT_VIEW_DEPTH, the range in use.  Blocks; draws nothing.  shown = PT_VIEW_BEAUTY on failure.
+  [[nodiscard]] pt_view_stats viewStats() const {
+    pt_view_stats s{};
+    if (!m_pt || !m_started || !pushOptions()) return s;
+    if (!check(pt_read_view_stats(m_pt, &s))) s = pt_view_stats{};
+    return s;
+  }
   void wait() const { if (m_pt && m_started) check(pt_wait(m_pt)); }
   [[nodiscard]] bool ok() const { return m_pt != nullptr && m_lastError.empty(); }
   [[nodiscard]] const std::string& lastError() const { return m_lastError; }
@@ -327,6 +341,7 @@ private:
     pt_default_matte_options(&m_matte);
     pt_default_selection_options(&m_selection);
     pt_default_film_options(&m_film);
+    pt_default_view_options(&m_view);
     std::vector<int32_t> ord(devices, devices + count);
     pt_create_info ci{};
     ci.abi_version = PT_ABI_VERSION;
@@ -351,7 +366,8 @@ private:
     return check(pt_set_gmon_options(m_pt, &m_gmonOptions)) && check(pt_set_post_options(m_pt, &post)) && check(pt_set_tonemap_options(m_pt, &tonemap)) &&
            check(pt_set_denoise_options(m_pt, &m_denoise)) && check(pt_set_despeckle_options(m_pt, &m_despeckle)) &&
            check(pt_set_exposure_options(m_pt, &m_autoExposure)) && check(pt_set_bloom_options(m_pt, &m_bloom)) &&
-           check(pt_set_selection_options(m_pt, &m_selection)) && check(pt_set_film_options(m_pt, &m_film));
+           check(pt_set_selection_options(m_pt, &m_selection)) && check(pt_set_film_options(m_pt, &m_film)) &&
+           check(pt_set_view_options(m_pt, &m_view));
   }
 
   pt_renderer* m_pt = nullptr;
@@ -377,6 +393,7 @@ private:
   pt_matte_options m_matte{};
   pt_selection_options m_selection{};
   pt_film_options m_film{};
+  pt_view_options m_view{};
   mutable void* m_presentStream = nullptr;
   mutable std::string m_lastError;
 };

@@ -266,6 +266,28 @@ class FilmOptions(C.Structure):
     _fields_ = [("enabled", C.c_uint32), ("backdrop", C.c_uint32), ("backdrop_rgb", C.c_float * 3)]
 
 
+(VIEW_BEAUTY, VIEW_ALBEDO, VIEW_NORMAL, VIEW_DEPTH, VIEW_ALPHA, VIEW_MATTE, VIEW_SAMPLES, VIEW_NOISE, VIEW_COUNT) = range(9)
+VIEW_NAMES = ("beauty", "albedo", "normal", "depth", "alpha", "matte", "samples", "noise")
+RAMP_GREY, RAMP_HEAT = 0, 1
+
+
+class ViewOptions(C.Structure):
+    """pt_view_options: what the render target shows (read by every target read / present, no restart)."""
+    _fields_ = [("view", C.c_uint32), ("layer", C.c_uint32), ("ramp", C.c_uint32), ("auto_range", C.c_uint32),
+                ("depth_min", C.c_float), ("depth_max", C.c_float), ("noise_max", C.c_float), ("_pad", C.c_uint32)]
+
+
+class ViewStats(C.Structure):
+    """pt_view_stats: the view the target shows now, and under DEPTH the range in use."""
+    _fields_ = [("shown", C.c_uint32), ("depth_pixels", C.c_uint32), ("depth_min", C.c_float), ("depth_max", C.c_float)]
+
+
+class ViewInputs(C.Structure):
+    """pt_view_inputs: host images for pt_debug_view; a pointer the view does not read may be None."""
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("moments", C.c_void_p), ("film", C.c_void_p),
+                ("slots", C.c_void_p), ("counts", C.c_void_p), ("spp", C.c_uint32)]
+
+
 class HitRecord(C.Structure):
     _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("instance", C.c_int32), ("primitive", C.c_int32)]
 
@@ -358,6 +380,11 @@ SYMBOLS = [
     ("pt_set_selection", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     ("pt_get_selection", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("pt_debug_selection_overlay", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(SelectionOptions), C.c_void_p]),
+    ("pt_default_view_options", None, [C.POINTER(ViewOptions)]),
+    ("pt_set_view_options", C.c_int, [C.c_void_p, C.POINTER(ViewOptions)]),
+    ("pt_read_view_stats", C.c_int, [C.c_void_p, C.POINTER(ViewStats)]),
+    ("pt_debug_view", C.c_int, [C.c_void_p, C.POINTER(ViewInputs), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(ViewOptions), C.c_void_p,
+                                C.POINTER(ViewStats)]),
     ("pt_last_error", C.c_char_p, []),
     ("pt_get_constants", C.c_int, [C.c_void_p, C.POINTER(Constants)]),
     ("pt_get_lights", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),

@@ -1,8 +1,9 @@
 // display.hip — everything between an HDR image and the RGBA8 render target: the options of the post-process, the tonemapper, the denoiser,
 // the firefly clamp, auto exposure, bloom and the selection overlay, and the display chain that runs them (enqueue_display at the end of this
 // file): source (merged | film over a backdrop | denoised | accumulator), auto exposure, bloom, k_postprocess, the film's alpha
-// byte, selection overlay.  No kernel lives here:
-// the launches are those of kernels.hip, denoise.hip, exposure.hip, bloom.hip, matte.hip, selection.hip and film.hip, and the path tracer's driver
+// byte, selection overlay; or, under a pass view, the albedo AOV as the source, or a data view in place of everything up to
+// the overlay.  No kernel lives here:
+// the launches are those of kernels.hip, denoise.hip, exposure.hip, bloom.hip, matte.hip, selection.hip, film.hip and view.hip, and the path tracer's driver
 // (renderer.hip) is reached through flush_pending and dev_wait.
 #include <hip/hip_runtime.h>
 
@@ -356,6 +357,151 @@ int dev_set_film_options(pt_renderer* r, const pt_film_options* o) {
   return PT_OK;
 }
 
+// ---- pass views (view.hip) ----
+extern "C" void pt_default_view_options(pt_view_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->view = PT_VIEW_BEAUTY; o->layer = PT_MATTE_INSTANCE; o->ramp = PT_RAMP_GREY;
+  o->auto_range = 1u;
+  o->depth_min = 0.0f; o->depth_max = 1.0f;
+  o->noise_max = 0.1f;
+}
+
+// (the options are checked before the renderer, as dev_set_film_options)
+int dev_set_view_options(pt_renderer* r, const pt_view_options* o) {
+  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (const char* why = view_options_error(*o)) return fail(PT_ERR_INVALID_ARGUMENT, std::string("pt_set_view_options: ") + why);
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_view_options: null renderer");
+  r->view_opts = *o;
+  return PT_OK;
+}
+
+// The view this render's target shows now: the one asked for when the render keeps its data, else the beauty (a group's merged image always).
+static uint32_t view_now(const pt_renderer* r, const vec4* merged) {
+  return view_shown(r->view_opts.view, r->aov, r->film, r->matte, r->adaptive, merged != nullptr);
+}
+
+// what the render keeps, as the view kernels read it: the pixel's n as dev_read_sample_counts gives it
+static ViewImages view_images(const pt_renderer* r) {
+  const size_t npix = (size_t)r->S.width * r->S.height;
+  ViewImages I{};
+  if (r->aov) { I.normal = r->aov_img.p + PT_AOV_NORMAL * npix; I.moments = r->aov_img.p + PT_AOV_MOMENTS * npix; }
+  if (r->adaptive) I.mom2 = r->ad_mom.p;
+  if (r->film) I.film = r->film_img.p;
+  if (r->matte) { I.slots = r->matte_slots.p + r->view_opts.layer * (kMatteSlots / 2u); I.slot_stride = kMattePixelVec4; }
+  I.tile_n = r->vtiles ? r->ad_tile_n.p : nullptr;
+  I.n_uniform = (uint32_t)r->launched;
+  I.rect = r->rect;
+  I.width = r->S.width; I.height = r->S.height;
+  return I;
+}
+
+// the record, allocated on first use
+static int view_record(pt_renderer* r) {
+  if (r->view_rec.p) return PT_OK;
+  PT_HIP(r->view_rec.alloc(1));
+  return PT_OK;
+}
+
+// A data view in place of source, exposure, bloom, post-process and the film's alpha byte, enqueued on the renderer's stream: the depth
+// range first when the view asks for the frame's own (the record stays on the device: present does not block), then k_view_pass into
+// r->render_target.
+static int enqueue_view(pt_renderer* r, uint32_t view) {
+  const size_t npix = (size_t)r->S.width * r->S.height;
+  if (r->render_target.n != npix) PT_HIP(r->render_target.alloc(npix));
+  const ViewImages I = view_images(r);
+  ViewParams P = view_params(r->view_opts, r->params.spp);
+  P.view = view;
+  if (view == PT_VIEW_DEPTH && P.auto_range) {
+    if (const int rc = view_record(r)) return rc;
+    PT_HIP(launch_view_range(r->stream, I, r->view_rec.p, false));
+  }
+  launch_view_pass(r->stream, I, P, r->view_rec.p, r->render_target.p);
+  PT_HIP(hipGetLastError());
+  return PT_OK;
+}
+
+// What a target read would show now, and under DEPTH the range it would use: the range pass alone, waited for.  Nothing is drawn.
+int dev_read_view_stats(pt_renderer* r, const vec4* merged, pt_view_stats* out) {
+  if (!r || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (!r->started) return fail(PT_ERR_BAD_STATE, "pt_read_view_stats before pt_start_render");
+  if (merged) PT_HIP(hipSetDevice(r->device));
+  else if (const int rc = dev_wait(r)) return rc;
+  memset(out, 0, sizeof(*out));
+  out->shown = view_now(r, merged);
+  if (out->shown != PT_VIEW_DEPTH) return PT_OK;
+  if (const int rc = view_record(r)) return rc;
+  PT_HIP(launch_view_range(r->stream, view_images(r), r->view_rec.p, true));
+  PT_HIP(hipStreamSynchronize(r->stream));
+  ViewRecord rec;
+  PT_HIP(hipMemcpy(&rec, r->view_rec.p, sizeof(rec), hipMemcpyDeviceToHost));
+  out->depth_pixels = rec.count;
+  view_range(view_params(r->view_opts, r->params.spp), rec, &out->depth_min, &out->depth_max);
+  return PT_OK;
+}
+
+// the two kernels on uploaded inputs, with buffers and a record of their own; the renderer's own state is untouched
+int dev_debug_view(pt_renderer* r, const pt_view_inputs* in, uint32_t width, uint32_t height, const uint32_t* rect, const pt_view_options* options,
+                   uint8_t* rgba8_out, pt_view_stats* stats_out) {
+  if (!options || !in || !rgba8_out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (const char* why = view_options_error(*options)) return fail(PT_ERR_INVALID_ARGUMENT, std::string("pt_debug_view: ") + why);
+  const uint32_t view = options->view;
+  if (!view_is_data(view)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_view: BEAUTY and ALBEDO go through the post-process, not through a view kernel");
+  if (width == 0 || height == 0 || (uint64_t)width * height > (1ull << 28)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_view: the image must hold 1..2^28 pixels");
+  Rect rc{0u, 0u, width, height};
+  if (rect) {
+    rc = Rect{rect[0], rect[1], rect[2], rect[3]};
+    if (rc.x0 >= rc.x1 || rc.y0 >= rc.y1 || rc.x1 > width || rc.y1 > height) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_view: the rectangle is empty or does not fit the image");
+  }
+  const bool reads_normal = view == PT_VIEW_NORMAL || view == PT_VIEW_DEPTH, reads_moments = view == PT_VIEW_DEPTH || view == PT_VIEW_NOISE;
+  if (!in->counts || (reads_normal && !in->normal) || (reads_moments && !in->moments) || (view == PT_VIEW_ALPHA && !in->film) ||
+      (view == PT_VIEW_MATTE && !in->slots))
+    return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_view: a null input that the view reads");
+  if (view == PT_VIEW_SAMPLES && in->spp == 0u) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_view: SAMPLES needs spp >= 1");
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_view: null renderer");
+  PT_HIP(hipSetDevice(r->device));
+  const size_t npix = (size_t)width * height;
+  DevBuf<vec4> normal, moments, film;
+  DevBuf<uint4> slots;
+  DevBuf<uint32_t> counts, target;
+  DevBuf<ViewRecord> rec;
+  ViewImages I{};
+  PT_HIP(counts.alloc(npix)); PT_HIP(target.alloc(npix)); PT_HIP(rec.alloc(1));
+  PT_HIP(hipMemcpyAsync(counts.p, in->counts, sizeof(uint32_t) * npix, hipMemcpyHostToDevice, r->stream));
+  const auto upload = [&](DevBuf<vec4>& b, const float* src, const vec4** dst) -> int {
+    PT_HIP(b.alloc(npix));
+    PT_HIP(hipMemcpyAsync(b.p, src, sizeof(vec4) * npix, hipMemcpyHostToDevice, r->stream));
+    *dst = b.p;
+    return PT_OK;
+  };
+  if (reads_normal) { if (const int e = upload(normal, in->normal, &I.normal)) return e; }
+  if (reads_moments) { if (const int e = upload(moments, in->moments, &I.moments)) return e; }
+  if (view == PT_VIEW_ALPHA) { if (const int e = upload(film, in->film, &I.film)) return e; }
+  if (view == PT_VIEW_MATTE) {
+    PT_HIP(slots.alloc(npix * (kMatteSlots / 2u)));
+    PT_HIP(hipMemcpyAsync(slots.p, in->slots, sizeof(pt_matte_slot) * kMatteSlots * npix, hipMemcpyHostToDevice, r->stream));
+    I.slots = slots.p; I.slot_stride = kMatteSlots / 2u;
+  }
+  I.counts = counts.p;
+  I.rect = rc;
+  I.width = width; I.height = height;
+  const ViewParams P = view_params(*options, in->spp);
+  if (view == PT_VIEW_DEPTH) PT_HIP(launch_view_range(r->stream, I, rec.p, true));
+  else PT_HIP(hipMemsetAsync(rec.p, 0, sizeof(ViewRecord), r->stream));
+  launch_view_pass(r->stream, I, P, rec.p, target.p);
+  PT_HIP(hipGetLastError());
+  PT_HIP(hipStreamSynchronize(r->stream));
+  PT_HIP(hipMemcpy(rgba8_out, target.p, 4 * npix, hipMemcpyDeviceToHost));
+  if (stats_out) {
+    ViewRecord h;
+    PT_HIP(hipMemcpy(&h, rec.p, sizeof(h), hipMemcpyDeviceToHost));
+    memset(stats_out, 0, sizeof(*stats_out));
+    stats_out->shown = view;
+    if (view == PT_VIEW_DEPTH) { stats_out->depth_pixels = h.count; view_range(P, h, &stats_out->depth_min, &stats_out->depth_max); }
+  }
+  return PT_OK;
+}
+
 // ---- the display chain.  Everything is enqueued on r->stream; the callers below decide what is waited for. ----
 
 // The image the chain starts from: a group's merged image when one is given, else the denoised image (its filter enqueued here) of a
@@ -382,12 +528,24 @@ static int display_source(pt_renderer* r, const vec4* merged, const vec4** src) 
 
 // Source, auto exposure, bloom, post-process into r->render_target, the film's alpha byte and the selection overlay onto it: one step of the exposure smoothing state
 // per call, and nothing allocated or launched for a stage that is disabled.  (A group's merged image gets no overlay: a group keeps no mattes.)
+// Pass views.  BEAUTY: the chain as above.  A data view: k_view_pass writes the target in place of everything up to the
+// overlay, which still draws on top; the exposure smoothing state does not advance.  ALBEDO: the albedo AOV is the source, auto exposure and
+// bloom are skipped (the state does not advance either) and no alpha byte is written: the composed film is not made.
 static int enqueue_display(pt_renderer* r, const vec4* merged) {
-  const vec4* src;
-  if (const int rc = display_source(r, merged, &src)) return rc;
-  if (r->exposure.enabled) { const int rc = enqueue_exposure(r, &src); if (rc != PT_OK) return rc; }
-  if (r->bloom.enabled) { const int rc = enqueue_bloom(r, &src); if (rc != PT_OK) return rc; }
+  const uint32_t view = view_now(r, merged);
   const size_t npix = (size_t)r->S.width * r->S.height;
+  if (view_is_data(view)) {
+    if (const int rc = enqueue_view(r, view)) return rc;
+    if (selection_drawn(r)) { const int rc = enqueue_selection(r); if (rc != PT_OK) return rc; }
+    return PT_OK;
+  }
+  const vec4* src;
+  if (view == PT_VIEW_ALBEDO) src = r->aov_img.p + PT_AOV_ALBEDO * npix;
+  else {
+    if (const int rc = display_source(r, merged, &src)) return rc;
+    if (r->exposure.enabled) { const int rc = enqueue_exposure(r, &src); if (rc != PT_OK) return rc; }
+    if (r->bloom.enabled) { const int rc = enqueue_bloom(r, &src); if (rc != PT_OK) return rc; }
+  }
   if (r->render_target.n != npix) PT_HIP(r->render_target.alloc(npix));
   PostConstants pc;
   pc.post = r->post;
@@ -397,7 +555,7 @@ static int enqueue_display(pt_renderer* r, const vec4* merged) {
   launch_postprocess(r->stream, src, r->render_target.p, r->S.width, r->S.height, pc);
   PT_HIP(hipGetLastError());
   // transparent film: the alpha byte from the composed source, before the overlay (which leaves alpha alone)
-  if (backdrop_shown(r, merged) && r->film_opts.backdrop == PT_BACKDROP_TRANSPARENT) {
+  if (view == PT_VIEW_BEAUTY && backdrop_shown(r, merged) && r->film_opts.backdrop == PT_BACKDROP_TRANSPARENT) {
     launch_film_alpha(r->stream, r->render_target.p, r->film_src.p, (uint32_t)npix);
     PT_HIP(hipGetLastError());
   }

@@ -818,6 +818,23 @@ int pt_debug_selection_overlay(pt_renderer* r, const uint8_t* rgba8_in, const fl
   return dev_debug_selection_overlay(is_group(r) ? r->group->shards[0] : r, rgba8_in, coverage, width, height, options, rgba8_out);
 }
 
+// Pass views read what a group does not keep, and a group's merged image shows the beauty whatever is asked: the options are never refused
+// and go to every member, like the bloom options.
+int pt_set_view_options(pt_renderer* r, const pt_view_options* o) { return on_members(r, dev_set_view_options, o); }
+
+int pt_read_view_stats(pt_renderer* r, pt_view_stats* out) {
+  if (!is_group(r)) return dev_read_view_stats(r, nullptr, out);
+  if (!out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  pt_renderer* m;
+  if (const int rc = displaying_member(r, "pt_read_view_stats before pt_start_render", &m)) return rc;
+  return dev_read_view_stats(m, r->group->merged, out);
+}
+
+int pt_debug_view(pt_renderer* r, const pt_view_inputs* in, uint32_t width, uint32_t height, const uint32_t* rect, const pt_view_options* options,
+                  uint8_t* rgba8_out, pt_view_stats* stats_out) {
+  return dev_debug_view(is_group(r) ? r->group->shards[0] : r, in, width, height, rect, options, rgba8_out, stats_out);
+}
+
 int pt_get_stats(pt_renderer* r, pt_stats* out) {
   if (!r || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
   return is_group(r) ? group_get_stats(r, out) : dev_get_stats(r, out);

@@ -320,6 +320,7 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   pt_default_matte_options(&r->matte_opts);
   pt_default_selection_options(&r->selection);
   pt_default_film_options(&r->film_opts);
+  pt_default_view_options(&r->view_opts);
   r->device = device_ordinal;
   if (const char* e = getenv("PTAMD_REFILL")) r->refill_threshold = (uint32_t)atoi(e);
   if (const char* e = getenv("PTAMD_TILES_PER_SEG")) r->tiles_per_seg_override = (uint32_t)std::max(0, atoi(e));  // tuning knobs

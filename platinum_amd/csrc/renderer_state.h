@@ -20,6 +20,7 @@
 #include "matte.h"
 #include "pt_math_probe.h"
 #include "selection.h"
+#include "view.h"
 #include "kernels.h"
 #include "pt_bvh.h"
 
@@ -163,6 +164,10 @@ struct pt_renderer {
   DevBuf<uint32_t> Fbuf;            // 1: the camera ray hit, 0: it missed, per Lbuf entry
   DevBuf<vec4> film_img;            // [pixel] {premultiplied foreground, coverage} running means
   DevBuf<vec4> film_src;            // the film over the backdrop: what the display chain starts from
+  // pass views (view.hip): nothing is allocated or launched under PT_VIEW_BEAUTY.  The record (the depth view's range) is
+  // allocated by the first target read under DEPTH with auto_range, or the first pt_read_view_stats, and outlives pt_start_render like exp_rec.
+  pt_view_options view_opts{};
+  DevBuf<ViewRecord> view_rec;      // [1] what k_view_range found: read by k_view_pass on the device, never through the host
   // auto exposure (exposure.hip): nothing is allocated or launched until a target is read with exposure.enabled, or the
   // meter is read.  The record holds the previous ev, so it outlives pt_start_render like the other arrays.
   pt_exposure_options exposure{};
@@ -345,3 +350,7 @@ int dev_set_selection(pt_renderer* r, const uint32_t* ids, uint32_t id_count);
 int dev_get_selection(const pt_renderer* r, uint32_t* ids_out, uint32_t capacity, uint32_t* count);
 int dev_debug_selection_overlay(pt_renderer* r, const uint8_t* rgba8_in, const float* coverage, uint32_t width, uint32_t height,
                                 const pt_selection_options* options, uint8_t* rgba8_out);
+int dev_set_view_options(pt_renderer* r, const pt_view_options* o);
+int dev_read_view_stats(pt_renderer* r, const vec4* merged, pt_view_stats* out);                   // blocks; draws nothing
+int dev_debug_view(pt_renderer* r, const pt_view_inputs* in, uint32_t width, uint32_t height, const uint32_t* rect, const pt_view_options* options,
+                   uint8_t* rgba8_out, pt_view_stats* stats_out);

@@ -440,6 +440,55 @@ class Renderer:
         abi.check(self._lib, self._lib.pt_read_film(self._h, out.ctypes.data))
         return out
 
+    # pass views (include/ptamd.h, an additive extension of ABI 5): no counterpart in the reference's path tracer
+    def viewOptions(self):
+        """The options in effect (pt_default_view_options until setViewOptions is called)."""
+        if getattr(self, "_view", None) is None:
+            self._view = abi.ViewOptions()
+            self._lib.pt_default_view_options(C.byref(self._view))
+        o = abi.ViewOptions()
+        C.memmove(C.byref(o), C.byref(self._view), C.sizeof(o))
+        return o
+
+    def setViewOptions(self, o=None, **fields):
+        """Sets `o` (default: the current options) with `fields` overriding it, e.g. setViewOptions(view=abi.VIEW_DEPTH,
+        ramp=abi.RAMP_HEAT).  The view takes effect at the next readbackRenderTarget / presentRenderTarget; no restart is needed."""
+        o = self.viewOptions() if o is None else o
+        for k, v in fields.items():
+            setattr(o, k, v)
+        abi.check(self._lib, self._lib.pt_set_view_options(self._h, C.byref(o)))
+        self._view = o
+
+    def viewStats(self):
+        """abi.ViewStats: the view the target shows now (VIEW_BEAUTY when the one asked for is not available) and, under VIEW_DEPTH, the
+        range in use.  Blocks; draws nothing."""
+        s = abi.ViewStats()
+        abi.check(self._lib, self._lib.pt_read_view_stats(self._h, C.byref(s)))
+        return s
+
+    def debugView(self, size, options=None, rect=None, spp=1, counts=None, normal=None, moments=None, film=None, slots=None):
+        """The data-view kernels on host images of `size` = (W, H) with `options` (default: the current ones): ((H, W, 4) uint8,
+        abi.ViewStats).  counts (H, W) uint32; normal / moments / film (H, W, 4) float32; slots (H, W, MATTE_SLOTS) of one layer."""
+        w, h = size
+        keep = []
+
+        def ptr(a, dtype, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            assert a.shape == shape, (a.shape, shape)
+            keep.append(a)
+            return a.ctypes.data
+
+        inp = abi.ViewInputs(None, ptr(normal, np.float32, (h, w, 4)), ptr(moments, np.float32, (h, w, 4)), ptr(film, np.float32, (h, w, 4)),
+                             ptr(slots, np.dtype(abi.MATTE_SLOT_DTYPE), (h, w, abi.MATTE_SLOTS)), ptr(counts, np.uint32, (h, w)), spp)
+        o = self.viewOptions() if options is None else options
+        r = None if rect is None else (C.c_uint32 * 4)(*rect)
+        out = np.empty((h, w, 4), np.uint8)
+        stats = abi.ViewStats()
+        abi.check(self._lib, self._lib.pt_debug_view(self._h, C.byref(inp), w, h, r, C.byref(o), out.ctypes.data, C.byref(stats)))
+        return out, stats
+
     def setGmonOptions(self, cap=1.0):
         """gmonOptions().cap (renderer_pt.hpp:71)."""
         o = abi.GmonOptions(cap)

@@ -14,6 +14,8 @@ tracing (GMoN optional), fused post-process + tonemap — to an 8-bit PNG.
     python tools/render_scene.py builtin:c3 out.png --size 960 540 --spp 32 --select 497,498,530 --outline-width 3
     python tools/render_scene.py builtin:c5 cutout.png --size 960 540 --spp 64 --film transparent     (an RGBA PNG with straight alpha)
     python tools/render_scene.py builtin:c5 studio.png --size 960 540 --spp 64 --film 0.18,0.18,0.18  (the objects over a flat colour)
+    python tools/render_scene.py builtin:c3 ids.png --size 960 540 --spp 32 --view matte --matte instance   (the picture itself shows the ids)
+    python tools/render_scene.py builtin:c3 heat.png --size 960 540 --spp 256 --adaptive 0.05 --view samples --ramp heat
 """
 import argparse, os, struct, sys, time, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -75,7 +77,12 @@ def main():
     ap.add_argument("--film", default=None, metavar="transparent|R,G,B",
                     help="keep the transparent film and show the objects without the environment behind them: 'transparent' writes straight alpha "
                          "into the PNG, R,G,B (scene-linear, >= 0) puts that flat colour behind them; the environment still lights the scene")
+    ap.add_argument("--view", choices=abi.VIEW_NAMES, default="beauty",
+                    help="what the picture shows (the render target's pass view, drawn on the device): the beauty, or the albedo, normals, depth, "
+                         "film alpha, ID mattes (the layer of --matte, default instance), sample counts or noise estimate; what the view needs is kept")
+    ap.add_argument("--ramp", choices=("grey", "heat"), default="grey", help="with --view depth / samples / noise: grey, or blue-cyan-green-yellow-red")
     a = ap.parse_args()
+    view = abi.VIEW_NAMES.index(a.view)
     backdrop = None
     if a.film is not None and a.film != "transparent":
         try:
@@ -133,13 +140,20 @@ def main():
         r.setAdaptiveOptions(enabled=1, threshold=a.adaptive)
     if region is not None:
         r.setRenderRegion(*region)
-    if a.matte or select:
+    if a.matte or select or view == abi.VIEW_MATTE:
         r.setMatteOptions(enabled=1)
+    if view in (abi.VIEW_ALBEDO, abi.VIEW_NORMAL, abi.VIEW_DEPTH) or (view == abi.VIEW_NOISE and a.adaptive is None):
+        r.setDenoiseOptions(enabled=1)       # (keeps the AOVs; the filter runs only with --denoise)
     if select:
         r.setSelectionOptions(enabled=1, layer=abi.MATTE_INSTANCE if a.select_layer == "instance" else abi.MATTE_MATERIAL, width=a.outline_width)
         r.setSelection(select)
     if a.film is not None:
         r.setFilmOptions(enabled=1, backdrop=abi.BACKDROP_TRANSPARENT if backdrop is None else abi.BACKDROP_COLOR, backdrop_rgb=backdrop or (0.0, 0.0, 0.0))
+    elif view == abi.VIEW_ALPHA:
+        r.setFilmOptions(enabled=1)
+    if view != abi.VIEW_BEAUTY:
+        r.setViewOptions(view=view, ramp=abi.RAMP_HEAT if a.ramp == "heat" else abi.RAMP_GREY,
+                         layer=abi.MATTE_MATERIAL if a.matte[:1] == ["material"] else abi.MATTE_INSTANCE)
     flags = abi.FLAG_MULTISCATTER_GGX | (abi.FLAG_GMON if a.gmon > 1 else 0)
     r.startRender(sc, tuple(a.size), a.spp, gmonBuckets=max(1, a.gmon), flags=flags, max_bounces=a.bounces, nonfinite_policy=abi.NONFINITE_ZERO)
     t1 = time.time()
@@ -149,6 +163,9 @@ def main():
     r.setPostProcessOptions(po)
     img = r.readbackRenderTarget()
     write_png_rgba8(a.output, img)
+    if view != abi.VIEW_BEAUTY:
+        vs = r.viewStats()
+        print(f"view: {abi.VIEW_NAMES[vs.shown]}" + (f", depth {vs.depth_min:.4g} .. {vs.depth_max:.4g} over {vs.depth_pixels} pixels" if vs.shown == abi.VIEW_DEPTH else ""))
     if a.auto_exposure is not None:
         m = r.readbackExposureMeter()   # (no smoothing: the ev a read resolves now is the one the image above got)
         print(f"auto exposure: {m.metered} pixels metered ({m.below} below, {m.above} above, {m.nonfinite} non-finite), mean log2 luminance {m.mean_log2:.3f}, "
