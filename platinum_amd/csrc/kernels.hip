@@ -694,10 +694,11 @@ k_camera_primary(DeviceScene S, PathState st, vec4* __restrict__ Lbuf, vec4* __r
 // Per block, once: the read-mostly tables every hit touches are staged in LDS — the Halton entries of the dimensions
 // this bounce can reach (5 + 7b .. 15 + 12b: raygen consumes 4, every bounce 7 to 12), the area-light table (binary
 // search + one record per NEE sample) and the E_avg / E_ms_avg energy tables.
-// Per hit: geometry + material + BSDF set-up, then next-event estimation whose shadow record is compacted into the shadow
-// queue right away, then the BSDF sample / throughput / roulette and the compaction of the survivor.  NEE before the
-// sample (each random number is addressed by its dimension, so the order does not matter) means the shadow record is
-// not held in registers across the sampling code.
+// Per hit: geometry + material (NEE's draws run under their gathers), the light sample, then the BSDF set-up and the NEE
+// eval on energy-table taps that were all issued together (wo's and the light direction's: one round trip instead of four),
+// the shadow record compacted into the shadow queue right away, then the BSDF sample / throughput / roulette and the
+// compaction of the survivor.  NEE before the sample (each random number is addressed by its dimension, so the order does
+// not matter) means the shadow record is not held in registers across the sampling code.
 #ifndef PT_SHADE_WAVES
 #define PT_SHADE_WAVES 4   // waves per SIMD the kernel is compiled for (128 VGPRs; 14 spill to scratch)
 #endif
@@ -707,7 +708,7 @@ k_camera_primary(DeviceScene S, PathState st, vec4* __restrict__ Lbuf, vec4* __r
 constexpr uint32_t kShadeBlock = PT_SHADE_BLOCK;
 constexpr uint32_t kShadeHalton = 128;  // staged Halton window (entries); dimensions beyond it are read from HBM
 constexpr uint32_t kShadeLights = 64;   // staged area lights; a bigger table is read from HBM
-constexpr int kLutE = 128, kLutEavg = 128, kLutEavgMs = 32;  // table shapes (checked by load_luts)
+constexpr int kLutE = 128, kLutEavg = 128, kLutEavgMs = 32, kLut3 = 32;  // table shapes (checked by load_luts); kLut3: EMs, ETransIn, ETransOut
 constexpr uint32_t kBinCap = 128;       // a bin is emptied as soon as it holds 64 entries, and a scan step adds at most 64
 
 __global__ void __launch_bounds__(PT_SHADE_BLOCK, (PT_SHADE_WAVES * 4 * 64) / PT_SHADE_BLOCK)
@@ -744,10 +745,10 @@ k_shade(const DeviceScene* __restrict__ Sp, PathState sin, PathState sout, const
   ShadeTables T;
   T.luts.E = Lut{S.luts.E.d, kLutE, kLutE, 1, 0};
   T.luts.Eavg = Lut{lds_Eavg, kLutEavg, 1, 1, 1};
-  T.luts.EMs = Lut{S.luts.EMs.d, S.luts.EMs.w, S.luts.EMs.h, S.luts.EMs.depth, 0};
+  T.luts.EMs = Lut{S.luts.EMs.d, kLut3, kLut3, kLut3, 0};
   T.luts.EavgMs = Lut{lds_EavgMs, kLutEavgMs, kLutEavgMs, 1, 1};
-  T.luts.ETransIn = Lut{S.luts.ETransIn.d, S.luts.ETransIn.w, S.luts.ETransIn.h, S.luts.ETransIn.depth, 0};
-  T.luts.ETransOut = Lut{S.luts.ETransOut.d, S.luts.ETransOut.w, S.luts.ETransOut.h, S.luts.ETransOut.depth, 0};
+  T.luts.ETransIn = Lut{S.luts.ETransIn.d, kLut3, kLut3, kLut3, 0};
+  T.luts.ETransOut = Lut{S.luts.ETransOut.d, kLut3, kLut3, kLut3, 0};
   T.halton = HaltonTab{S.halton, lds_halton, halton_base, halton_count};
   T.lights = lights_in_lds ? lds_lights : S.light_recs;
   T.light_cdf = S.light_cdf;
@@ -872,12 +873,20 @@ k_shade(const DeviceScene* __restrict__ Sp, PathState sin, PathState sout, const
         in.tri = tri;
         ShadeGeom g;
         ShadingContext sc;
-        shade_geometry(S, in, g, sc);
-        const BSDF bsdf(sc, S.flags, T.luts, g.wo);
+        // ---- the gathers behind the ShadeRec are started, NEE's three draws (VALU + LDS only) run under them ----
+        const ShadeGeomRaw raw = shade_geometry_fetch(S, in);
+        const NeeDraws draws = shade_nee_draws(T, in);
+        shade_geometry_finish(S, in, raw, g, sc);
+        // ---- the light sample first (it needs no table), then the energy-table taps of wo and of the light direction are issued
+        //      together and waited for once (pt_shade.h shade_issue / shade_land) ----
+        const NeeLight light = shade_nee_light(S, T, in, g, sc, draws);
+        BSDF bsdf(sc, S.flags, T.luts);
+        const ShadeFlight flight = shade_issue(g, bsdf, light);
+        const BSDF::DirTerms light_terms = shade_land(bsdf, flight);
         // ---- NEE; its shadow ray goes to this segment of the shadow queue now (ballot over the lanes in here) ----
         uint32_t dim_rr;
         {
-          const NeeOut nee = shade_nee(S, T, in, g, sc, bsdf, in.dim + 6);
+          const NeeOut nee = shade_nee_eval(S, T, in, g, bsdf, light, light_terms);
           dim_rr = nee.dim;
           const unsigned long long m = __ballot(nee.shadow);
           if (nee.shadow) {

@@ -16,13 +16,21 @@ enum SampleFlags {  // defs.metal:264-272
   Sample_Diffuse = 1 << 3, Sample_Glossy = 1 << 4, Sample_Specular = 1 << 5,
 };
 
+// A lookup is split into FETCH (axes -> addresses -> raw taps) and RESOLVE (the lerps): a caller that needs several
+// lookups whose coordinates do not depend on each other's values issues all the fetches first and resolves afterwards,
+// so that the taps travel together instead of one group per round trip.  lut1 / lut2 / lut3 are resolve(fetch(...)):
+// the arithmetic has one spelling.
 struct LutAxis { int i0, i1; float w; };
+// Total over the floats: the texel index is taken from floor(x) clamped to [-1, 1e9] FIRST (a NaN clamps to -1; no table
+// has 1e9 texels on an axis), so the float -> int conversion is always defined and every address lies inside the table —
+// also for a coordinate that is only fetched speculatively and never used.  For every coordinate whose conversion was
+// defined before, i0, i1 and w are what they were (w comes from the unclamped floor).
 PT_HD LutAxis lut_axis(float c, int n) {
   float x = c * (float)n - 0.5f;
   float fl = floorf(x);
   LutAxis a;
   a.w = x - fl;
-  int i = (int)fl;
+  int i = (int)fminf(fmaxf(fl, -1.0f), 1.0e9f);
   a.i0 = i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
   int j = i + 1;
   a.i1 = j < 0 ? 0 : (j > n - 1 ? n - 1 : j);
@@ -30,27 +38,34 @@ PT_HD LutAxis lut_axis(float c, int n) {
 }
 // one texel: from the block's LDS copy when the table was staged there, from HBM (global_load) otherwise
 PT_HD float lut_tap(const Lut& l, int i) { return l.lds ? l.d[i] : ldg(&l.d[i]); }
-PT_HD float lut1(const Lut& l, float cx) {
-  LutAxis ax = lut_axis(cx, l.w);
-  float a = lut_tap(l, ax.i0), b = lut_tap(l, ax.i1);
-  return a + (b - a) * ax.w;
+struct LutTaps1 { float a, b, wx; };
+struct LutTaps2 { float t00, t01, t10, t11, wx, wy; };
+struct LutTaps3 { LutTaps2 lo, hi; float wz; };
+PT_HD LutTaps1 lut1_fetch(const Lut& l, const LutAxis& ax) { return {lut_tap(l, ax.i0), lut_tap(l, ax.i1), ax.w}; }
+PT_HD LutTaps2 lut2_fetch(const Lut& l, int base, const LutAxis& ax, const LutAxis& ay) {
+  const int W = l.w;
+  return {lut_tap(l, base + ay.i0 * W + ax.i0), lut_tap(l, base + ay.i0 * W + ax.i1),
+          lut_tap(l, base + ay.i1 * W + ax.i0), lut_tap(l, base + ay.i1 * W + ax.i1), ax.w, ay.w};
 }
-PT_HD float lut2_slice(const Lut& l, int base, int W, const LutAxis& ax, const LutAxis& ay) {
-  float t00 = lut_tap(l, base + ay.i0 * W + ax.i0), t01 = lut_tap(l, base + ay.i0 * W + ax.i1);
-  float t10 = lut_tap(l, base + ay.i1 * W + ax.i0), t11 = lut_tap(l, base + ay.i1 * W + ax.i1);
-  float a = t00 + (t01 - t00) * ax.w;
-  float b = t10 + (t11 - t10) * ax.w;
-  return a + (b - a) * ay.w;
+PT_HD LutTaps2 lut2_fetch(const Lut& l, const LutAxis& ax, const LutAxis& ay) { return lut2_fetch(l, 0, ax, ay); }
+PT_HD LutTaps3 lut3_fetch(const Lut& l, const LutAxis& ax, const LutAxis& ay, const LutAxis& az) {
+  return {lut2_fetch(l, az.i0 * (l.w * l.h), ax, ay), lut2_fetch(l, az.i1 * (l.w * l.h), ax, ay), az.w};
 }
-PT_HD float lut2(const Lut& l, float cx, float cy) {
-  LutAxis ax = lut_axis(cx, l.w), ay = lut_axis(cy, l.h);
-  return lut2_slice(l, 0, l.w, ax, ay);
+PT_HD float lut_resolve(const LutTaps1& t) { return t.a + (t.b - t.a) * t.wx; }
+PT_HD float lut_resolve(const LutTaps2& t) {
+  float a = t.t00 + (t.t01 - t.t00) * t.wx;
+  float b = t.t10 + (t.t11 - t.t10) * t.wx;
+  return a + (b - a) * t.wy;
 }
+PT_HD float lut_resolve(const LutTaps3& t) {
+  float a = lut_resolve(t.lo);
+  float b = lut_resolve(t.hi);
+  return a + (b - a) * t.wz;
+}
+PT_HD float lut1(const Lut& l, float cx) { return lut_resolve(lut1_fetch(l, lut_axis(cx, l.w))); }
+PT_HD float lut2(const Lut& l, float cx, float cy) { return lut_resolve(lut2_fetch(l, lut_axis(cx, l.w), lut_axis(cy, l.h))); }
 PT_HD float lut3(const Lut& l, float cx, float cy, float cz) {
-  LutAxis ax = lut_axis(cx, l.w), ay = lut_axis(cy, l.h), az = lut_axis(cz, l.depth);
-  float a = lut2_slice(l, az.i0 * (l.w * l.h), l.w, ax, ay);
-  float b = lut2_slice(l, az.i1 * (l.w * l.h), l.w, ax, ay);
-  return a + (b - a) * az.w;
+  return lut_resolve(lut3_fetch(l, lut_axis(cx, l.w), lut_axis(cy, l.h), lut_axis(cz, l.depth)));
 }
 
 // defs.metal:283-299, bsdf.metal:12-43
@@ -212,38 +227,63 @@ struct BSDF {
   // again in every lobe of sample() and of the NEE eval() (bsdf.metal:291-326, defs.metal:349-361); a shaded hit uses ONE
   // wo for both calls, so they are looked up once here — same functions, same arguments, same bits.
   float cE_wo = 0.0f, cE_avg = 0.0f, cEms_wo = 0.0f, cEms_avg = 0.0f;
+  // Every E / EMs lookup of a hit has the material's roughness (and (ior-1)/ior) on its second (and third) axis: the axes
+  // are computed once here.  Only the first axis, the direction's cosine, differs between the lookups of a hit.
+  LutAxis axE_r, axEMs_r, axEMs_ior;
 
-  PT_HD BSDF(const ShadingContext& c, int rendererFlags, const LutSet& l, vec3 wo)
+  // The two direction-dependent energy terms E(w.z, roughness) and EMs(w.z, roughness, iorParam) of one direction, as raw
+  // taps (in flight) and resolved.  Neither address depends on another lookup's value, so a caller may fetch for several
+  // directions — wo, the light sample, the sample candidates — before it resolves the first (pt_shade.h).
+  struct DirTaps { LutTaps2 E; LutTaps3 EMs; };
+  struct DirTerms { float E, EMs; };
+  PT_HD LutTaps2 fetchE(float wz) const { return lut2_fetch(luts.E, lut_axis(wz, luts.E.w), axE_r); }
+  PT_HD LutTaps3 fetchEMs(float wz) const { return lut3_fetch(luts.EMs, lut_axis(wz, luts.EMs.w), axEMs_r, axEMs_ior); }
+  PT_HD DirTaps fetchDir(float wz) const { return {fetchE(wz), fetchEMs(wz)}; }
+  static PT_HD DirTerms resolveDir(const DirTaps& t) { return {lut_resolve(t.E), lut_resolve(t.EMs)}; }
+
+  // Set-up in two steps, so that a caller can put other fetches between them (pt_shade.h shade_issue):
+  //   BSDF b(ctx, flags, luts);  t = b.fetchDir(wo.z);  ...more fetches...;  b.setWo(BSDF::resolveDir(t));
+  // The four-argument constructor below is the two steps back to back.
+  PT_HD BSDF(const ShadingContext& c, int rendererFlags, const LutSet& l)
       : ctx(c), luts(l), ggx(make_ggx(c.roughness, c.anisotropy)), ggxCoat(make_ggx(c.clearcoatRoughness)),
         ms((rendererFlags & PT_FLAG_MULTISCATTER_GGX) != 0) {
-    const float m = c.metallic, t = c.transmission;
+    const float iorParam = (ctx.ior - 1.0f) / ctx.ior;
+    axE_r = lut_axis(ctx.roughness, luts.E.h);
+    axEMs_r = lut_axis(ctx.roughness, luts.EMs.h);
+    axEMs_ior = lut_axis(iorParam, luts.EMs.depth);
+  }
+  // wo_terms: both tap groups of wo, fetched together (a lane whose lobes need neither discards them)
+  PT_HD void setWo(const DirTerms& wo_terms) {
+    const float m = ctx.metallic, t = ctx.transmission;
     // the opaque lobe can be SAMPLED with probability (1-m)(1-t) and is EVALUATED with weight (1-m)(1-(1-m)t)
     const bool opaque_lobe = (1.0f - m) * (1.0f - t) > 0.0f || (1.0f - m) * (1.0f - (1.0f - m) * t) > 0.0f;
-    if (opaque_lobe || (ms && m > 0.0f)) cE_wo = lut2(luts.E, wo.z, ctx.roughness);
+    if (opaque_lobe || (ms && m > 0.0f)) cE_wo = wo_terms.E;
     if (ms && (opaque_lobe || m > 0.0f)) cE_avg = lut1(luts.Eavg, ctx.roughness);
     if (opaque_lobe) {
       const float iorParam = (ctx.ior - 1.0f) / ctx.ior;
-      cEms_wo = lut3(luts.EMs, wo.z, ctx.roughness, iorParam);
+      cEms_wo = wo_terms.EMs;
       cEms_avg = lut2(luts.EavgMs, iorParam, ctx.roughness);
     }
   }
+  PT_HD BSDF(const ShadingContext& c, int rendererFlags, const LutSet& l, vec3 wo) : BSDF(c, rendererFlags, l) {
+    setWo(resolveDir(fetchDir(wo.z)));
+  }
 
-  // defs.metal:349-361 — the E / Eavg part is shared by the float and float3 instantiations
-  PT_HD void multiscatter_terms(vec3 wo, vec3 wi, float* brdf_ms, float* E_avg) const {
+  // defs.metal:349-361 — the E / Eavg part is shared by the float and float3 instantiations; E_wi = E(wi.z, roughness)
+  PT_HD void multiscatter_terms(float E_wi, float* brdf_ms, float* E_avg) const {
     const float E_wo = cE_wo;
-    const float E_wi = lut2(luts.E, wi.z, ctx.roughness);
     *E_avg = cE_avg;
     *brdf_ms = (1.0f - E_wo) * (1.0f - E_wi) / (kPi * (1.0f - *E_avg));
   }
-  PT_HD float multiscatter(vec3 wo, vec3 wi, float F_avg) const {
+  PT_HD float multiscatter(float E_wi, float F_avg) const {
     float brdf_ms, E_avg;
-    multiscatter_terms(wo, wi, &brdf_ms, &E_avg);
+    multiscatter_terms(E_wi, &brdf_ms, &E_avg);
     const float fresnel_ms = F_avg * F_avg * E_avg / (1.0f - F_avg * (1.0f - E_avg));
     return fresnel_ms * brdf_ms;
   }
-  PT_HD vec3 multiscatter(vec3 wo, vec3 wi, vec3 F_avg) const {
+  PT_HD vec3 multiscatter(float E_wi, vec3 F_avg) const {
     float brdf_ms, E_avg;
-    multiscatter_terms(wo, wi, &brdf_ms, &E_avg);
+    multiscatter_terms(E_wi, &brdf_ms, &E_avg);
     const vec3 fresnel_ms = F_avg * F_avg * E_avg / (v3(1.0f) - F_avg * (1.0f - E_avg));
     return fresnel_ms * brdf_ms;
   }
@@ -255,10 +295,8 @@ struct BSDF {
     const float E_wo = lut3(luts.ETransIn, fabsf(wo.z), ctx.roughness, (ior - 1.0f) / ior);
     return 1.0f / E_wo;
   }
-  PT_HD float diffuseFactor(vec3 wo, vec3 wi) const {  // bsdf.metal:291-305
-    const float iorParam = (ctx.ior - 1.0f) / ctx.ior;
+  PT_HD float diffuseFactor(float E_ms_wi) const {  // bsdf.metal:291-305; E_ms_wi = EMs(wi.z, roughness, iorParam)
     const float E_ms_wo = cEms_wo;
-    const float E_ms_wi = lut3(luts.EMs, wi.z, ctx.roughness, iorParam);
     const float E_ms_avg = cEms_avg;
     return (1.0f - E_ms_wo) * (1.0f - E_ms_wi) / (kPi * (1.0f - E_ms_avg));
   }
@@ -270,21 +308,22 @@ struct BSDF {
   }
 
   // ---- evaluation ----------------------------------------------------------------------------------------------
-  PT_HD BsdfEval evalMetallicWm(vec3 wo, vec3 wi, vec3 wm) const {  // bsdf.metal:339-355
+  // (E_wi, wi_terms: the energy terms of wi, fetched by the caller — eval() / sample() below, or ahead of them by shade_issue)
+  PT_HD BsdfEval evalMetallicWm(vec3 wo, vec3 wi, vec3 wm, float E_wi) const {  // bsdf.metal:339-355
     const vec3 fresnel_ss = schlick(ctx.albedo, fabsf(dot(wo, wm)));
     vec3 brdf = fresnel_ss * ggx.singleScatterBRDF(wo, wi, wm);
     if (ms) {
       const vec3 F_avg = (20.0f * ctx.albedo + v3(1.0f)) / 21.0f;
-      brdf = brdf + multiscatter(wo, wi, F_avg);
+      brdf = brdf + multiscatter(E_wi, F_avg);
     }
     return {brdf, ggx.pdf(wo, wm)};
   }
-  PT_HD BsdfEval evalMetallic(vec3 wo, vec3 wi) const {  // bsdf.metal:360-370
+  PT_HD BsdfEval evalMetallic(vec3 wo, vec3 wi, float E_wi) const {  // bsdf.metal:360-370
     if (ggx.isSmooth()) return eval_default();
     vec3 wm = normalize(wo + wi);
     if (length_squared(wm) == 0.0f) return eval_default();
     wm = wm * sign(wm.z);
-    return evalMetallicWm(wo, wi, wm);
+    return evalMetallicWm(wo, wi, wm, E_wi);
   }
   PT_HD BsdfEval evalTransparentWm(vec3 wo, vec3 wi, vec3 wm, float fresnel_ss, float ior) const {  // :377-419
     const bool thin = (ctx.flags & PT_MATERIAL_THIN_DIELECTRIC) != 0;
@@ -327,10 +366,10 @@ struct BSDF {
     const float fresnel_ss = fresnel(dot(wo, wm), ior);
     return evalTransparentWm(wo, wi, wm, fresnel_ss, ior);
   }
-  PT_HD BsdfEval evalOpaque(vec3 wo, vec3 wi) const {  // bsdf.metal:451-486
+  PT_HD BsdfEval evalOpaque(vec3 wo, vec3 wi, const DirTerms& wi_terms) const {  // bsdf.metal:451-486
     const float F_avg = avgDielectricFresnelFit(ctx.ior);
     const float blendingFactor = opaqueDielectricFactor(wo, F_avg);
-    const float cDiffuse = diffuseFactor(wo, wi);
+    const float cDiffuse = diffuseFactor(wi_terms.EMs);
     const float diffusePdf = fabsf(wi.z) / kPi;
     if (ggx.isSmooth()) return {ctx.albedo * cDiffuse, diffusePdf * (1.0f - blendingFactor)};
     vec3 wm = normalize(wo + wi);
@@ -338,7 +377,7 @@ struct BSDF {
     wm = wm * sign(wm.z);
     const float fresnel_ss = fresnel(fabsf(dot(wo, wm)), ctx.ior);
     float dielectricBrdf = fresnel_ss * ggx.singleScatterBRDF(wo, wi, wm);
-    if (ms) dielectricBrdf += multiscatter(wo, wi, F_avg);
+    if (ms) dielectricBrdf += multiscatter(wi_terms.E, F_avg);
     return {v3(dielectricBrdf) + ctx.albedo * cDiffuse,
             ggx.pdf(wo, wm) * blendingFactor + diffusePdf * (1.0f - blendingFactor)};
   }
@@ -352,14 +391,15 @@ struct BSDF {
     *fresnel_ss = fresnel(dot(wo, wm), kClearcoatIor);
     return {v3(ggxCoat.singleScatterBRDF(wo, wi, wm)), ggxCoat.pdf(wo, wm)};
   }
-  PT_HD BsdfEval eval(vec3 wo, vec3 wi) const {  // bsdf.metal:199-223
+  PT_HD BsdfEval eval(vec3 wo, vec3 wi) const { return eval(wo, wi, resolveDir(fetchDir(wi.z))); }
+  PT_HD BsdfEval eval(vec3 wo, vec3 wi, const DirTerms& wi_terms) const {  // bsdf.metal:199-223
     if (wo.z < 1.5e-3f || wi.z < 1.5e-3f) return eval_default();
     const float metallic = ctx.metallic;
     const float transparent = (1.0f - metallic) * ctx.transmission;
     const float opaque = (1.0f - metallic) * (1.0f - transparent);
     BsdfEval result = {v3(0.0f), 0.0f};
     if (metallic > 0.0f) {
-      BsdfEval e = evalMetallic(wo, wi);
+      BsdfEval e = evalMetallic(wo, wi, wi_terms.E);
       result.f = result.f + e.f * metallic;
       result.pdf = result.pdf + e.pdf * metallic;
     }
@@ -369,7 +409,7 @@ struct BSDF {
       result.pdf = result.pdf + e.pdf * transparent;
     }
     if (opaque > 0.0f) {
-      BsdfEval e = evalOpaque(wo, wi);
+      BsdfEval e = evalOpaque(wo, wi, wi_terms);
       result.f = result.f + e.f * opaque;
       result.pdf = result.pdf + e.pdf * opaque;
     }
@@ -393,7 +433,7 @@ struct BSDF {
     const vec3 wm = ggx.sampleVmdf(wo, {r.x, r.y});
     const vec3 wi = reflect(-wo, wm);
     if (wo.z * wi.z < 0.0f) return sample_none();
-    const BsdfEval e = evalMetallicWm(wo, wi, wm);
+    const BsdfEval e = evalMetallicWm(wo, wi, wm, lut_resolve(fetchE(wi.z)));
     return {wi, e.f, v3(0.0f), e.pdf, Sample_Reflected | Sample_Glossy};
   }
   PT_HD BsdfSample sampleTransparent(vec3 wo, vec3 r) const {  // bsdf.metal:550-619
@@ -449,12 +489,12 @@ struct BSDF {
       const vec3 wi = reflect(-wo, wm);
       const float fresnel_ss = fresnel(fabsf(dot(wo, wm)), ctx.ior);
       float dielectricBrdf = fresnel_ss * ggx.singleScatterBRDF(wo, wi, wm);
-      if (ms) dielectricBrdf += multiscatter(wo, wi, F_avg);
+      if (ms) dielectricBrdf += multiscatter(lut_resolve(fetchE(wi.z)), F_avg);
       return {wi, v3(dielectricBrdf), v3(0.0f), ggx.pdf(wo, wm) * blendingFactor, Sample_Reflected | Sample_Glossy};
     }
     vec3 wi = sampleCosineHemisphere({r.x, r.y});
     if (wo.z < 0.0f) wi = wi * -1.0f;
-    const float cDiffuse = diffuseFactor(wo, wi);
+    const float cDiffuse = diffuseFactor(lut_resolve(fetchEMs(wi.z)));
     int flags = Sample_Reflected | Sample_Diffuse;
     if (ctx.flags & PT_MATERIAL_EMISSIVE) flags |= Sample_Emitted;
     return {wi, ctx.albedo * cDiffuse, ctx.emission / (1.0f - blendingFactor),

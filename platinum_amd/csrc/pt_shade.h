@@ -235,12 +235,31 @@ struct ShadeGeom {
   Frame frame;
   vec3 wo;
 };
-PT_HD void shade_geometry(const DeviceScene& S, const ShadeIn& in, ShadeGeom& g, ShadingContext& ctx) {
+// The gathers (ShadeRec -> instance, material, three vertices) are a step of their own, so that the caller can put work that
+// needs none of them — the Halton draws below — between issuing them and using them.
+struct ShadeGeomRaw { InstanceInfo inst; pt_material_gpu material; pt_vertex_data vd0, vd1, vd2; };
+PT_HD ShadeGeomRaw shade_geometry_fetch(const DeviceScene& S, const ShadeIn& in) {
   // (vertexResources / primitiveResources / instanceResources lookups, resolved per render into ShadeRec)
   const ShadeRec rec = ldg(&S.shade_recs[in.tri]);
-  const InstanceInfo inst = ldg(&S.instances[rec.inst]);
-  const pt_material_gpu material = ldg(&S.materials[rec.material]);
-  const pt_vertex_data vd0 = ldg(&S.vdata[rec.v[0]]), vd1 = ldg(&S.vdata[rec.v[1]]), vd2 = ldg(&S.vdata[rec.v[2]]);
+  return {ldg(&S.instances[rec.inst]), ldg(&S.materials[rec.material]), ldg(&S.vdata[rec.v[0]]), ldg(&S.vdata[rec.v[1]]), ldg(&S.vdata[rec.v[2]])};
+}
+// NEE's three draws (the light's surface point and the light choice, at in.dim + 6).  They need only (offset, dim) and the Halton
+// table — every random number is addressed by its dimension, so when it is computed does not change a bit.  They are computed
+// even for a hit that turns out to skip NEE (a perfectly specular material: its dimensions are not consumed then, the values are
+// dropped).  The BSDF sample's draws stay in shade_bounce: computed here as well they cost four registers across NEE and bought
+// nothing measurable (profiles/r15_shade_issue_early.md).
+struct NeeDraws { vec2 rl; float rz; };
+PT_HD NeeDraws shade_nee_draws(const ShadeTables& T, const ShadeIn& in) {
+  Halton halton{T.halton, in.offset, in.dim + 6};
+  NeeDraws d;
+  d.rl = halton.sample2d();
+  d.rz = halton.sample1d();
+  return d;
+}
+PT_HD void shade_geometry_finish(const DeviceScene& S, const ShadeIn& in, const ShadeGeomRaw& raw, ShadeGeom& g, ShadingContext& ctx) {
+  const InstanceInfo& inst = raw.inst;
+  const pt_material_gpu& material = raw.material;
+  const pt_vertex_data &vd0 = raw.vd0, &vd1 = raw.vd1, &vd2 = raw.vd2;
   const float tangentSign = vd0.tangent[3];
 
   const vec3 surfaceNormal = interpolate3(ld3(vd0.normal), ld3(vd1.normal), ld3(vd2.normal), in.u, in.v);
@@ -264,9 +283,12 @@ PT_HD void shade_geometry(const DeviceScene& S, const ShadeIn& in, ShadeGeom& g,
   g.wo = g.frame.worldToLocal(-in.d);
   ctx = make_shading_context(S, material, surfaceUV);
 }
+PT_HD void shade_geometry(const DeviceScene& S, const ShadeIn& in, ShadeGeom& g, ShadingContext& ctx) {
+  shade_geometry_finish(S, in, shade_geometry_fetch(S, in), g, ctx);
+}
 
-// Next-event estimation (kernel.metal:587-639).  `dim` = the first NEE dimension (the six BSDF-sample dimensions come
-// before it in the schedule); returns the cursor after NEE in `dim`.
+// Next-event estimation (kernel.metal:587-639).  Its first dimension is in.dim + 6 (the six BSDF-sample dimensions come
+// before it in the schedule); NeeOut::dim is the cursor after NEE.
 struct NeeOut {
   bool shadow;
   vec3 d;
@@ -275,16 +297,26 @@ struct NeeOut {
   float payload;
   uint32_t dim;
 };
-PT_HD NeeOut shade_nee(const DeviceScene& S, const ShadeTables& T, const ShadeIn& in, const ShadeGeom& g, const ShadingContext& ctx,
-                       const BSDF& bsdf, uint32_t dim) {
-  NeeOut out;
-  out.shadow = false;
-  out.dim = dim;
+// The light sample: everything of NEE that does not need the BSDF — the hit point, the frame and three Halton draws decide it.
+// `lit` = a light was sampled and the BSDF is to be evaluated towards it; otherwise lwi = 0 (a direction whose table taps
+// are in range and are never used) and only `dim` means anything.
+struct NeeLight {
+  bool lit;
+  vec3 Li, lwi;
+  float lpdf, pLight, dist;  // dist = |lpos - hitPos|
+  uint32_t dim;              // the cursor after the light sample's three dimensions (or the unchanged one: NEE not run)
+};
+PT_HD NeeLight shade_nee_light(const DeviceScene& S, const ShadeTables& T, const ShadeIn& in, const ShadeGeom& g, const ShadingContext& ctx,
+                               const NeeDraws& draws) {
+  NeeLight out;
+  out.lit = false;
+  out.Li = v3(0.0f); out.lwi = v3(0.0f);
+  out.lpdf = 0.0f; out.pLight = 0.0f; out.dist = 0.0f;
+  out.dim = in.dim + 6;
   if (!(S.integrator == PT_INTEGRATOR_MIS && (ctx.roughness > 0.0f || ctx.metallic + ctx.transmission < 1.0f))) return out;
-  Halton halton{T.halton, in.offset, dim};
-  const vec2 rl = halton.sample2d();
-  float rz = halton.sample1d();
-  out.dim = halton.dim;
+  const vec2 rl = draws.rl;
+  float rz = draws.rz;
+  out.dim = in.dim + 9;
   // kernel.metal:590-616. Without any light the reference indexes envLights[0] out of bounds (UB): NEE is skipped then,
   // the three dimensions are still consumed.
   const uint32_t envCount = S.envLightCount;
@@ -313,18 +345,32 @@ PT_HD NeeOut shade_nee(const DeviceScene& S, const ShadeTables& T, const ShadeIn
     lpdf = length_squared(lpos - g.hitPos) / (fabsf(dot(lnormal, lwi)) * light.area);
     Li = v3(light.e0, light.e1, light.e2);
   }
-
-  const vec3 wi = g.frame.worldToLocal(lwi);
-  const BsdfEval ev = bsdf.eval(g.wo, wi);
+  out.lit = true;
+  out.Li = Li; out.lwi = lwi;
+  out.lpdf = lpdf; out.pLight = pLight;
+  out.dist = length(lpos - g.hitPos);
+  return out;
+}
+// The BSDF towards the light sample and the shadow ray (kernel.metal:618-639).  wi_terms = the energy terms of the light
+// direction, BSDF::resolveDir(bsdf.fetchDir(wi.z)) with wi = g.frame.worldToLocal(light.lwi).
+PT_HD NeeOut shade_nee_eval(const DeviceScene& S, const ShadeTables& T, const ShadeIn& in, const ShadeGeom& g, const BSDF& bsdf,
+                            const NeeLight& light, const BSDF::DirTerms& wi_terms) {
+  NeeOut out;
+  out.shadow = false;
+  out.dim = light.dim;
+  if (!light.lit) return out;
+  const vec3 wi = g.frame.worldToLocal(light.lwi);
+  const BsdfEval ev = bsdf.eval(g.wo, wi, wi_terms);
   if (length_squared(ev.f) > 0.0f) {
+    Halton halton{T.halton, in.offset, light.dim};
     // `ir` payload of the shadow ray (kernel.metal:625): only evaluated when an alpha test can consume it
     out.payload = S.has_alpha ? halton.sample1d() : (halton.dim++, 0.0f);
     out.dim = halton.dim;
-    const float pdfLight = pLight * lpdf;
-    const vec3 Ld = Li * ev.f * fabsf(wi.z) / (pdfLight + ev.pdf);
+    const float pdfLight = light.pLight * light.lpdf;
+    const vec3 Ld = light.Li * ev.f * fabsf(wi.z) / (pdfLight + ev.pdf);
     out.shadow = true;
-    out.d = lwi;
-    out.tmax = length(lpos - g.hitPos) - 1e-3f;
+    out.d = light.lwi;
+    out.tmax = light.dist - 1e-3f;
     out.contrib = in.att * Ld;
   }
   return out;
@@ -343,6 +389,24 @@ struct BounceOut {
 };
 // a NaN or an infinity among the three (conservative: also the last finite binade): a throughput in k_shade's scan of the misses, a sample in the accumulate kernels
 PT_HD bool not_finite(vec3 a) { return !(fabsf(a.x) <= 3.0e38f && fabsf(a.y) <= 3.0e38f && fabsf(a.z) <= 3.0e38f); }
+
+// ---- issue early, wait once.  None of a hit's energy-table addresses depends on another lookup's value: wo is known after the
+//      geometry, the light direction after shade_nee_light().  shade_issue() fetches the taps of both — E and EMs of wo,
+//      EMs and E of the light direction: four tap groups, one round trip; shade_land() resolves them — the first use of a
+//      tap, so the one place the hit waits for the tables.  What follows (NEE eval, sample, emission, throughput, roulette)
+//      runs on resolved values in the order it always had.  A lane that would not have run a lookup (smooth GGX, a light
+//      below the 1.5e-3 cut, no NEE for a specular material, a scene without lights, a lobe the material does not have)
+//      fetches an in-range texel (lut_axis is total) and never uses it.
+struct ShadeFlight { BSDF::DirTaps wo_taps, light_taps; };
+PT_HD ShadeFlight shade_issue(const ShadeGeom& g, const BSDF& bsdf, const NeeLight& light) {
+  return {bsdf.fetchDir(g.wo.z), bsdf.fetchDir(dot(light.lwi, g.frame.z))};  // (the dot = worldToLocal(lwi).z)
+}
+// returns the light direction's terms (for shade_nee_eval); the BSDF's own wo terms are set
+PT_HD BSDF::DirTerms shade_land(BSDF& bsdf, const ShadeFlight& f) {
+  bsdf.setWo(BSDF::resolveDir(f.wo_taps));
+  return BSDF::resolveDir(f.light_taps);
+}
+
 PT_HD BounceOut shade_bounce(const DeviceScene& S, const ShadeTables& T, const ShadeIn& in, const ShadeGeom& g, const ShadingContext& ctx,
                              const BSDF& bsdf, uint32_t dim_rr) {
   BounceOut out;
@@ -417,9 +481,14 @@ PT_HD ShadeOut stage_shade(const DeviceScene& S, const ShadeIn& in) {
   const ShadeTables T = shade_tables(S);
   ShadeGeom g;
   ShadingContext ctx;
-  shade_geometry(S, in, g, ctx);
-  const BSDF bsdf(ctx, S.flags, T.luts, g.wo);
-  const NeeOut nee = shade_nee(S, T, in, g, ctx, bsdf, in.dim + 6);
+  const ShadeGeomRaw raw = shade_geometry_fetch(S, in);
+  const NeeDraws draws = shade_nee_draws(T, in);
+  shade_geometry_finish(S, in, raw, g, ctx);
+  const NeeLight light = shade_nee_light(S, T, in, g, ctx, draws);
+  BSDF bsdf(ctx, S.flags, T.luts);
+  const ShadeFlight flight = shade_issue(g, bsdf, light);
+  const BSDF::DirTerms light_terms = shade_land(bsdf, flight);
+  const NeeOut nee = shade_nee_eval(S, T, in, g, bsdf, light, light_terms);
   const BounceOut bo = shade_bounce(S, T, in, g, ctx, bsdf, nee.dim);
   ShadeOut out;
   out.emitted = bo.emitted;
