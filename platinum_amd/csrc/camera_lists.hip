@@ -1,5 +1,5 @@
 // camera_lists.hip — once per pt_start_render, after the BVH build: for every pixel of a pinhole camera the 6-wide nodes whose leaf children
-// the pixel's cone can touch (pt_camlist.h), sorted by the distance at which a ray can first enter them.  k_trace_camera (kernels.hip) traces
+// the pixel's cone can touch (pt_camlist.h), sorted by the distance at which a ray can first enter them.  k_camera_primary (kernels.hip) traces
 // bounce 0 of every batch of the render from these lists instead of walking the tree from the root once per sample.
 //
 // One wave per 8x8 tile.  The wave walks the tree with the TILE's cone, all lanes in step (lanes 0..5 test one child each, a ballot makes the

@@ -314,7 +314,7 @@ static int enqueue_selection(pt_renderer* r) {
   PT_HIP(r->sel_cov.alloc((size_t)r->S.width * r->S.height));
   launch_matte_resolve(r->stream, r->matte_slots.p, r->selection.layer, r->sel_ids.p, (uint32_t)r->sel_set.size(), r->vtiles ? r->ad_tile_n.p : nullptr,
                        (uint32_t)r->launched, r->rect, r->S.width, r->S.height, r->sel_cov.p);
-  launch_selection_overlay(r->stream, r->render_target.p, r->sel_cov.p, r->S.width, r->S.height, r->selection, !r->sel_no_early_out);
+  launch_selection_overlay(r->stream, r->render_target.p, r->sel_cov.p, r->S.width, r->S.height, r->selection);
   PT_HIP(hipGetLastError());
   return PT_OK;
 }
@@ -334,7 +334,7 @@ int dev_debug_selection_overlay(pt_renderer* r, const uint8_t* rgba8_in, const f
   PT_HIP(target.alloc(npix)); PT_HIP(cov.alloc(npix));
   PT_HIP(hipMemcpyAsync(target.p, rgba8_in, 4 * npix, hipMemcpyHostToDevice, r->stream));
   PT_HIP(hipMemcpyAsync(cov.p, coverage, sizeof(float) * npix, hipMemcpyHostToDevice, r->stream));
-  launch_selection_overlay(r->stream, target.p, cov.p, width, height, *options, !r->sel_no_early_out);
+  launch_selection_overlay(r->stream, target.p, cov.p, width, height, *options);
   PT_HIP(hipGetLastError());
   PT_HIP(hipStreamSynchronize(r->stream));
   PT_HIP(hipMemcpy(rgba8_out, target.p, 4 * npix, hipMemcpyDeviceToHost));

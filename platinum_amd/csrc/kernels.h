@@ -55,16 +55,11 @@ uint32_t trace_block_threads(bool two_level);
 uint32_t trace_blocks_per_cu_two_level();  // 256 (7 blocks per CU) for one BVH, 1024 (one block per CU) for the two-level structure
 void launch_trace_closest(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState st, vec4* hit, Segments seg, uint32_t cur,
                           BatchCounters* ctr, uint32_t bounce, uint32_t* spill, int32_t* hitlog, uint32_t log_stride, bool count);
-// Bounce 0 of a render batch from the per-pixel leaf lists `cl` (camera_lists.hip) instead of launch_trace_closest: k_trace_camera (`grid` blocks,
-// camera_blocks_per_cu() per CU) and, when the build flagged pixels (any_unlisted), the ordinary traversal for their rays (`grid_unlisted` blocks
-// as launch_trace_closest takes them).  One-BVH 6-wide structure only.
-void launch_trace_camera(hipStream_t s, uint32_t grid, uint32_t grid_unlisted, const DeviceScene& S, PathState st, vec4* hit, Segments seg,
-                         BatchCounters* ctr, uint32_t* spill, const CameraLists& cl, bool any_unlisted);
-uint32_t camera_blocks_per_cu();
-// launch_raygen + launch_chunk_tables(bounce 0) + launch_trace_camera of a full-frame render batch with lists, with the first and the last as ONE
-// kernel (k_camera_primary, `grid` blocks, primary_blocks_per_cu() per CU): the camera rays are generated and traced in registers, and every word
-// the two kernels leave in memory is written as they write it.  The caller runs the table pass behind it — unless the build flagged pixels
-// (any_unlisted): then the table pass and k_trace_closest_unlisted, which claims from that table, follow here.
+// Bounce 0 of a full-frame render batch from the per-pixel leaf lists `cl` (camera_lists.hip) instead of launch_raygen + launch_trace_closest, as
+// ONE kernel (k_camera_primary, `grid` blocks, primary_blocks_per_cu() per CU): the camera rays are generated and traced in registers, and every
+// word launch_raygen leaves in memory is written as it writes it, with hit[] beside it.  One-BVH 6-wide structure only.  The caller runs the table
+// pass behind it — unless the build flagged pixels (any_unlisted): then the table pass and the ordinary traversal for those pixels' rays
+// (k_trace_closest_unlisted, `grid_unlisted` blocks as launch_trace_closest takes them), which claims from that table, follow here.
 void launch_camera_primary(hipStream_t s, uint32_t grid, uint32_t grid_unlisted, const DeviceScene& S, PathState st, vec4* Lbuf, vec4* hit, Segments seg,
                            BatchCounters* ctr, uint32_t first_sample, uint32_t nsamples, uint32_t* spill, const CameraLists& cl, bool any_unlisted);
 uint32_t primary_blocks_per_cu();

@@ -397,7 +397,7 @@ __device__ __forceinline__ const BvhNode* stage_nodes(const DeviceScene& S, BvhN
 
 // ---- closest hit ---------------------------------------------------------------------------------------------------
 // (the body of k_trace_closest.  UNLISTED: the instantiation behind k_trace_closest_unlisted, which walks the tree for the camera rays of the
-//  pixels whose list did not fit and drops every other ray of the queue: k_trace_camera has traced those.  `cursor`: the launch's claim cursor.)
+//  pixels whose list did not fit and drops every other ray of the queue: k_camera_primary has traced those.  `cursor`: the launch's claim cursor.)
 template <bool COUNT, bool TWO, bool W6, bool UNLISTED>
 __device__ __forceinline__ void trace_closest_body(const DeviceScene& S, PathState st, vec4* __restrict__ hit, const Segments& seg, uint32_t cur,
                                                    BatchCounters* __restrict__ ctr, uint32_t bounce, uint32_t* __restrict__ cursor,
@@ -455,7 +455,7 @@ __device__ __forceinline__ void trace_closest_body(const DeviceScene& S, PathSta
       if (ts.dbg) printf("dbg ray slot %u lane %u wave %u o %.9g %.9g %.9g d %.9g %.9g %.9g\n", ray, lane, wave_index(), o4.x, o4.y, o4.z, d4.x, d4.y, d4.z);
 #endif
       if (UNLISTED && cl.count[pixel_slot_of_pid(segment_lbuf_base(seg, slot_segment(seg.nseg, ray)) + (f2u(d4.w) >> kMetaPidShift), seg.nsamples)] != kCamWalk)
-        ray = kInvalidRef;   // a listed pixel's ray: hit[ray] holds k_trace_camera's answer
+        ray = kInvalidRef;   // a listed pixel's ray: hit[ray] holds k_camera_primary's answer
       else if (trav_init(S, ts, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), 1e-3f, kInf, ir, stack, false, COUNT ? &tc : nullptr)) finish();
     }
     PT_TAIL_T(tail_setup)
@@ -488,47 +488,17 @@ k_trace_closest(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments se
 }
 
 // ---- camera rays from per-pixel leaf lists (pt_camlist.h; built once per render by camera_lists.hip) --------------------------------------
-// Bounce 0 of a render batch of a pinhole camera over the 6-wide one-BVH structure.  Same chunk table, same claims, same hit[] record as
-// k_trace_closest; but a camera ray's candidates are known before it exists: its pixel's list names every node with a leaf child the pixel's cone
-// can touch, nearest first.  A lane takes a ray, finds its pixel (slot -> pid -> pixel slot: a chunk straddles pixels whenever the batch is not
-// a multiple of 64 samples) and runs ITS OWN slab test (node6_slabs: the walk's arithmetic) against the leaf children each entry names and
-// trav_leaf on those that pass, until an entry lies beyond best.t * kCamCullSlack.  So a triangle is tested iff its leaf child passes this
-// ray's slab test, as in the walk; what differs is the order in which candidates lower best.t, against which the list trace culls with a
-// wider margin than the walk (kCamCullSlack, pt_camlist.h).  No node stack, no leaf queue, no LDS; the next entry's node is fetched while the current one's triangles are tested.  The 64
-// lanes of a chunk are samples of one pixel (k_raygen): they read the same list and the same nodes.  Pixels flagged kCamWalk are left to
-// k_trace_closest_unlisted.
-#ifndef PT_CAMERA_WAVES
-#define PT_CAMERA_WAVES 6
-#endif
-__global__ void __launch_bounds__(kBlock, PT_CAMERA_WAVES)
-k_trace_camera(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments seg, BatchCounters* __restrict__ ctr, CameraLists cl) {
-  const uint32_t lane = wave_lane();
-  ChunkClaims src;
-  src.init(seg.table_closest, ctr->chunks_closest[0], &ctr->work_closest[0], seg, lane);
-  const BvhNode6* __restrict__ nodes = reinterpret_cast<const BvhNode6*>(S.nodes);
-  for (;;) {
-    const uint32_t ray = src.take(true);   // every lane wants a ray: the lanes of a wave all start and end a chunk together
-    if (__ballot(ray != kInvalidRef) == 0) break;   // (take() returns nothing for every lane only when no chunk is left)
-    if (ray != kInvalidRef) {
-      const vec4 o4 = st.rayO[ray];
-      const vec4 d4 = st.rayD[ray];
-      const uint32_t q = pixel_slot_of_pid(segment_lbuf_base(seg, slot_segment(seg.nseg, ray)) + (f2u(d4.w) >> kMetaPidShift), seg.nsamples);
-      const uint32_t len = cl.count[q];
-      if (len != kCamWalk) {
-        float ir = 0.0f;  // alpha-test payload, as in k_trace_closest
-        if (S.has_alpha) ir = Halton{halton_table(S.halton), f2u(st.att[ray].w), f2u(d4.w) & kMetaDimMask}.sample1d();
-        TravState ts;
-        (void)trav_init(S, ts, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), 1e-3f, kInf, ir, TraversalStack{}, false, nullptr);   // (lists exist only over a tree whose root is a node)
-        cam_trace_ray(S, ts, nodes, cl.entries + (size_t)q * cl.cap, len);   // (pt_camlist.h: shared with k_camera_primary and tests/emu)
-        const RayHit& h = ts.best;
-        hit[ray] = vec4{h.t, h.u, h.v, u2f(hit_word(h))};
-      }
-    }
-  }
-}
+// Bounce 0 of a full-frame render batch of a pinhole camera over the 6-wide one-BVH structure.  A camera ray's candidates are known before it
+// exists: its pixel's list names every node with a leaf child the pixel's cone can touch, nearest first.  A ray runs ITS OWN slab test
+// (node6_slabs: the walk's arithmetic) against the leaf children each entry names and trav_leaf on those that pass, until an entry lies beyond
+// best.t * kCamCullSlack.  So a triangle is tested iff its leaf child passes this ray's slab test, as in the walk; what differs is the order
+// in which candidates lower best.t, against which the list trace culls with a wider margin than the walk (kCamCullSlack, pt_camlist.h).  No
+// node stack, no leaf queue, no LDS; the next entry's node is fetched while the current one's triangles are tested.  The hit[] record is
+// k_trace_closest's.  Pixels flagged kCamWalk are left to k_trace_closest_unlisted.
 
-// the ordinary traversal for the camera rays of the pixels flagged kCamWalk (launched only when the build flagged any); its claims run on a
-// cursor of its own (work_closest[63]: bounces stop at 50), k_trace_camera has used up bounce 0's
+// the ordinary traversal for the camera rays of the pixels flagged kCamWalk (launched only when the build flagged any), from the chunk table
+// k_chunk_tables makes of the queue k_camera_primary filled.  Its claims run on a cursor of its own (work_closest[63]: bounces stop at 50):
+// k_camera_primary has used up bounce 0's for its work units
 constexpr uint32_t kUnlistedCursor = 63;
 __global__ void __launch_bounds__(kBlock, PT_CLOSEST_WAVES)
 k_trace_closest_unlisted(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments seg, BatchCounters* __restrict__ ctr, uint32_t* __restrict__ spill,
@@ -536,12 +506,12 @@ k_trace_closest_unlisted(DeviceScene S, PathState st, vec4* __restrict__ hit, Se
   trace_closest_body<false, false, true, true>(S, st, hit, seg, 0u, ctr, 0u, &ctr->work_closest[kUnlistedCursor], spill, nullptr, 0u, cl);
 }
 
-// ---- bounce 0 in one kernel: k_raygen + k_trace_camera for a full-frame render batch with lists --------------------------------------------
-// k_trace_camera needs no stack, no leaf queue and no LDS, and the wave that generates 64 samples of a pixel knows the pixel: it goes
-// straight to that pixel's list with the ray in registers.  What k_raygen leaves in memory (rayO, rayD, att, Lbuf, the segment's count and
-// poison flag, paths / closest of WaveStats) and what k_trace_camera leaves (hit[]) is written word for word, to the same slots: the ray is
-// never read back, and the state stores drain while the trace waits for its nodes.  k_chunk_tables still runs behind it (shade_order, and
-// the table k_trace_closest_unlisted claims from).
+// ---- bounce 0 in one kernel: camera rays generated and traced from their pixels' lists -----------------------------------------------------
+// The list trace needs no stack, no leaf queue and no LDS, and the wave that generates 64 samples of a pixel knows the pixel: it goes
+// straight to that pixel's list with the ray in registers.  What k_raygen would leave in memory (rayO, rayD, att, Lbuf, the segment's count
+// and poison flag, paths / closest of WaveStats) is written word for word, to the same slots, and hit[] beside it: the ray is never read
+// back, and the state stores drain while the trace waits for its nodes.  k_chunk_tables still runs behind it (shade_order, and the table
+// k_trace_closest_unlisted claims from).
 //
 // Work units: a segment costs k_raygen the same everywhere, here its cost follows the list lengths.  A unit is PT_PRIMARY_UNIT consecutive wave
 // iterations of a segment, claimed from bounce 0's cursor (work_closest[0]: nothing else uses it in this path); where a unit's first ray lands
@@ -558,9 +528,6 @@ k_trace_closest_unlisted(DeviceScene S, PathState st, vec4* __restrict__ hit, Se
 #endif
 #ifndef PT_PRIMARY_UNIT
 #define PT_PRIMARY_UNIT 16
-#endif
-#ifndef PT_PRIMARY_UNIFORM
-#define PT_PRIMARY_UNIFORM 1   // 0: every batch takes the per-lane instantiation (the A/B build of profiles/r08_fused_camera.md)
 #endif
 constexpr uint32_t kPrimaryUnit = PT_PRIMARY_UNIT;
 
@@ -594,7 +561,7 @@ __device__ __forceinline__ void cam_trace_wave(const DeviceScene& S, TravState& 
 }
 
 // ONE_PIXEL: the batch's sample count is a multiple of 64, every iteration is one pixel and the wave walks its list together; otherwise every
-// ray walks its own pixel's list (cam_trace_ray, as in k_trace_camera).  Two instantiations, chosen per batch by launch_camera_primary: with both
+// ray walks its own pixel's list (cam_trace_ray, pt_camlist.h).  Two instantiations, chosen per batch by launch_camera_primary: with both
 // walks in one kernel the allocator spilled 46 registers into the entry and triangle loops, apart the wave walk needs no scratch at all.
 template <bool ONE_PIXEL>
 __global__ void __launch_bounds__(kBlock, PT_PRIMARY_WAVES)
@@ -648,7 +615,7 @@ k_camera_primary(DeviceScene S, PathState st, vec4* __restrict__ Lbuf, vec4* __r
       }
       n_out += (uint32_t)__popcll(m);
       if (m == 0) continue;
-      // ---- k_trace_camera for these rays ----
+      // ---- the list trace of these rays ----
       // a ray's list: that of its pixel's slot (pixel_slot_of_pid of its pid); a count of kCamWalk leaves the pixel to k_trace_closest_unlisted
       if constexpr (ONE_PIXEL) {
         const uint32_t qs = tile * 64u + r0 / nsamples;
@@ -1283,16 +1250,10 @@ void launch_trace_closest(hipStream_t s, uint32_t grid, const DeviceScene& S, Pa
   else
     hipLaunchKernelGGL((k_trace_closest<false, false>), dim3(grid), dim3(kBlock), 0, s, S, st, hit, seg, cur, ctr, bounce, spill, hitlog, log_stride);
 }
-void launch_trace_camera(hipStream_t s, uint32_t grid, uint32_t grid_unlisted, const DeviceScene& S, PathState st, vec4* hit, Segments seg,
-                         BatchCounters* ctr, uint32_t* spill, const CameraLists& cl, bool any_unlisted) {
-  hipLaunchKernelGGL(k_trace_camera, dim3(grid), dim3(kBlock), 0, s, S, st, hit, seg, ctr, cl);
-  if (any_unlisted) hipLaunchKernelGGL(k_trace_closest_unlisted, dim3(grid_unlisted), dim3(kBlock), 0, s, S, st, hit, seg, ctr, spill, cl);
-}
-uint32_t camera_blocks_per_cu() { return PT_CAMERA_WAVES; }
 void launch_camera_primary(hipStream_t s, uint32_t grid, uint32_t grid_unlisted, const DeviceScene& S, PathState st, vec4* Lbuf, vec4* hit, Segments seg,
                            BatchCounters* ctr, uint32_t first_sample, uint32_t nsamples, uint32_t* spill, const CameraLists& cl, bool any_unlisted) {
   const BvhNode6* nodes = reinterpret_cast<const BvhNode6*>(S.nodes);
-  if (PT_PRIMARY_UNIFORM && nsamples % 64u == 0u)
+  if (nsamples % 64u == 0u)
     hipLaunchKernelGGL(k_camera_primary<true>, dim3(grid), dim3(kBlock), 0, s, S, st, Lbuf, hit, seg, ctr, first_sample, nsamples, tiles_x(S.width),
                        tiles_y(S.height), cl.entries, cl.count, cl.cap, nodes);
   else

@@ -1,4 +1,4 @@
-// pt_camlist.h — the geometry behind the per-pixel leaf lists of a pinhole camera (camera_lists.hip builds them once per render, k_trace_camera
+// pt_camlist.h — the geometry behind the per-pixel leaf lists of a pinhole camera (camera_lists.hip builds them once per render, k_camera_primary
 // in kernels.hip traces bounce 0 from them).  Plain functions (PT_HD, no HIP types): the same code for hipcc and for the g++ build
 // under tests/emu, which proves the conservative part by test (tests/test_camera_lists_host.py).
 //
@@ -129,7 +129,7 @@ PT_HD void cam_list_insert(CamListEntry* list, uint32_t len, uint32_t ref, float
   list[j] = CamListEntry{ref, dist};
 }
 
-// Bounce 0 of one ray from its pixel's list: what k_trace_camera runs per lane, and what tests/emu compares with the walk.  ts comes from
+// Bounce 0 of one ray from its pixel's list: what k_camera_primary runs per lane, and what tests/emu compares with the walk.  ts comes from
 // trav_init.  For each entry in order: stop when its dist lies beyond best.t * kCamCullSlack (its slab test and every later one's would fail); else
 // slab-test the node's leaf children with the walk's own arithmetic and run trav_leaf on those that pass and that the list names.
 PT_HD void cam_trace_list(const DeviceScene& S, TravState& ts, const CamListEntry* list, uint32_t len) {
@@ -149,7 +149,7 @@ PT_HD void cam_trace_list(const DeviceScene& S, TravState& ts, const CamListEntr
 }
 
 
-// cam_trace_list as the kernels run it per lane (k_trace_camera, and k_camera_primary where the lanes of a wave iteration belong to more than
+// cam_trace_list as the kernel runs it per lane (k_camera_primary where the lanes of a wave iteration belong to more than
 // one pixel): the same entries, children and triangles in the same order, as ONE loop whose step is either "next entry" or "next triangle".
 // The addresses do not depend on the traversal: entry i + 1 is loaded one step ahead, and its node is fetched as soon as entry i's slab
 // tests are done with the node registers — it arrives while entry i's triangles are tested.  (Holding two whole nodes cost 62 spilled

@@ -82,9 +82,7 @@ PT_HD void halton_digits(const HaltonEntry& e, float rem, float& f, float& r) {
     f = f * e.inv;
     r = r + f * digit;
     rem = qf;
-#ifndef PT_HALTON_FULL_TOP   // (A/B switch: the r1-r5 form)
     if (TOP && !(rem > 0.0f)) break;
-#endif
   }
 }
 

@@ -110,10 +110,11 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
   const bool ad = mode == BATCH_RENDER && r->vtiles;
   const TileSet tile_set = r->tile_set();
   const TileSet* tiles = ad ? &tile_set : nullptr;
-  // A full-frame render batch with lists generates and traces its camera rays in one kernel (k_camera_primary), timed as bounce 0's closest-hit
-  // launch together with the walk for flagged pixels; the table pass alone is left in the raygen class.
-  const bool fused = mode == BATCH_RENDER && r->cam_lists && !ad && !r->no_fused_camera;
-  if (fused) {
+  // Bounce 0, the camera rays.  A render batch with lists generates and traces them in one kernel (k_camera_primary), timed as bounce 0's
+  // closest-hit launch together with the walk for flagged pixels; the table pass alone is left in the raygen class.  Lists imply a full-frame
+  // render (camera_lists_wanted, host_scene.h: no adaptive sampling, no region), so `tiles` is null here.  Every other batch generates them,
+  // lists the queue's chunks and walks the tree; the debug and measuring batches always do (the hit log and nodes_per_ray stay what they are).
+  if (mode == BATCH_RENDER && r->cam_lists) {
     const bool any_unlisted = r->cam_stats.pixels_walk != 0;
     {
       ScopedTimer t(r, K_CLOSEST);
@@ -125,35 +126,37 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
       launch_chunk_tables(s, seg, 0, ctr, 0, 0, false);
     }
   } else {
-    ScopedTimer t(r, K_RAYGEN);
-    launch_raygen(s, r->grid, S, r->path_state(0), r->Lbuf.p, seg, ctr, first, ns, tiles);
-    launch_chunk_tables(s, seg, 0, ctr, 0, 0, false);
+    {
+      ScopedTimer t(r, K_RAYGEN);
+      launch_raygen(s, r->grid, S, r->path_state(0), r->Lbuf.p, seg, ctr, first, ns, tiles);
+      launch_chunk_tables(s, seg, 0, ctr, 0, 0, false);
+    }
+    ScopedTimer t(r, K_CLOSEST);
+    launch_trace_closest(s, r->closest_grid, S, r->path_state(0), r->hit.p, seg, 0u, ctr, 0u, r->spill.p, hitlog, S.width * S.height, count);
   }
+  // The first-hit passes of a render batch: the camera rays' hits, read from the queue before k_shade consumes it.
+  if (mode == BATCH_RENDER) {
+    // first-hit AOVs of a render that keeps them (denoise.hip)
+    if (r->aov) launch_aov(s, r->grid, r->scene_d.p, r->path_state(0), r->hit.p, seg, r->Abuf.p);
+    // ID mattes of a render that keeps them (matte.hip): the same hits' instance and material, independent of the AOVs (timed with the
+    // accumulate class, where its other kernel is: pt_stats.ms_accumulate with mattes on minus off is what mattes cost)
+    if (r->matte) {
+      ScopedTimer t(r, K_ACCUM);
+      launch_matte_ids(s, r->grid, r->scene_d.p, r->path_state(0), r->hit.p, seg, r->Mbuf.p);
+    }
+    // the film of a render that keeps one (film.hip): which of the same camera rays hit anything (timed with the accumulate class, as the mattes)
+    if (r->film) {
+      ScopedTimer t(r, K_ACCUM);
+      launch_film_flags(s, r->grid, r->path_state(0), r->hit.p, seg, r->Fbuf.p);
+    }
+  }
+  // The bounces: bounce b's closest hits (bounce 0's are in hit[] already), k_shade, and the shadow rays it queued.
   int cur = 0;
   const bool mis = S.integrator == PT_INTEGRATOR_MIS;
   for (uint32_t b = 0; b < S.max_bounces; b++) {
-    if (b != 0 || !fused) {
+    if (b != 0) {
       ScopedTimer t(r, K_CLOSEST);
-      // the camera rays of a render batch come from the per-pixel leaf lists when the render has them; the debug and measuring batches keep the walk
-      // (the hit log and nodes_per_ray stay what they are)
-      if (b == 0 && mode == BATCH_RENDER && r->cam_lists)
-        launch_trace_camera(s, r->camera_grid, r->closest_grid, S, r->path_state(cur), r->hit.p, seg, ctr, r->spill.p,
-                            CameraLists{r->cam_entries.p, r->cam_count.p, r->cam_cap}, r->cam_stats.pixels_walk != 0);
-      else
-        launch_trace_closest(s, r->closest_grid, S, r->path_state(cur), r->hit.p, seg, (uint32_t)cur, ctr, b, r->spill.p, hitlog, S.width * S.height, count);
-    }
-    // first-hit AOVs of a render that keeps them (denoise.hip): the camera rays' hits, read from the queue before k_shade consumes it
-    if (b == 0 && mode == BATCH_RENDER && r->aov) launch_aov(s, r->grid, r->scene_d.p, r->path_state(cur), r->hit.p, seg, r->Abuf.p);
-    // ID mattes of a render that keeps them (matte.hip): the same hits' instance and material, independent of the AOVs (timed with the
-    // accumulate class, where its other kernel is: pt_stats.ms_accumulate with mattes on minus off is what mattes cost)
-    if (b == 0 && mode == BATCH_RENDER && r->matte) {
-      ScopedTimer t(r, K_ACCUM);
-      launch_matte_ids(s, r->grid, r->scene_d.p, r->path_state(cur), r->hit.p, seg, r->Mbuf.p);
-    }
-    // the film of a render that keeps one (film.hip): which of the same camera rays hit anything (timed with the accumulate class, as the mattes)
-    if (b == 0 && mode == BATCH_RENDER && r->film) {
-      ScopedTimer t(r, K_ACCUM);
-      launch_film_flags(s, r->grid, r->path_state(cur), r->hit.p, seg, r->Fbuf.p);
+      launch_trace_closest(s, r->closest_grid, S, r->path_state(cur), r->hit.p, seg, (uint32_t)cur, ctr, b, r->spill.p, hitlog, S.width * S.height, count);
     }
     {
       ScopedTimer t(r, K_SHADE);
@@ -329,8 +332,6 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   if (const char* e = getenv("PTAMD_BLOCKS_PER_CU")) r->blocks_per_cu = (uint32_t)std::max(1, std::min(8, atoi(e)));
   if (const char* e = getenv("PTAMD_CLOSEST_BLOCKS_PER_CU")) r->closest_blocks_per_cu = (uint32_t)std::max(1, std::min(8, atoi(e)));
   if (const char* e = getenv("PTAMD_NO_CAMERA_LISTS")) r->no_camera_lists = atoi(e) != 0;
-  if (const char* e = getenv("PTAMD_NO_FUSED_CAMERA")) r->no_fused_camera = atoi(e) != 0;
-  if (const char* e = getenv("PTAMD_NO_SELECTION_EARLY_OUT")) r->sel_no_early_out = atoi(e) != 0;
   if (const char* e = getenv("PTAMD_TEST_CAMLIST_CAP")) r->cam_cap_override = (uint32_t)std::max(1, std::min((int)kCamListMaxCapacity, atoi(e)));
   if (const char* e = getenv("PTAMD_SHADOW_BLOCKS_PER_CU")) r->shadow_blocks_per_cu = (uint32_t)std::max(1, std::min(8, atoi(e)));
   hipDeviceProp_t prop;
@@ -620,7 +621,6 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
   const uint32_t sif = r->samples_in_flight;
   r->grid = (uint32_t)r->num_cu * r->blocks_per_cu;                 // raygen, hit records: 256-thread blocks
   r->shade_grid = (uint32_t)r->num_cu * shade_blocks_per_cu();     // as many blocks as k_shade's registers / LDS keep resident
-  r->camera_grid = (uint32_t)r->num_cu * camera_blocks_per_cu();
   r->primary_grid = (uint32_t)r->num_cu * primary_blocks_per_cu();
   r->closest_grid = (uint32_t)r->num_cu * (r->two_level ? trace_blocks_per_cu_two_level() : r->closest_blocks_per_cu);
   r->shadow_grid = (uint32_t)r->num_cu * (r->two_level ? trace_blocks_per_cu_two_level() : r->shadow_blocks_per_cu);

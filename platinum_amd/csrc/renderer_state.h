@@ -156,7 +156,6 @@ struct pt_renderer {
   std::vector<uint32_t> sel_set;    // pt_set_selection: the ids, sorted and without duplicates
   DevBuf<uint32_t> sel_ids;         // sel_set on the device
   DevBuf<float> sel_cov;            // the set's coverage image: what k_selection_overlay reads
-  bool sel_no_early_out = false;    // $PTAMD_NO_SELECTION_EARLY_OUT: blocks that see no coverage run on (the A/B switch; the same bytes)
   // transparent film (film.hip): only a render started with film_opts.enabled allocates or launches any of it; the composed
   // source only once a target of such a render is read under a backdrop other than PT_BACKDROP_SCENE
   pt_film_options film_opts{};
@@ -200,7 +199,8 @@ struct pt_renderer {
   Rect rect{};                      // what this render samples: the region, or the whole frame
   uint32_t ad_tiles0 = 0;           // length of the first active list: the lists' capacity, the most tiles a batch can cover
   // per-pixel leaf lists of the camera rays (camera_lists.hip): built at pt_start_render for a pinhole camera over the 6-wide one-BVH
-  // structure of a full-frame, non-adaptive render; every other render releases them and traces bounce 0 with k_trace_closest as before
+  // structure of a full-frame, non-adaptive render (host_scene.h camera_lists_wanted); every other render releases them and traces bounce 0 with
+  // k_raygen + k_trace_closest
   DevBuf<CamListEntry> cam_entries;    // [pixel slot][cam_cap]
   DevBuf<uint32_t> cam_count;          // [pixel slot] entries, or kCamWalk
   DevBuf<CamListCounters> cam_counters;
@@ -208,8 +208,6 @@ struct pt_renderer {
   bool no_camera_lists = false;        // $PTAMD_NO_CAMERA_LISTS: never build them (the A/B switch)
   uint32_t cam_cap = 0, cam_cap_override = 0;   // entries per pixel; $PTAMD_TEST_CAMLIST_CAP (tests only: a tiny capacity exercises the kCamWalk path)
   pt_camera_list_stats cam_stats{};
-  uint32_t camera_grid = 0;
-  bool no_fused_camera = false;        // $PTAMD_NO_FUSED_CAMERA: bounce 0 as k_raygen + k_trace_camera, not as k_camera_primary (the A/B switch)
   uint32_t primary_grid = 0;
   uint32_t closest_grid = 0, shadow_grid = 0, closest_blocks_per_cu = PT_CLOSEST_WAVES, shadow_blocks_per_cu = PT_SHADOW_WAVES;  // persistent trace grids, each sized for its kernel's occupancy
   uint32_t last_batch_ns = 0, last_batch_first = 0;  // the batch Lbuf holds ($PTAMD_DEBUG_PIXEL)

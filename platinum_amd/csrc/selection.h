@@ -7,9 +7,7 @@
 namespace pt {
 
 // Draws the outline and the tint of `o` onto the W x H target (0xAABBGGRR per pixel, in place) from `coverage` (W x H floats, read only):
-// one k_selection_overlay block per 16 x 16 pixels.  `early_out` = false keeps the blocks that see no coverage from returning early (the
-// A/B switch of tools/selection_timing.py; the bytes are the same).
-void launch_selection_overlay(hipStream_t s, uint32_t* target, const float* coverage, uint32_t width, uint32_t height, const pt_selection_options& o,
-                              bool early_out = true);
+// one k_selection_overlay block per 16 x 16 pixels.
+void launch_selection_overlay(hipStream_t s, uint32_t* target, const float* coverage, uint32_t width, uint32_t height, const pt_selection_options& o);
 
 }  // namespace pt

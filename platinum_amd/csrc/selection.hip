@@ -16,7 +16,7 @@
 namespace pt {
 
 __global__ void __launch_bounds__(256) k_selection_overlay(uint32_t* __restrict__ target, const float* __restrict__ coverage, uint32_t width,
-                                                           uint32_t height, uint32_t blocks_x, SelParams P, uint32_t early_out) {
+                                                           uint32_t height, uint32_t blocks_x, SelParams P) {
   __shared__ float tile[kSelTileMax * kSelTileMax];
   __shared__ float weights[kSelTapsMax * kSelTapsMax];
   const uint32_t by = blockIdx.x / blocks_x, bx = blockIdx.x - by * blocks_x;
@@ -34,8 +34,7 @@ __global__ void __launch_bounds__(256) k_selection_overlay(uint32_t* __restrict_
     const uint32_t j = i / taps;
     weights[i] = sel_weight(P.lim, (int32_t)(i - j * taps) - R, (int32_t)j - R);
   }
-  const bool any = __syncthreads_or(some) != 0;
-  if (early_out && !any) return;
+  if (__syncthreads_or(some) == 0) return;
   const bool full = __syncthreads_and(ones) != 0;
   const uint32_t lx = threadIdx.x & (kSelBlock - 1u), ly = threadIdx.x / kSelBlock;
   const uint32_t x = bx * kSelBlock + lx, y = by * kSelBlock + ly;
@@ -51,11 +50,9 @@ __global__ void __launch_bounds__(256) k_selection_overlay(uint32_t* __restrict_
   if (after != before) *px = after;
 }
 
-void launch_selection_overlay(hipStream_t s, uint32_t* target, const float* coverage, uint32_t width, uint32_t height, const pt_selection_options& o,
-                              bool early_out) {
+void launch_selection_overlay(hipStream_t s, uint32_t* target, const float* coverage, uint32_t width, uint32_t height, const pt_selection_options& o) {
   const uint32_t blocks_x = (width + kSelBlock - 1u) / kSelBlock, blocks_y = (height + kSelBlock - 1u) / kSelBlock;
-  hipLaunchKernelGGL(k_selection_overlay, dim3(blocks_x * blocks_y), dim3(256), 0, s, target, coverage, width, height, blocks_x, sel_params(o),
-                     early_out ? 1u : 0u);
+  hipLaunchKernelGGL(k_selection_overlay, dim3(blocks_x * blocks_y), dim3(256), 0, s, target, coverage, width, height, blocks_x, sel_params(o));
 }
 
 }  // namespace pt

@@ -1,8 +1,8 @@
 """The build of the fused bounce-0 kernel (k_camera_primary, kernels.hip), no GPU: registers, scratch, occupancy and LDS as
 tools/kernel_resources.sh reports them for the Makefile's flags, and where in its code the scratch accesses lie.  The wave walk
 (k_camera_primary<true>, batches of a multiple of 64 samples: the flagship's) holds the node in scalar registers and must not touch scratch
-anywhere; the per-lane instantiation inherits k_trace_camera's loop and its budget, with every scratch access outside the entry / triangle
-loop.  The kernels that were there before keep the lines they had."""
+anywhere; the per-lane instantiation runs cam_trace_ray's loop (pt_camlist.h) inside that loop's budget, with every scratch access outside the
+entry / triangle loop.  The kernels that were there before keep the lines they had."""
 import os
 import re
 import subprocess
@@ -18,7 +18,6 @@ BUDGET = {
 UNCHANGED = (
     "k_raygen VGPRs 48 scratch 0 spill 0 occ 8 LDS 0",
     "k_raygen_adaptive VGPRs 48 scratch 0 spill 0 occ 8 LDS 0",
-    "k_trace_camera VGPRs 80 scratch 32 spill 13 occ 6 LDS 0",
     "k_trace_closest_unlisted VGPRs 76 scratch 0 spill 0 occ 6 LDS 22528",
     "k_chunk_tables VGPRs 20 scratch 0 spill 0 occ 8 LDS 9220",
 )
@@ -37,7 +36,7 @@ def test_the_fused_kernel_stays_inside_its_budgets_and_its_neighbours_keep_their
         v, s, sp, o, l = seen[name]
         print(name, "VGPRs %d scratch %d spill %d occ %d LDS %d" % seen[name])
         assert v <= vgpr and s <= scratch and sp <= spill and o >= occ and l == lds, (name, seen[name])
-    assert seen["void k_camera_primary<true>"][3] >= seen["k_trace_camera"][3]
+    assert seen["void k_camera_primary<true>"][3] >= 6   # the waves per SIMD of the list trace it took over
     for line in UNCHANGED:
         assert line in lines, line
 

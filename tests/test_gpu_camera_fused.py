@@ -1,6 +1,6 @@
-"""GPU: bounce 0 as one kernel (k_camera_primary) leaves every bit where k_raygen + k_trace_camera leave it.  Three renderers in
-one process — the default, one created under $PTAMD_NO_FUSED_CAMERA=1 (the parent's two launches) and one under $PTAMD_NO_CAMERA_LISTS=1 (the
-ordinary traversal) — must agree on every accumulator word and on the ray counters.  The shapes are the smallest at which each path of the
+"""GPU: bounce 0 as one kernel (k_camera_primary) leaves every bit where k_raygen + k_trace_closest leave it.  Two renderers in
+one process — the default and one created under $PTAMD_NO_CAMERA_LISTS=1 (the ordinary traversal) — must agree on every accumulator word and on
+the ray counters.  The shapes are the smallest at which each path of the
 kernel can go wrong: batches whose iterations straddle pixels (the per-lane walk), batches of a multiple of 64 samples (the wave walk, with
 whole iterations squeezed out of partial tiles), a tail batch, flagged pixels behind the fused kernel, cut-outs and misses, and the AOV pass
 that reads the queue behind it."""
@@ -16,7 +16,7 @@ from platinum_amd.renderer import Renderer  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-SWITCHES = ("PTAMD_NO_FUSED_CAMERA", "PTAMD_NO_CAMERA_LISTS", "PTAMD_TEST_CAMLIST_CAP")
+SWITCHES = ("PTAMD_NO_CAMERA_LISTS", "PTAMD_TEST_CAMLIST_CAP")
 
 
 def _renderer_under(env):
@@ -33,21 +33,20 @@ def _renderer_under(env):
 
 
 @pytest.fixture(scope="module")
-def trio():
-    """(fused, split, no lists)"""
+def pair():
+    """(fused, no lists)"""
     for k in SWITCHES:
         assert os.environ.get(k, "0") in ("", "0"), "this module compares the switches' two sides"
-    rs = [Renderer(device=0), _renderer_under({"PTAMD_NO_FUSED_CAMERA": "1"}), _renderer_under({"PTAMD_NO_CAMERA_LISTS": "1"})]
+    rs = [Renderer(device=0), _renderer_under({"PTAMD_NO_CAMERA_LISTS": "1"})]
     yield rs
     for r in rs:
         r.close()
 
 
 @pytest.fixture(scope="module")
-def trio_tiny():
-    """the same three with two entries per pixel: some pixels are left to the walk"""
-    rs = [_renderer_under({"PTAMD_TEST_CAMLIST_CAP": "2"}), _renderer_under({"PTAMD_TEST_CAMLIST_CAP": "2", "PTAMD_NO_FUSED_CAMERA": "1"}),
-          _renderer_under({"PTAMD_NO_CAMERA_LISTS": "1"})]
+def pair_tiny():
+    """the same two with two entries per pixel: some pixels are left to the walk"""
+    rs = [_renderer_under({"PTAMD_TEST_CAMLIST_CAP": "2"}), _renderer_under({"PTAMD_NO_CAMERA_LISTS": "1"})]
     yield rs
     for r in rs:
         r.close()
@@ -84,51 +83,49 @@ def _same(a, b):
         assert diff.size == 0, "%d words differ, the first at %d" % (diff.size, diff[0])
 
 
-def _all_three(rs, *args, **kw):
-    fused, split, walk = (_render(r, *args, **kw) for r in rs)
+def _both(rs, *args, **kw):
+    fused, walk = (_render(r, *args, **kw) for r in rs)
     assert fused[1][3] > 0
-    _same(fused, split)
     _same(fused, walk)
-    return fused, split, walk
+    return fused, walk
 
 
 @pytest.mark.parametrize("spp", [1, 46, 64, 130])
-def test_field_scene_with_partial_tiles(trio, field, spp):
+def test_field_scene_with_partial_tiles(pair, field, spp):
     # 67x41: partial tiles on both edges.  1 and 46 samples: iterations straddle pixels; 64: one pixel per iteration; 130: 64 + 64 + 2
-    fused, split, walk = _all_three(trio, field, (67, 41), spp, sif=64)
-    assert fused[2].built == 1 and fused[2].pixels_walk == 0 and split[2].built == 1 and walk[2].built == 0
+    fused, walk = _both(pair, field, (67, 41), spp, sif=64)
+    assert fused[2].built == 1 and fused[2].pixels_walk == 0 and walk[2].built == 0
 
 
-def test_two_iterations_per_pixel(trio, field):
-    _all_three(trio, field, (67, 41), 128, sif=128)
+def test_two_iterations_per_pixel(pair, field):
+    _both(pair, field, (67, 41), 128, sif=128)
 
 
-def test_cornell_in_two_consecutive_batches(trio):
-    fused, _, _ = _all_three(trio, scenes.cornell_scene("bench"), (64, 64), 16, steps=(8, 8), sif=8)
+def test_cornell_in_two_consecutive_batches(pair):
+    fused, _ = _both(pair, scenes.cornell_scene("bench"), (64, 64), 16, steps=(8, 8), sif=8)
     assert fused[2].built == 1 and fused[2].pixels_walk == 0
 
 
-def test_cutouts_and_environment(trio):
-    _all_three(trio, scenes.textured_scene(), (64, 48), 8)
+def test_cutouts_and_environment(pair):
+    _both(pair, scenes.textured_scene(), (64, 48), 8)
 
 
 @pytest.mark.parametrize("spp", [46, 64])
-def test_flagged_pixels_go_to_the_walk_behind_the_fused_kernel(trio_tiny, field, spp):
-    fused, split, _ = _all_three(trio_tiny, field, (67, 41), spp, sif=64)
-    for side in (fused, split):
-        assert side[2].built == 1 and side[2].capacity == 2 and 0 < side[2].pixels_walk < 67 * 41
+def test_flagged_pixels_go_to_the_walk_behind_the_fused_kernel(pair_tiny, field, spp):
+    fused, _ = _both(pair_tiny, field, (67, 41), spp, sif=64)
+    assert fused[2].built == 1 and fused[2].capacity == 2 and 0 < fused[2].pixels_walk < 67 * 41
 
 
 @pytest.mark.parametrize("spp", [46, 64])
-def test_first_hit_aovs_read_the_queue_behind_the_fused_kernel(trio, field, spp):
-    fused, _, _ = _all_three(trio, field, (67, 41), spp, sif=64, aov=True)
+def test_first_hit_aovs_read_the_queue_behind_the_fused_kernel(pair, field, spp):
+    fused, _ = _both(pair, field, (67, 41), spp, sif=64, aov=True)
     assert len(fused[3]) == 3 and np.any(fused[3][0][..., :3] != 0)
 
 
-def test_thin_lens_and_region_renders_keep_their_kernels(trio):
+def test_thin_lens_and_region_renders_keep_their_kernels(pair):
     sc = scenes.cornell_scene("bench")
-    _all_three(trio, sc, (64, 64), 8, region=(9, 5, 50, 41))
+    _both(pair, sc, (64, 64), 8, region=(9, 5, 50, 41))
     sc.camera.aperture = 2.0
     sc.camera.focus_distance = 15.0
-    fused, _, _ = _all_three(trio, sc, (64, 64), 8)
+    fused, _ = _both(pair, sc, (64, 64), 8)
     assert fused[2].built == 0

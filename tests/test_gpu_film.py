@@ -28,7 +28,7 @@ f32 = np.float32
 SIZE, SPP, BOUNCES = (24, 17), 16, 4     # 24x17: a partial tile row, and a 1-pixel-high edge tile
 W, H = SIZE
 INVALID, BAD_STATE, UNSUPPORTED = -1, -5, -6
-SWITCHES = ("PTAMD_NO_FUSED_CAMERA", "PTAMD_NO_CAMERA_LISTS", "PTAMD_TEST_CAMLIST_CAP")
+SWITCHES = ("PTAMD_NO_CAMERA_LISTS", "PTAMD_TEST_CAMLIST_CAP")
 AOVS = (abi.AOV_ALBEDO, abi.AOV_NORMAL, abi.AOV_MOMENTS)
 GREY = (0.18, 0.25, 0.6)
 
@@ -202,17 +202,17 @@ def _renderer_under(env):
                 os.environ[k] = v
 
 
-def test_fused_split_and_walked_camera_rays_give_the_same_film(r, sc, ref):
+def test_fused_and_walked_camera_rays_give_the_same_film(r, sc, ref):
     for k in SWITCHES:
         assert os.environ.get(k, "0") in ("", "0"), "this test compares the switches' two sides"
-    others = [_renderer_under({"PTAMD_NO_FUSED_CAMERA": "1"}), _renderer_under({"PTAMD_NO_CAMERA_LISTS": "1"})]
+    others = [_renderer_under({"PTAMD_NO_CAMERA_LISTS": "1"})]
     try:
         built = []
-        for x, what in zip([r] + others, ("fused", "split", "no lists")):
+        for x, what in zip([r] + others, ("fused", "no lists")):
             _start(x, sc, sif=SPP)
             built.append(x.cameraListStats().built)
             _assert_film(_finish(x), ref[2], what)
-        assert built == [1, 1, 0]
+        assert built == [1, 0]
     finally:
         for x in others:
             x.close()

@@ -20,7 +20,7 @@ NONE = ml.NONE
 LAYERS = (abi.MATTE_INSTANCE, abi.MATTE_MATERIAL)
 SIZE, SPP, BOUNCES = (24, 17), 64, 4     # 24x17: a partial tile row, and a 1-pixel-high edge tile
 INVALID, BAD_STATE, UNSUPPORTED = -1, -5, -6
-SWITCHES = ("PTAMD_NO_FUSED_CAMERA", "PTAMD_NO_CAMERA_LISTS", "PTAMD_TEST_CAMLIST_CAP")
+SWITCHES = ("PTAMD_NO_CAMERA_LISTS", "PTAMD_TEST_CAMLIST_CAP")
 
 
 @pytest.fixture(scope="module")
@@ -173,7 +173,7 @@ def test_every_other_output_is_the_same_bits_with_mattes_on(r, gmon):
         assert np.any(a != 0) and al.same_bits_or_both_nan(a, b).all()
 
 
-# ---- the three camera paths -----------------------------------------------------------------------------------------------------------------
+# ---- the two camera paths -------------------------------------------------------------------------------------------------------------------
 def _renderer_under(env):
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
@@ -187,18 +187,18 @@ def _renderer_under(env):
                 os.environ[k] = v
 
 
-def test_fused_split_and_walked_camera_rays_give_the_same_slots(r, field, field_ref):
+def test_fused_and_walked_camera_rays_give_the_same_slots(r, field, field_ref):
     for k in SWITCHES:
         assert os.environ.get(k, "0") in ("", "0"), "this test compares the switches' two sides"
     _ids, want = field_ref
-    others = [_renderer_under({"PTAMD_NO_FUSED_CAMERA": "1"}), _renderer_under({"PTAMD_NO_CAMERA_LISTS": "1"})]
+    others = [_renderer_under({"PTAMD_NO_CAMERA_LISTS": "1"})]
     try:
         built = []
-        for rr, what in zip([r] + others, ("fused", "split", "no lists")):
+        for rr, what in zip([r] + others, ("fused", "no lists")):
             _start(rr, field, SIZE, SPP, sif=SPP)
             built.append(rr.cameraListStats().built)
             _assert_slots(_finish(rr), want, what)
-        assert built == [1, 1, 0]
+        assert built == [1, 0]
     finally:
         for rr in others:
             rr.close()

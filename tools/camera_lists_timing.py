@@ -2,8 +2,7 @@
 """Camera-ray leaf lists on the GPU (DESIGN.md §3 "Camera rays from per-pixel leaf lists", §4 measurements): per workload the build's
 device time, the share of pixels left to the ordinary traversal, and the histogram of list lengths (before the capacity is applied).
 With --front-end: the event time of bounce 0's front end (raygen + closest classes of one render(0) call — all batches of the workload's
-samples — traced to a single bounce) of the fused kernel (k_camera_primary) against the split launches ($PTAMD_NO_FUSED_CAMERA=1), two
-renderers in one process, alternated.
+samples — traced to a single bounce): k_camera_primary, the table pass and the walk for flagged pixels.
 
 Run each invocation under its own time limit, e.g.  timeout -k 10 300 python tools/camera_lists_timing.py --workloads c3 c2 c5 --json out.json
 """
@@ -32,19 +31,6 @@ def measure(r, name):
             "samples_in_flight": r.stats().samples_in_flight}
 
 
-def renderer_under(env):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return Renderer(device=0)    # (the PTAMD_* switches are read at pt_create)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
 def front_end_ms(r, name, repeats=3):
     """raygen + closest event time of one render(0) call traced to ONE bounce: the camera rays' generation, table pass and trace"""
     make, w, h, spp, _ = scenes.CONFIGS[name]
@@ -63,7 +49,7 @@ def front_end_ms(r, name, repeats=3):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--front-end", action="store_true", help="time bounce 0's front end, fused against split")
+    ap.add_argument("--front-end", action="store_true", help="time bounce 0's front end")
     ap.add_argument("--workloads", nargs="+", default=["c3", "c2", "c5"], choices=sorted(scenes.CONFIGS))
     ap.add_argument("--json")
     args = ap.parse_args()
@@ -79,16 +65,9 @@ def main():
         h = m["length_histogram"]
         print("  length histogram: " + " ".join("%d:%d" % (k, n) for k, n in enumerate(h) if n) + "   (64 = 64 or more)")
     if args.front_end:
-        split = renderer_under({"PTAMD_NO_FUSED_CAMERA": "1"})
         for m in out:
-            a, b = [], []
-            for _ in range(2):    # alternate the sides
-                a += front_end_ms(r, m["workload"], 2)
-                b += front_end_ms(split, m["workload"], 2)
-            m["front_end_ms_fused"], m["front_end_ms_split"] = a, b
-            print("%s front end (raygen + closest of a one-bounce render): fused %s ms, split %s ms" % (m["workload"], " ".join("%.3f" % v for v in a),
-                  " ".join("%.3f" % v for v in b)))
-        split.close()
+            m["front_end_ms"] = front_end_ms(r, m["workload"], 4)
+            print("%s front end (raygen + closest of a one-bounce render): %s ms" % (m["workload"], " ".join("%.3f" % v for v in m["front_end_ms"])))
     r.close()
     if args.json:
         with open(args.json, "w") as f:

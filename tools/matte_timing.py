@@ -4,7 +4,7 @@
 Per workload (C3, C2, C5 at their benchmark sizes and bounce counts), with per-kernel HIP-event timing on:
   * the device time of k_matte_ids + k_accumulate_matte per batch of --samples samples: pt_stats.ms_accumulate of a render with mattes on
     minus the same render with mattes off (both matte kernels are timed in the accumulate class), per batch;
-  * beside it, that batch's accumulate class with mattes off (k_accumulate) and, from a renderer created under PTAMD_NO_FUSED_CAMERA=1 and
+  * beside it, that batch's accumulate class with mattes off (k_accumulate) and, from a renderer created under
     PTAMD_NO_CAMERA_LISTS=1 (the default path generates the camera rays inside the bounce-0 trace), its k_raygen: the yardsticks, which
     move 16 and 68 bytes per path where the mattes move 8;
   * one pt_read_matte of a 300-id set on the instance layer: wall time of the call (the resolve kernel, the upload of the ids and the
@@ -63,7 +63,7 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     r = Renderer(device=0)
-    plain = renderer_under({"PTAMD_NO_FUSED_CAMERA": "1", "PTAMD_NO_CAMERA_LISTS": "1"})
+    plain = renderer_under({"PTAMD_NO_CAMERA_LISTS": "1"})
     r.setProfiling(True)
     plain.setProfiling(True)
     out = {"samples_per_batch": a.samples, "batches": a.batches, "reps": a.reps, "configs": {}}

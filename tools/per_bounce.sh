@@ -16,13 +16,13 @@ names = [r["Kernel_Name"] for r in rows]
 last = max(i for i, n in enumerate(names) if "k_raygen" in n or "k_camera_primary" in n)   # the timed batch = the LAST raygen (or fused bounce 0) onwards
 seq = rows[last:]
 def dur(r): return (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
-# (bounce 0 of a render with camera-ray lists is k_camera_primary — raygen and trace in one kernel — or k_trace_camera under
-#  PTAMD_NO_FUSED_CAMERA=1, plus k_trace_closest_unlisted when pixels were left to the walk: one entry)
+# (bounce 0 of a render with camera-ray lists is k_camera_primary — raygen and trace in one kernel — plus k_trace_closest_unlisted when
+#  pixels were left to the walk: one entry)
 cl = []
 for r in seq:
     n = r["Kernel_Name"]
     if "k_trace_closest_unlisted" in n: cl[-1] += dur(r)
-    elif "k_trace_closest" in n or "k_trace_camera" in n or "k_camera_primary" in n: cl.append(dur(r))
+    elif "k_trace_closest" in n or "k_camera_primary" in n: cl.append(dur(r))
 sh = [dur(r) for r in seq if "k_shade" in r["Kernel_Name"] and "records" not in r["Kernel_Name"]]
 sd = [dur(r) for r in seq if "k_trace_shadow" in r["Kernel_Name"]]
 print("$WL: bounce | closest chunks  ms  Grays/s | shade ms | shadow chunks  ms  Grays/s")

@@ -7,7 +7,6 @@ with the spread min..max.  Per size:
   * off            the overlay disabled: the launches of a build without the feature
   * small / large  the overlay on at widths 2 and 16, for SMALL (two rows of spheres in the middle of the field: a few percent of the frame)
                    and LARGE (instance 0, the floor and the walls: most of it); the fraction of pixels the set touches is measured and reported
-  * no early out   the same small selection on a renderer created under PTAMD_NO_SELECTION_EARLY_OUT=1 (the block vote's A/B)
 --off-only times the first row alone and needs nothing of the feature: it runs against an older build too.
 
 Run each invocation under its own time limit, e.g.  timeout -k 10 600 python tools/selection_timing.py --json out.json
@@ -45,19 +44,6 @@ def present_ms(r, presents, reps):
     return summary(out[1:])
 
 
-def renderer_under(env):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return Renderer(device=0)    # (the PTAMD_* switches are read at pt_create)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
 def start(r, sc, size, spp, bounces, matte):
     if matte:
         r.setMatteOptions(enabled=1)
@@ -78,14 +64,12 @@ def main():
     factory, _w, _h, _spp, bounces = scenes.CONFIGS["c3"]
     sc = factory()
     r = Renderer(device=0)
-    ab = None if a.off_only else renderer_under({"PTAMD_NO_SELECTION_EARLY_OUT": "1"})
     out = {"presents": a.presents, "reps": a.reps, "sizes": {}}
     for size in SIZES:
         row = {}
         start(r, sc, size, a.spp, bounces, matte=not a.off_only)
         row["off"] = present_ms(r, a.presents, a.reps)
         if not a.off_only:
-            start(ab, sc, size, a.spp, bounces, matte=True)
             for name, ids in (("small", SMALL), ("large", LARGE)):
                 r.setSelection(ids)
                 cov = r.readbackMatte(abi.MATTE_INSTANCE, ids)
@@ -93,17 +77,11 @@ def main():
                 for width in (2.0, 16.0):
                     r.setSelectionOptions(enabled=1, width=width)
                     row["%s_width_%g" % (name, width)] = present_ms(r, a.presents, a.reps)
-                    if name == "small":
-                        ab.setSelection(ids)
-                        ab.setSelectionOptions(enabled=1, width=width)
-                        row["small_width_%g_no_early_out" % width] = present_ms(ab, a.presents, a.reps)
                 r.setSelectionOptions(enabled=0)
             row["off_again"] = present_ms(r, a.presents, a.reps)
         out["sizes"]["%dx%d" % size] = row
         print("%dx%d" % size, json.dumps(row), flush=True)
     r.close()
-    if ab is not None:
-        ab.close()
     if a.json:
         with open(a.json, "w") as f:
             json.dump(out, f, indent=1)

@@ -36,7 +36,7 @@ def short(name):
     m = re.search(r"k_camera_primary<(?:\(bool\))?(\w+)>", name)
     if m:   # bounce 0 as one kernel: the wave walk (batches of a multiple of 64 samples) is the bare name
         return "k_camera_primary" + ("" if m.group(1) in ("true", "1") else "[per-lane]")
-    for k in KEYS + ("k_trace_camera", "k_trace_closest_unlisted"):
+    for k in KEYS + ("k_trace_closest_unlisted",):
         if k in name:
             return k
     if "rocprim" in name:
