@@ -667,7 +667,7 @@ k_camera_primary(DeviceScene S, PathState st, vec4* __restrict__ Lbuf, vec4* __r
 // compaction of the survivor.  NEE before the sample (each random number is addressed by its dimension, so the order does
 // not matter) means the shadow record is not held in registers across the sampling code.
 #ifndef PT_SHADE_WAVES
-#define PT_SHADE_WAVES 4   // waves per SIMD the kernel is compiled for (128 VGPRs; 14 spill to scratch)
+#define PT_SHADE_WAVES 4   // waves per SIMD the kernel is compiled for (128 VGPRs at most; its row in tests/test_kernel_resources.py)
 #endif
 #ifndef PT_SHADE_BLOCK
 #define PT_SHADE_BLOCK 256

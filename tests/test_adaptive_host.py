@@ -1,10 +1,8 @@
 """CPU: the tile-adaptive sampling criterion (platinum_amd/csrc/pt_adaptive.h, built for the host by tests/emu/adaptive_emu.cpp) against a
-float64 restatement of DESIGN.md §3b, its edge cases, the denoiser's per-pixel-N prep, the pt_adaptive_options ABI, and the adaptive
-kernels' resource budgets."""
+float64 restatement of DESIGN.md §3b, its edge cases, the denoiser's per-pixel-N prep, and the pt_adaptive_options ABI.  (The adaptive
+kernels' resource budgets: tests/test_kernel_resources.py.)"""
 import ctypes as C
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -15,8 +13,6 @@ import adaptive_lib as al  # noqa: E402
 import denoise_lib as dl  # noqa: E402
 from test_denoise_host import random_inputs  # noqa: E402
 from platinum_amd import abi  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("n,seed", [(2, 0), (3, 1), (16, 2), (33, 3), (256, 4), (4096, 5)])
@@ -115,21 +111,3 @@ def test_adaptive_options_abi():
         setattr(bad, field, value)
         assert lib.pt_set_adaptive_options(None, C.byref(bad)) == -1, field
         assert word in lib.pt_last_error(), (field, lib.pt_last_error())
-
-
-def test_adaptive_kernels_stay_inside_the_budgets_of_the_kernels_they_mirror():
-    from test_kernel_resources import BUDGET
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh")], capture_output=True, text=True, timeout=600).stdout
-    lines = {}
-    for line in out.splitlines():
-        m = re.match(r"(.+?) VGPRs (\d+) scratch (\d+) spill (\d+) occ (\d+) LDS (\d+)", line.strip())
-        if m:
-            lines[m.group(1)] = (line.strip(), tuple(int(x) for x in m.groups()[1:]))
-    for name, budget_of in (("k_raygen_adaptive", "k_raygen"), ("k_accumulate_adaptive", "k_accumulate")):
-        assert name in lines, sorted(lines)
-        v, s, _spill, o, l = lines[name][1]
-        vgpr, scratch, occ, lds = BUDGET[budget_of]
-        assert v <= vgpr and s <= scratch and o >= occ and l <= lds, lines[name][0]
-    # the kernels an adaptive-off render launches are left as they were
-    assert lines["k_raygen"][0] == "k_raygen VGPRs 48 scratch 0 spill 0 occ 8 LDS 0"
-    assert lines["k_accumulate"][0] == "k_accumulate VGPRs 54 scratch 0 spill 0 occ 4 LDS 36864"

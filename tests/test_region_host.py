@@ -1,9 +1,9 @@
 """CPU: render regions: the pt_render_region ABI and its validation, pt_region_tiles against a numpy enumeration, the
 host-only region reference (region_lib.reference_region_render) against the host's uniform renders and against the full-frame adaptive
-reference, the C++ header's accessors, and the resource budgets of the kernels that took the rectangle predicate, a pitch or an origin."""
+reference, and the C++ header's accessors.  (The budgets of the kernels that took the rectangle predicate, a pitch or an origin:
+tests/test_kernel_resources.py.)"""
 import ctypes as C
 import os
-import re
 import subprocess
 import sys
 
@@ -190,40 +190,3 @@ def test_python_wrapper_has_the_region_accessors():
     from platinum_amd.renderer import Renderer
     for member in ("renderRegion", "setRenderRegion", "clearRenderRegion"):
         assert callable(getattr(Renderer, member)), member
-
-
-# ---- kernel budgets ----------------------------------------------------------------------------------------------------------------------
-# kernel -> (max VGPRs, min waves per SIMD, max LDS bytes): the kernels that took the rectangle predicate, a row pitch or an origin.  The
-# virtual-tile kernels mirror the full-frame kernels and stay inside their budgets (tests/test_kernel_resources.py BUDGET for the first two;
-# k_accumulate_aov's own resource line, 150 VGPRs at 2 waves per SIMD with its 27 KB of staging, for the third).  The filter kernels and the
-# checkpoint are launched with 256 threads and no LDS and were built for full occupancy: 64 VGPRs is what 8 waves per SIMD leave a lane.
-REGION_BUDGET = {
-    "k_accumulate_aov_adaptive": (150, 2, 27 * 1024),
-    "k_adaptive_check": (64, 8, 0),
-    "k_dn_prep": (64, 8, 0),
-    "k_dn_prep_counts": (64, 8, 0),
-    "k_atrous": (64, 8, 0),
-    "k_dn_copy": (64, 8, 0),
-}
-
-
-def test_region_kernels_stay_inside_the_budgets_of_the_kernels_they_mirror():
-    from test_kernel_resources import BUDGET
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh")], capture_output=True, text=True, timeout=600).stdout
-    lines = {}
-    for line in out.splitlines():
-        mt = re.match(r"(.+?) VGPRs (\d+) scratch (\d+) spill (\d+) occ (\d+) LDS (\d+)", line.strip())
-        if mt:
-            lines[mt.group(1)] = (line.strip(), tuple(int(x) for x in mt.groups()[1:]))
-    budgets = {"k_raygen_adaptive": BUDGET["k_raygen"], "k_accumulate_adaptive": BUDGET["k_accumulate"]}
-    budgets.update({k: (v, 0, occ, lds) for k, (v, occ, lds) in REGION_BUDGET.items()})
-    for name, (vgpr, scratch, occ, lds) in budgets.items():
-        assert name in lines, (name, sorted(lines))
-        v, s, spill, o, l = lines[name][1]
-        assert v <= vgpr and s <= scratch == 0 and spill == 0 and o >= occ and l <= lds, lines[name][0]
-    # k_accumulate_aov is the kernel k_accumulate_aov_adaptive mirrors: the budget above is its own line
-    v, s, spill, o, l = lines["k_accumulate_aov"][1]
-    assert (v, s, spill, o) == (150, 0, 0, 2) and l <= 27 * 1024, lines["k_accumulate_aov"][0]
-    # a render without a region and without adaptive sampling launches the kernels it launched before, as they were
-    assert lines["k_raygen"][0] == "k_raygen VGPRs 48 scratch 0 spill 0 occ 8 LDS 0"
-    assert lines["k_accumulate"][0] == "k_accumulate VGPRs 54 scratch 0 spill 0 occ 4 LDS 36864"
