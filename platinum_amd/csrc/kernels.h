@@ -9,8 +9,6 @@
 
 namespace pt {
 
-constexpr int kBlock = 256;  // 4 waves; traversal kernels keep a 16 KiB LDS stack slab per block
-
 struct WaveStats { unsigned long long closest, shadow, shaded, paths; };  // per physical wave, owner-updated, reduced by k_fold_counters
 
 // Queue segments (kernels.hip): segment s = the queue share of `tiles_per_seg` consecutive tiles (pt_layout.h segment_first_tile) under
@@ -51,8 +49,13 @@ void launch_raygen(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState
 // `bounce_closest`) and, if do_shadow, of the shadow queue consumed at `bounce_shadow`.
 void launch_chunk_tables(hipStream_t s, Segments seg, uint32_t cur, BatchCounters* ctr, uint32_t bounce_closest,
                          uint32_t bounce_shadow, bool do_shadow);
-uint32_t trace_block_threads(bool two_level);
-uint32_t trace_blocks_per_cu_two_level();  // 256 (7 blocks per CU) for one BVH, 1024 (one block per CU) for the two-level structure
+// What the host has to know of the structure the trace kernels walk (pt_bvh.h Walk4 / Walk6 / WalkTwoLevel, as kernels.hip was compiled)
+struct TraceWalk {
+  uint32_t block_threads, closest_blocks_per_cu, shadow_blocks_per_cu;
+  bool blocks_tunable;         // $PTAMD_CLOSEST_BLOCKS_PER_CU / $PTAMD_SHADOW_BLOCKS_PER_CU apply (not where one block fills a CU's LDS)
+  uint32_t pushes_per_level, exit_entries;   // stack entries a tree of L levels needs: L * pushes_per_level + exit_entries
+};
+TraceWalk trace_walk(bool two_level, bool wide6);
 void launch_trace_closest(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState st, vec4* hit, Segments seg, uint32_t cur,
                           BatchCounters* ctr, uint32_t bounce, uint32_t* spill, int32_t* hitlog, uint32_t log_stride, bool count);
 // Bounce 0 of a full-frame render batch from the per-pixel leaf lists `cl` (camera_lists.hip) instead of launch_raygen + launch_trace_closest, as

@@ -27,6 +27,8 @@
 // Compiled with -ffp-contract=off (deterministic fp32 contract, pt_math.h).
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "kernels.h"
 #include "pt_camlist.h"
 #include "pt_denoise.h"
@@ -339,22 +341,14 @@ __global__ void __launch_bounds__(kBlock) k_raygen_adaptive(DeviceScene S, PathS
 // exhausted with nobody else able to advance), every lane with a queued leaf runs ONE triangle test.  The triangle code
 // therefore executes with most lanes busy instead of whenever a single lane met a leaf.  A ray is finished when its node
 // stack is exhausted and its queue is empty (any-hit: on the first accepted hit).
-#ifndef PT_TWO_BLOCK
-#define PT_TWO_BLOCK 1024
-#define PT_TWO_BLOCKS_PER_CU 1
-#define PT_TWO_LDS_NODES 1024
-#endif
-constexpr uint32_t kTraceBlock2 = PT_TWO_BLOCK;  // two-level kernels: ONE block per CU (4 waves per SIMD) sharing the staged node array
-constexpr uint32_t kLdsNodes = PT_TWO_LDS_NODES; // 64 KB of nodes in LDS beside the 88 KB of stacks and leaf queues of 1024 lanes (152 of 160 KB)
 #ifndef PT_TRI_VOTE
 #define PT_TRI_VOTE 2
 #endif
-template <bool ANY, bool COUNT, bool TWO, bool W6 = false>
+template <class W, bool ANY, bool COUNT>
 __device__ __forceinline__ void wave_traverse(const DeviceScene& S, const BvhNode* lds_nodes, TravState& ts, TraversalCount* tc) {
-  // room a node step needs in the lane's leaf queue: one entry per child it can queue (4-wide), one entry per node (6-wide: a range)
-  constexpr int kRoom = W6 ? 1 : 4, kRows = W6 ? kPendLeaves6 : kPendLeaves;
-  if (ts.cur != kInvalidRef && ts.st.npend <= kRows - kRoom) {
-    if (TWO) {
+  constexpr int kFull = W::kPendRows - W::kRoom;   // a lane with more leaves queued has no room for a node step's
+  if (ts.cur != kInvalidRef && ts.st.npend <= kFull) {
+    if (W::kTwoLevel) {
       // Exit markers are handled at once; ENTERING an instance (two dependent loads, three divides) is voted on like the
       // triangle tests: it runs when half of the lanes that can advance are waiting at an instance, or nobody has a node.
       trav_leave(ts);
@@ -364,30 +358,27 @@ __device__ __forceinline__ void wave_traverse(const DeviceScene& S, const BvhNod
       if (mi != 0 && (2 * __popcll(mi) >= __popcll(mn) || mn == 0)) {
         if (at_inst) trav_resolve(S, ts);
       } else if (at_node) {
-        if (lds_nodes) trav_node<COUNT, true>(lds_nodes, ts, tc); else trav_node<COUNT, true>(S.nodes, ts, tc);
+        if (lds_nodes) W::template node<COUNT>(lds_nodes, ts, tc); else W::template node<COUNT>(S.nodes, ts, tc);
       }
-    } else if (W6) {
-      trav_node6<COUNT>(S.nodes, ts, tc);
     } else {
-      trav_node<COUNT, false>(S.nodes, ts, tc);
+      W::template node<COUNT>(S.nodes, ts, tc);
     }
   }
   const bool pending = ts.st.npend > 0;
-  const bool stuck = pending && (ts.cur == kInvalidRef || ts.st.npend > kRows - kRoom);
+  const bool stuck = pending && (ts.cur == kInvalidRef || ts.st.npend > kFull);
   const bool advancing = ts.cur != kInvalidRef && !stuck;
   const unsigned long long mp = __ballot(pending);
   if (mp == 0) return;
   // triangle round when half of the lanes holding a ray have a queued leaf, a lane's queue is full, or nobody can advance
-  const bool go = PT_TRI_VOTE * __popcll(mp) >= __popcll(__ballot(1)) || __ballot(ts.st.npend > kRows - kRoom) != 0 || __ballot(advancing) == 0;
+  const bool go = PT_TRI_VOTE * __popcll(mp) >= __popcll(__ballot(1)) || __ballot(ts.st.npend > kFull) != 0 || __ballot(advancing) == 0;
   if (go && pending) {
-    const bool fin = W6 ? trav_pending_leaf6<ANY, COUNT>(S, ts, tc) : trav_pending_leaf<ANY, COUNT>(S, ts, tc);
-    if (fin) { ts.cur = kInvalidRef; ts.st.npend = 0; ts.st.sp = 0; }
+    if (W::template leaf<ANY, COUNT>(S, ts, tc)) { ts.cur = kInvalidRef; ts.st.npend = 0; ts.st.sp = 0; }
   }
 }
 
 // the two-level structure's nodes -> LDS (when they fit); returns the pointer the traversal should use (nullptr: HBM)
-__device__ __forceinline__ const BvhNode* stage_nodes(const DeviceScene& S, BvhNode* lds_nodes) {
-  if (S.node_count > kLdsNodes) return nullptr;
+__device__ __forceinline__ const BvhNode* stage_nodes(const DeviceScene& S, BvhNode* lds_nodes, uint32_t room) {
+  if (S.node_count > room) return nullptr;
   const uint4* src = reinterpret_cast<const uint4*>(S.nodes);
   uint4* dst = reinterpret_cast<uint4*>(lds_nodes);
   for (uint32_t i = threadIdx.x; i < S.node_count * 4; i += blockDim.x) dst[i] = src[i];
@@ -395,22 +386,24 @@ __device__ __forceinline__ const BvhNode* stage_nodes(const DeviceScene& S, BvhN
   return lds_nodes;
 }
 
-// ---- closest hit ---------------------------------------------------------------------------------------------------
-// (the body of k_trace_closest.  UNLISTED: the instantiation behind k_trace_closest_unlisted, which walks the tree for the camera rays of the
-//  pixels whose list did not fit and drops every other ray of the queue: k_camera_primary has traced those.  `cursor`: the launch's claim cursor.)
-template <bool COUNT, bool TWO, bool W6, bool UNLISTED>
-__device__ __forceinline__ void trace_closest_body(const DeviceScene& S, PathState st, vec4* __restrict__ hit, const Segments& seg, uint32_t cur,
-                                                   BatchCounters* __restrict__ ctr, uint32_t bounce, uint32_t* __restrict__ cursor,
-                                                   uint32_t* __restrict__ spill, int32_t* __restrict__ hitlog, uint32_t log_stride, const CameraLists& cl) {
+// ---- the persistent ray loop of the trace kernels ---------------------------------------------------------------------
+// What k_trace_closest, k_trace_closest_unlisted and k_trace_shadow share: the LDS stack and leaf queue (and the staged nodes), the chunk
+// claims from `table` / `total` / `cursor`, the take / traverse / refill-vote loop over the wave's 64 rays, the COUNT fold into *nodes / *tris
+// and the PT_TAIL_* marks of kind TAIL.  The kernel owns the ray (`ts`, `ray`) and says what differs: begin(stack, tc) loads ray `ray` and
+// runs trav_init on it (or drops it: ray = kInvalidRef), true = finished at once; finish() writes the ray's result and sets ray = kInvalidRef.
+template <class W, bool ANY, bool COUNT, int TAIL, class Begin, class Finish>
+__device__ __forceinline__ void trace_rays(const DeviceScene& S, const Segments& seg, const uint32_t* __restrict__ table, uint32_t total,
+                                           uint32_t* __restrict__ cursor, uint32_t* __restrict__ spill, BatchCounters* __restrict__ ctr, uint32_t bounce,
+                                           unsigned long long* nodes, unsigned long long* tris, Begin begin, Finish finish) {
   PT_TAIL_BEGIN
-  constexpr uint32_t kTB = TWO ? kTraceBlock2 : kBlock;
-  __shared__ uint32_t lds_stack[(W6 ? kLdsStack6 : kLdsStack) + 1][kTB];
-  __shared__ uint32_t lds_pend[(W6 ? kPendLeaves6 : kPendLeaves) + 1][kTB];
-  __shared__ BvhNode lds_nodes_buf[TWO && kLdsNodes ? kLdsNodes : 1];
-  const BvhNode* lds_nodes = TWO && kLdsNodes ? stage_nodes(S, lds_nodes_buf) : nullptr;
+  constexpr uint32_t kTB = W::kThreads;
+  __shared__ uint32_t lds_stack[W::kStackRows + 1][kTB];
+  __shared__ uint32_t lds_pend[W::kPendRows + 1][kTB];
+  __shared__ BvhNode lds_nodes_buf[W::kLdsNodes ? W::kLdsNodes : 1];
+  const BvhNode* lds_nodes = W::kLdsNodes ? stage_nodes(S, lds_nodes_buf, W::kLdsNodes) : nullptr;
   const uint32_t lane = wave_lane();
   ChunkClaims src;
-  src.init(seg.table_closest, ctr->chunks_closest[bounce], cursor, seg, lane);
+  src.init(table, total, cursor, seg, lane);
   TraversalStack stack;
   stack.lds = &lds_stack[0][threadIdx.x];
   stack.pend = &lds_pend[0][threadIdx.x];
@@ -423,7 +416,60 @@ __device__ __forceinline__ void trace_closest_body(const DeviceScene& S, PathSta
   //  1.5x slower on secondary rays)
   TravState ts;
   uint32_t ray = kInvalidRef;
-  auto finish = [&]() {
+  const uint32_t refill = seg.refill_threshold;
+  for (;;) {
+    PT_TAIL_MARK
+    const uint32_t fresh = src.take(ray == kInvalidRef);
+    PT_TAIL_T(tail_take)
+    if (fresh != kInvalidRef) {
+      ray = fresh;
+      if (begin(ray, ts, stack, COUNT ? &tc : nullptr)) finish(ray, ts);
+    }
+    PT_TAIL_T(tail_setup)
+    if (__ballot(ray != kInvalidRef) == 0) {
+      if (src.exhausted && src.pool_next == src.pool_end) break;
+      continue;
+    }
+    while (ray != kInvalidRef) {
+      wave_traverse<W, ANY, COUNT>(S, lds_nodes, ts, &tc);
+      if (ts.cur == kInvalidRef && ts.st.npend == 0) finish(ray, ts);
+      // lanes still in this loop vote: leave for a refill once the wave has emptied below the threshold
+      if (refill && !src.exhausted && (uint32_t)__popcll(__ballot(ray != kInvalidRef)) < refill) break;
+    }
+  }
+  if (COUNT) {
+    const uint32_t nn = wave_sum(tc.nodes), t = wave_sum(tc.tris);
+    if (lane == 0) {
+      atomicAdd(nodes, (unsigned long long)nn);
+      atomicAdd(tris, (unsigned long long)t);
+    }
+  }
+  PT_TAIL_END(TAIL)
+}
+
+// ---- closest hit ---------------------------------------------------------------------------------------------------
+// (the body of k_trace_closest.  UNLISTED: the instantiation behind k_trace_closest_unlisted, which walks the tree for the camera rays of the
+//  pixels whose list did not fit and drops every other ray of the queue: k_camera_primary has traced those.  `cursor`: the launch's claim cursor.)
+template <class W, bool COUNT, bool UNLISTED>
+__device__ __forceinline__ void trace_closest_body(const DeviceScene& S, PathState st, vec4* __restrict__ hit, const Segments& seg, uint32_t cur,
+                                                   BatchCounters* __restrict__ ctr, uint32_t bounce, uint32_t* __restrict__ cursor,
+                                                   uint32_t* __restrict__ spill, int32_t* __restrict__ hitlog, uint32_t log_stride, const CameraLists& cl) {
+  auto begin = [&](uint32_t& ray, TravState& ts, const TraversalStack& stack, TraversalCount* tc) {
+    const vec4 o4 = st.rayO[ray];
+    const vec4 d4 = st.rayD[ray];
+    float ir = 0.0f;  // alpha-test payload: the sample drawn before `intersect` (kernel.metal:510), only needed with cut-outs
+    if (S.has_alpha) ir = Halton{halton_table(S.halton), f2u(st.att[ray].w), f2u(d4.w) & kMetaDimMask}.sample1d();
+#ifdef PT_DEBUG_PID
+    ts.dbg = ctr->_pad[1] == bounce + 1u && segment_lbuf_base(seg, slot_segment(seg.nseg, ray)) + (f2u(d4.w) >> kMetaPidShift) == ctr->_pad[0];
+    if (ts.dbg) printf("dbg ray slot %u lane %u wave %u o %.9g %.9g %.9g d %.9g %.9g %.9g\n", ray, wave_lane(), wave_index(), o4.x, o4.y, o4.z, d4.x, d4.y, d4.z);
+#endif
+    if (UNLISTED && cl.count[pixel_slot_of_pid(segment_lbuf_base(seg, slot_segment(seg.nseg, ray)) + (f2u(d4.w) >> kMetaPidShift), seg.nsamples)] != kCamWalk) {
+      ray = kInvalidRef;   // a listed pixel's ray: hit[ray] holds k_camera_primary's answer
+      return false;
+    }
+    return trav_init(S, ts, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), 1e-3f, kInf, ir, stack, false, tc);
+  };
+  auto finish = [&](uint32_t& ray, TravState& ts) {
     const RayHit& h = ts.best;
 #ifdef PT_DEBUG_PID
     if (ts.dbg) printf("dbg finish: t %.9g u %.9g v %.9g tri %u gid %u\n", h.t, h.u, h.v, h.tri, h.gid >> 2);
@@ -439,52 +485,15 @@ __device__ __forceinline__ void trace_closest_body(const DeviceScene& S, PathSta
     }
     ray = kInvalidRef;
   };
-  const uint32_t refill = seg.refill_threshold;
-  for (;;) {
-    PT_TAIL_MARK
-    const uint32_t fresh = src.take(ray == kInvalidRef);
-    PT_TAIL_T(tail_take)
-    if (fresh != kInvalidRef) {
-      ray = fresh;
-      const vec4 o4 = st.rayO[ray];
-      const vec4 d4 = st.rayD[ray];
-      float ir = 0.0f;  // alpha-test payload: the sample drawn before `intersect` (kernel.metal:510), only needed with cut-outs
-      if (S.has_alpha) ir = Halton{halton_table(S.halton), f2u(st.att[ray].w), f2u(d4.w) & kMetaDimMask}.sample1d();
-#ifdef PT_DEBUG_PID
-      ts.dbg = ctr->_pad[1] == bounce + 1u && segment_lbuf_base(seg, slot_segment(seg.nseg, ray)) + (f2u(d4.w) >> kMetaPidShift) == ctr->_pad[0];
-      if (ts.dbg) printf("dbg ray slot %u lane %u wave %u o %.9g %.9g %.9g d %.9g %.9g %.9g\n", ray, lane, wave_index(), o4.x, o4.y, o4.z, d4.x, d4.y, d4.z);
-#endif
-      if (UNLISTED && cl.count[pixel_slot_of_pid(segment_lbuf_base(seg, slot_segment(seg.nseg, ray)) + (f2u(d4.w) >> kMetaPidShift), seg.nsamples)] != kCamWalk)
-        ray = kInvalidRef;   // a listed pixel's ray: hit[ray] holds k_camera_primary's answer
-      else if (trav_init(S, ts, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), 1e-3f, kInf, ir, stack, false, COUNT ? &tc : nullptr)) finish();
-    }
-    PT_TAIL_T(tail_setup)
-    if (__ballot(ray != kInvalidRef) == 0) {
-      if (src.exhausted && src.pool_next == src.pool_end) break;
-      continue;
-    }
-    while (ray != kInvalidRef) {
-      wave_traverse<false, COUNT, TWO, W6>(S, lds_nodes, ts, &tc);
-      if (ts.cur == kInvalidRef && ts.st.npend == 0) finish();
-      // lanes still in this loop vote: leave for a refill once the wave has emptied below the threshold
-      if (refill && !src.exhausted && (uint32_t)__popcll(__ballot(ray != kInvalidRef)) < refill) break;
-    }
-  }
-  if (COUNT) {
-    const uint32_t nn = wave_sum(tc.nodes), t = wave_sum(tc.tris);
-    if (lane == 0) {
-      atomicAdd(&ctr->nodes_closest, (unsigned long long)nn);
-      atomicAdd(&ctr->tris_closest, (unsigned long long)t);
-    }
-  }
-  PT_TAIL_END(0)
+  trace_rays<W, false, COUNT, 0>(S, seg, seg.table_closest, ctr->chunks_closest[bounce], cursor, spill, ctr, bounce, &ctr->nodes_closest, &ctr->tris_closest,
+                                 begin, finish);
 }
 
-template <bool COUNT, bool TWO, bool W6 = false>
-__global__ void __launch_bounds__(TWO ? kTraceBlock2 : kBlock, TWO ? PT_TWO_BLOCKS_PER_CU : PT_CLOSEST_WAVES)
+template <class W, bool COUNT>
+__global__ void __launch_bounds__(W::kThreads, W::kClosestBlocksPerCu)
 k_trace_closest(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments seg, uint32_t cur, BatchCounters* __restrict__ ctr, uint32_t bounce,
                 uint32_t* __restrict__ spill, int32_t* __restrict__ hitlog, uint32_t log_stride) {
-  trace_closest_body<COUNT, TWO, W6, false>(S, st, hit, seg, cur, ctr, bounce, &ctr->work_closest[bounce], spill, hitlog, log_stride, CameraLists{});
+  trace_closest_body<W, COUNT, false>(S, st, hit, seg, cur, ctr, bounce, &ctr->work_closest[bounce], spill, hitlog, log_stride, CameraLists{});
 }
 
 // ---- camera rays from per-pixel leaf lists (pt_camlist.h; built once per render by camera_lists.hip) --------------------------------------
@@ -500,10 +509,10 @@ k_trace_closest(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments se
 // k_chunk_tables makes of the queue k_camera_primary filled.  Its claims run on a cursor of its own (work_closest[63]: bounces stop at 50):
 // k_camera_primary has used up bounce 0's for its work units
 constexpr uint32_t kUnlistedCursor = 63;
-__global__ void __launch_bounds__(kBlock, PT_CLOSEST_WAVES)
+__global__ void __launch_bounds__(Walk6::kThreads, Walk6::kClosestBlocksPerCu)
 k_trace_closest_unlisted(DeviceScene S, PathState st, vec4* __restrict__ hit, Segments seg, BatchCounters* __restrict__ ctr, uint32_t* __restrict__ spill,
                          CameraLists cl) {
-  trace_closest_body<false, false, true, true>(S, st, hit, seg, 0u, ctr, 0u, &ctr->work_closest[kUnlistedCursor], spill, nullptr, 0u, cl);
+  trace_closest_body<Walk6, false, true>(S, st, hit, seg, 0u, ctr, 0u, &ctr->work_closest[kUnlistedCursor], spill, nullptr, 0u, cl);
 }
 
 // ---- bounce 0 in one kernel: camera rays generated and traced from their pixels' lists -----------------------------------------------------
@@ -912,32 +921,19 @@ k_shade(const DeviceScene* __restrict__ Sp, PathState sin, PathState sout, const
 }
 
 // ---- shadow (any hit) --------------------------------------------------------------------------------------------------
-template <bool COUNT, bool TWO, bool W6 = false>
-__global__ void __launch_bounds__(TWO ? kTraceBlock2 : kBlock, TWO ? PT_TWO_BLOCKS_PER_CU : PT_SHADOW_WAVES)
+template <class W, bool COUNT>
+__global__ void __launch_bounds__(W::kThreads, W::kShadowBlocksPerCu)
 k_trace_shadow(DeviceScene S, ShadowQueue sq, vec4* __restrict__ Lbuf, Segments seg, BatchCounters* __restrict__ ctr, uint32_t bounce,
                uint32_t* __restrict__ spill) {
-  PT_TAIL_BEGIN
-  constexpr uint32_t kTB = TWO ? kTraceBlock2 : kBlock;
-  __shared__ uint32_t lds_stack[(W6 ? kLdsStack6 : kLdsStack) + 1][kTB];
-  __shared__ uint32_t lds_pend[(W6 ? kPendLeaves6 : kPendLeaves) + 1][kTB];
-  __shared__ BvhNode lds_nodes_buf[TWO && kLdsNodes ? kLdsNodes : 1];
-  const BvhNode* lds_nodes = TWO && kLdsNodes ? stage_nodes(S, lds_nodes_buf) : nullptr;
-  const uint32_t lane = wave_lane();
-  ChunkClaims src;
-  src.init(seg.table_shadow, ctr->chunks_shadow[bounce], &ctr->work_shadow[bounce], seg, lane);
-  TraversalStack stack;
-  stack.lds = &lds_stack[0][threadIdx.x];
-  stack.pend = &lds_pend[0][threadIdx.x];
-  stack.lds_stride = kTB;
-  stack.spill = spill + ((size_t)blockIdx.x * kTB + threadIdx.x);
-  stack.spill_stride = gridDim.x * kTB;
-  TraversalCount tc;
-
-  // (written as an explicit init / step loop: with the whole traversal behind one call the compiler produced a kernel
-  //  1.5x slower on secondary rays)
-  TravState ts;
-  uint32_t ray = kInvalidRef, pid = 0;
-  auto finish = [&]() {
+  uint32_t pid = 0;
+  auto begin = [&](uint32_t& ray, TravState& ts, const TraversalStack& stack, TraversalCount* tc) {
+    const vec4 o4 = sq.o[ray];
+    const vec4 d4 = sq.d[ray];
+    pid = f2u(d4.w);
+    const float ir = S.has_alpha ? sq.contrib[ray].w : 0.0f;  // kernel.metal:625
+    return trav_init(S, ts, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), 1e-3f, o4.w, ir, stack, true, tc);
+  };
+  auto finish = [&](uint32_t& ray, TravState& ts) {
     if (ts.best.tri == kInvalidRef) {  // unoccluded: L += attenuation * Ld (kernel.metal:631-637)
       const vec4 c = sq.contrib[ray];
       vec4 L = Lbuf[pid];
@@ -946,38 +942,8 @@ k_trace_shadow(DeviceScene S, ShadowQueue sq, vec4* __restrict__ Lbuf, Segments 
     }
     ray = kInvalidRef;
   };
-  const uint32_t refill = seg.refill_threshold;
-  for (;;) {
-    PT_TAIL_MARK
-    const uint32_t fresh = src.take(ray == kInvalidRef);
-    PT_TAIL_T(tail_take)
-    if (fresh != kInvalidRef) {
-      ray = fresh;
-      const vec4 o4 = sq.o[ray];
-      const vec4 d4 = sq.d[ray];
-      pid = f2u(d4.w);
-      const float ir = S.has_alpha ? sq.contrib[ray].w : 0.0f;  // kernel.metal:625
-      if (trav_init(S, ts, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), 1e-3f, o4.w, ir, stack, true, COUNT ? &tc : nullptr)) finish();
-    }
-    PT_TAIL_T(tail_setup)
-    if (__ballot(ray != kInvalidRef) == 0) {
-      if (src.exhausted && src.pool_next == src.pool_end) break;
-      continue;
-    }
-    while (ray != kInvalidRef) {
-      wave_traverse<true, COUNT, TWO, W6>(S, lds_nodes, ts, &tc);
-      if (ts.cur == kInvalidRef && ts.st.npend == 0) finish();
-      if (refill && !src.exhausted && (uint32_t)__popcll(__ballot(ray != kInvalidRef)) < refill) break;
-    }
-  }
-  if (COUNT) {
-    const uint32_t nn = wave_sum(tc.nodes), t = wave_sum(tc.tris);
-    if (lane == 0) {
-      atomicAdd(&ctr->nodes_shadow, (unsigned long long)nn);
-      atomicAdd(&ctr->tris_shadow, (unsigned long long)t);
-    }
-  }
-  PT_TAIL_END(2)
+  trace_rays<W, true, COUNT, 2>(S, seg, seg.table_shadow, ctr->chunks_shadow[bounce], &ctr->work_shadow[bounce], spill, ctr, bounce, &ctr->nodes_shadow,
+                                &ctr->tris_shadow, begin, finish);
 }
 
 // ---- accumulate (kernel.metal:672-684): running mean, one sample at a time, in sample order --------------------------
@@ -1226,29 +1192,21 @@ void launch_chunk_tables(hipStream_t s, Segments seg, uint32_t cur, BatchCounter
                          uint32_t bounce_shadow, bool do_shadow) {
   hipLaunchKernelGGL(k_chunk_tables, dim3(kTableBlocks, 3), dim3(1024), 0, s, seg, cur, ctr, bounce_closest, bounce_shadow, do_shadow ? 1u : 0u);
 }
-// One-BVH scenes: `grid` blocks of 256 threads (7 per CU).  Two-level scenes (S.two_level): one 1024-thread block per CU.
-uint32_t trace_block_threads(bool two_level) { return two_level ? kTraceBlock2 : (uint32_t)kBlock; }
-uint32_t trace_blocks_per_cu_two_level() { return PT_TWO_BLOCKS_PER_CU; }
+// The structure S holds and `count` -> (its description, COUNT) as types: launch(Walk{}, std::bool_constant<COUNT>{}) launches that instantiation.
+template <class F> static void launch_walk(const DeviceScene& S, bool count, F launch) {
+  auto counted = [&](auto walk) { if (count) launch(walk, std::true_type{}); else launch(walk, std::false_type{}); };
+  if (S.two_level) counted(WalkTwoLevel{}); else if (S.wide6) counted(Walk6{}); else counted(Walk4{});
+}
+template <class W> static TraceWalk trace_walk_of() {
+  return {(uint32_t)W::kThreads, (uint32_t)W::kClosestBlocksPerCu, (uint32_t)W::kShadowBlocksPerCu, !W::kTwoLevel, W::kPushesPerLevel, W::kExitEntries};
+}
+TraceWalk trace_walk(bool two_level, bool wide6) { return two_level ? trace_walk_of<WalkTwoLevel>() : wide6 ? trace_walk_of<Walk6>() : trace_walk_of<Walk4>(); }
 void launch_trace_closest(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState st, vec4* hit, Segments seg, uint32_t cur,
                           BatchCounters* ctr, uint32_t bounce, uint32_t* spill, int32_t* hitlog, uint32_t log_stride, bool count) {
-  if (S.two_level) {
-    if (count)
-      hipLaunchKernelGGL((k_trace_closest<true, true>), dim3(grid), dim3(kTraceBlock2), 0, s, S, st, hit, seg, cur, ctr, bounce, spill, hitlog, log_stride);
-    else
-      hipLaunchKernelGGL((k_trace_closest<false, true>), dim3(grid), dim3(kTraceBlock2), 0, s, S, st, hit, seg, cur, ctr, bounce, spill, hitlog, log_stride);
-    return;
-  }
-  if (S.wide6) {
-    if (count)
-      hipLaunchKernelGGL((k_trace_closest<true, false, true>), dim3(grid), dim3(kBlock), 0, s, S, st, hit, seg, cur, ctr, bounce, spill, hitlog, log_stride);
-    else
-      hipLaunchKernelGGL((k_trace_closest<false, false, true>), dim3(grid), dim3(kBlock), 0, s, S, st, hit, seg, cur, ctr, bounce, spill, hitlog, log_stride);
-    return;
-  }
-  if (count)
-    hipLaunchKernelGGL((k_trace_closest<true, false>), dim3(grid), dim3(kBlock), 0, s, S, st, hit, seg, cur, ctr, bounce, spill, hitlog, log_stride);
-  else
-    hipLaunchKernelGGL((k_trace_closest<false, false>), dim3(grid), dim3(kBlock), 0, s, S, st, hit, seg, cur, ctr, bounce, spill, hitlog, log_stride);
+  launch_walk(S, count, [&](auto walk, auto counted) {
+    using W = decltype(walk);
+    hipLaunchKernelGGL((k_trace_closest<W, decltype(counted)::value>), dim3(grid), dim3(W::kThreads), 0, s, S, st, hit, seg, cur, ctr, bounce, spill, hitlog, log_stride);
+  });
 }
 void launch_camera_primary(hipStream_t s, uint32_t grid, uint32_t grid_unlisted, const DeviceScene& S, PathState st, vec4* Lbuf, vec4* hit, Segments seg,
                            BatchCounters* ctr, uint32_t first_sample, uint32_t nsamples, uint32_t* spill, const CameraLists& cl, bool any_unlisted) {
@@ -1273,18 +1231,10 @@ void launch_shade(hipStream_t s, uint32_t grid, const DeviceScene* S, PathState 
 }
 void launch_trace_shadow(hipStream_t s, uint32_t grid, const DeviceScene& S, ShadowQueue sq, vec4* Lbuf, Segments seg,
                          BatchCounters* ctr, uint32_t bounce, uint32_t* spill, bool count) {
-  if (S.two_level) {
-    if (count) hipLaunchKernelGGL((k_trace_shadow<true, true>), dim3(grid), dim3(kTraceBlock2), 0, s, S, sq, Lbuf, seg, ctr, bounce, spill);
-    else hipLaunchKernelGGL((k_trace_shadow<false, true>), dim3(grid), dim3(kTraceBlock2), 0, s, S, sq, Lbuf, seg, ctr, bounce, spill);
-    return;
-  }
-  if (S.wide6) {
-    if (count) hipLaunchKernelGGL((k_trace_shadow<true, false, true>), dim3(grid), dim3(kBlock), 0, s, S, sq, Lbuf, seg, ctr, bounce, spill);
-    else hipLaunchKernelGGL((k_trace_shadow<false, false, true>), dim3(grid), dim3(kBlock), 0, s, S, sq, Lbuf, seg, ctr, bounce, spill);
-    return;
-  }
-  if (count) hipLaunchKernelGGL((k_trace_shadow<true, false>), dim3(grid), dim3(kBlock), 0, s, S, sq, Lbuf, seg, ctr, bounce, spill);
-  else hipLaunchKernelGGL((k_trace_shadow<false, false>), dim3(grid), dim3(kBlock), 0, s, S, sq, Lbuf, seg, ctr, bounce, spill);
+  launch_walk(S, count, [&](auto walk, auto counted) {
+    using W = decltype(walk);
+    hipLaunchKernelGGL((k_trace_shadow<W, decltype(counted)::value>), dim3(grid), dim3(W::kThreads), 0, s, S, sq, Lbuf, seg, ctr, bounce, spill);
+  });
 }
 void launch_accumulate(hipStream_t s, vec4* acc, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,
                        uint32_t nonfinite_policy, BatchCounters* ctr, const TileSet* tiles, vec2* mom, uint32_t* tile_n) {

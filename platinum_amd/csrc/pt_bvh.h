@@ -99,7 +99,7 @@ PT_HD float slab_entry(const float lo[3], const float hi[3], vec3 o, vec3 inv, f
   t0 = (lo[2] - o.z) * inv.z; t1 = (hi[2] - o.z) * inv.z;
   tn = fmaxf(tn, fminf(t0, t1));
   tf = fminf(tf, fmaxf(t0, t1));
-  return (tn <= tf * 1.0000005f + 1e-30f) ? tn : -1.0f;
+  return (tn <= tf * kSlabSlack + 1e-30f) ? tn : -1.0f;
 }
 
 // Per-lane traversal stack: the first kLdsStack entries live in LDS ([depth][lane], bank = lane; row kLdsStack is a
@@ -129,7 +129,6 @@ PT_HD float slab_entry(const float lo[3], const float hi[3], vec3 o, vec3 inv, f
 constexpr int kLdsStack = PT_LDS_STACK;
 constexpr int kSpillStack = 96 - PT_LDS_STACK;  // total 96 entries: up to 3 pushes per level of a 4-wide tree that is <= 48 levels deep
                                  // (binary LBVH depth <= 95 over 63-bit codes + index tie-break, halved by the collapse)
-
 constexpr int kPendLeaves = PT_PEND_LEAVES;   // per-lane queue of leaf candidates awaiting their triangle test (LDS, [slot][lane])
 // The 6-wide kernels split the same 22 rows differently: a node queues ONE entry for all its leaf children (so the queue can be short)
 // and pushes up to five children (so the stack runs deeper).  Measured on C3 (closest-hit ms per 64 spp): 13 + 7 rows 59.4, 15 + 5 59.0,
@@ -143,6 +142,49 @@ constexpr int kPendLeaves = PT_PEND_LEAVES;   // per-lane queue of leaf candidat
 constexpr int kLdsStack6 = PT_LDS_STACK6, kPendLeaves6 = PT_PEND_LEAVES6;
 static_assert(kLdsStack6 + kPendLeaves6 == kLdsStack + kPendLeaves, "the 6-wide kernels use the LDS budget of the 4-wide ones");
 constexpr int kStackTotal = kLdsStack + kSpillStack;  // 96 entries, wherever the LDS part ends
+// The two-level kernels: ONE 1024-thread block per CU (4 waves per SIMD) sharing the staged node array: 64 KB of nodes in LDS beside the
+// 88 KB of stacks and leaf queues of 1024 lanes (152 of 160 KB).
+#ifndef PT_TWO_BLOCK
+#define PT_TWO_BLOCK 1024
+#define PT_TWO_BLOCKS_PER_CU 1
+#define PT_TWO_LDS_NODES 1024
+#endif
+constexpr int kBlock = 256;  // 4 waves; traversal kernels keep a 16 KiB LDS stack slab per block
+struct TravState; struct TraversalCount;
+
+// ---- the structures a trace kernel walks: one description each -------------------------------------------------------------------
+// Everything that depends on WHICH structure is walked is a member of its description: the trace kernels, wave_traverse, the stack
+// and trav_step take one as `W`; the launchers and the renderer's sizing read the same members (kernels.h trace_walk).
+//   kThreads / k*BlocksPerCu  block size and resident blocks per CU (the kernels' launch bounds, the persistent grids)
+//   kStackRows / kPendRows    rows of the per-lane node stack / leaf queue in LDS (each array has one scratch row more)
+//   kRoom                     leaf-queue entries a node step may add: one per child (4-wide), one per node (6-wide: a range)
+//   kLdsNodes                 nodes staged in LDS when the tree has no more (0: always read from HBM)
+//   kPushesPerLevel / kExitEntries   a tree of L levels needs L * kPushesPerLevel + kExitEntries <= kStackTotal stack entries
+// and node / leaf: one node step, one triangle test from the leaf queue.
+struct Walk4 {
+  static constexpr bool kTwoLevel = false;
+  static constexpr int kThreads = kBlock, kClosestBlocksPerCu = PT_CLOSEST_WAVES, kShadowBlocksPerCu = PT_SHADOW_WAVES;
+  static constexpr int kStackRows = kLdsStack, kPendRows = kPendLeaves, kRoom = 4;
+  static constexpr uint32_t kLdsNodes = 0, kPushesPerLevel = 3, kExitEntries = 0;
+  template <bool COUNT> static PT_HD void node(const BvhNode* __restrict__ nodes, TravState& ts, TraversalCount* cnt);
+  template <bool ANY, bool COUNT> static PT_HD bool leaf(const DeviceScene& S, TravState& ts, TraversalCount* cnt);
+};
+struct Walk6 {
+  static constexpr bool kTwoLevel = false;
+  static constexpr int kThreads = kBlock, kClosestBlocksPerCu = PT_CLOSEST_WAVES, kShadowBlocksPerCu = PT_SHADOW_WAVES;
+  static constexpr int kStackRows = kLdsStack6, kPendRows = kPendLeaves6, kRoom = 1;
+  static constexpr uint32_t kLdsNodes = 0, kPushesPerLevel = 5, kExitEntries = 0;
+  template <bool COUNT> static PT_HD void node(const BvhNode* __restrict__ nodes, TravState& ts, TraversalCount* cnt);
+  template <bool ANY, bool COUNT> static PT_HD bool leaf(const DeviceScene& S, TravState& ts, TraversalCount* cnt);
+};
+struct WalkTwoLevel {   // 4-wide nodes: a TLAS over instances, one object-space BLAS per mesh; an exit marker under every instance entered
+  static constexpr bool kTwoLevel = true;
+  static constexpr int kThreads = PT_TWO_BLOCK, kClosestBlocksPerCu = PT_TWO_BLOCKS_PER_CU, kShadowBlocksPerCu = PT_TWO_BLOCKS_PER_CU;
+  static constexpr int kStackRows = kLdsStack, kPendRows = kPendLeaves, kRoom = 4;
+  static constexpr uint32_t kLdsNodes = PT_TWO_LDS_NODES, kPushesPerLevel = 3, kExitEntries = 1;
+  template <bool COUNT> static PT_HD void node(const BvhNode* __restrict__ nodes, TravState& ts, TraversalCount* cnt);
+  template <bool ANY, bool COUNT> static PT_HD bool leaf(const DeviceScene& S, TravState& ts, TraversalCount* cnt);
+};
 
 struct TraversalStack {
   uint32_t* lds;     // &lds_stack[0][lane_in_block]
@@ -154,16 +196,16 @@ struct TraversalStack {
   int npend = 0;
   PT_HD void push_leaf(uint32_t ref) { pend[npend * lds_stride] = ref; npend++; }
   PT_HD uint32_t pop_leaf() { npend--; return pend[npend * lds_stride]; }
-  // (ROWS = stack rows in LDS: kLdsStack, or kLdsStack6 in the 6-wide kernels — a compile-time constant: as a member it cost 40 bytes of scratch)
-  template <int ROWS = kLdsStack> PT_HD void push(uint32_t v) {
-    if (sp < ROWS) lds[sp * lds_stride] = v;
-    else if (sp < kStackTotal) spill[(size_t)(sp - ROWS) * spill_stride] = v;
+  // (W::kStackRows = stack rows in LDS — a compile-time constant: as a member it cost 40 bytes of scratch)
+  template <class W> PT_HD void push(uint32_t v) {
+    if (sp < W::kStackRows) lds[sp * lds_stride] = v;
+    else if (sp < kStackTotal) spill[(size_t)(sp - W::kStackRows) * spill_stride] = v;
     sp++;
   }
-  template <int ROWS = kLdsStack> PT_HD uint32_t pop() {
+  template <class W> PT_HD uint32_t pop() {
     sp--;
-    if (sp < ROWS) return lds[sp * lds_stride];
-    if (sp < kStackTotal) return spill[(size_t)(sp - ROWS) * spill_stride];
+    if (sp < W::kStackRows) return lds[sp * lds_stride];
+    if (sp < kStackTotal) return spill[(size_t)(sp - W::kStackRows) * spill_stride];
     return kInvalidRef;  // overflowed entries were dropped; never reached with depth <= 96
   }
 };
@@ -374,8 +416,9 @@ PT_HD Box3 inflate_box(const Box3& b) {
 // they go to the lane's leaf queue, and the caller runs the triangle code when enough lanes of the wave have one queued
 // (measured before this split: the in-place triangle loop ran at 11 % lane utilisation on C2, 8 % on C3).
 // On return ts.cur is the next node, or kInvalidRef when the node stack is exhausted.
-template <bool COUNT, bool TWO = false>
+template <bool COUNT, class W = Walk4>
 PT_HD void trav_node(const BvhNode* __restrict__ nodes, TravState& ts, TraversalCount* cnt) {
+  constexpr bool TWO = W::kTwoLevel;
   const BvhNode n = nodes[ts.cur];
   if (COUNT) cnt->nodes++;
   const vec3 ro = TWO ? ts.co : ts.o, ri = TWO ? ts.cinv : ts.inv;
@@ -403,8 +446,8 @@ PT_HD void trav_node(const BvhNode* __restrict__ nodes, TravState& ts, Traversal
     const bool hit = n.ref[k] != kInvalidRef && tn <= __builtin_fmaf(tf, kSlabSlack, 1e-30f);
     const bool leaf = hit && (n.ref[k] & kLeafBit);
     dist[k] = hit && !leaf ? tn : kInf;  // leaves never go on the node stack (TLAS leaves — kInstBit — do: they are entered like nodes)
-    // queue the leaf (branch-free: a non-leaf writes to the scratch row kPendLeaves); two-level: as the flattened triangle
-    ts.st.pend[(leaf ? ts.st.npend : kPendLeaves) * ts.st.lds_stride] = TWO ? n.ref[k] + ts.tri_base : n.ref[k];
+    // queue the leaf (branch-free: a non-leaf writes to the scratch row W::kPendRows); two-level: as the flattened triangle
+    ts.st.pend[(leaf ? ts.st.npend : W::kPendRows) * ts.st.lds_stride] = TWO ? n.ref[k] + ts.tri_base : n.ref[k];
     ts.st.npend += leaf ? 1 : 0;
   }
   // internal children: nearest becomes `cur`, the others are pushed far-to-near
@@ -418,12 +461,12 @@ PT_HD void trav_node(const BvhNode* __restrict__ nodes, TravState& ts, Traversal
   if (d0 < kInf) {
     // push far-to-near (a branch-free variant that writes all three entries and redirects misses to the scratch row was
     // measured: neutral on C2, 6 % slower on C3 where deep stacks take the spill path more often)
-    if (d3 < kInf) ts.st.push(r3);
-    if (d2 < kInf) ts.st.push(r2);
-    if (d1 < kInf) ts.st.push(r1);
+    if (d3 < kInf) ts.st.push<W>(r3);
+    if (d2 < kInf) ts.st.push<W>(r2);
+    if (d1 < kInf) ts.st.push<W>(r1);
     ts.cur = r0;
   } else {
-    ts.cur = ts.st.sp == 0 ? kInvalidRef : ts.st.pop();
+    ts.cur = ts.st.sp == 0 ? kInvalidRef : ts.st.pop<W>();
   }
 }
 
@@ -528,7 +571,7 @@ PT_HD void trav_node6(const BvhNode* __restrict__ nodes, TravState& ts, Traversa
 #endif
   // leaf children that were hit: one queue entry (branch-free: no entry -> the scratch row)
   const uint32_t leaf_mask = hits >> n_int;
-  ts.st.pend[(leaf_mask ? ts.st.npend : kPendLeaves6) * ts.st.lds_stride] = n.base_leaf << 6 | leaf_mask;
+  ts.st.pend[(leaf_mask ? ts.st.npend : Walk6::kPendRows) * ts.st.lds_stride] = n.base_leaf << 6 | leaf_mask;
   ts.st.npend += leaf_mask ? 1 : 0;
   // internal children: the nearest is visited next, the others go on the stack
   uint32_t others = hits & ((1u << n_int) - 1u);
@@ -537,11 +580,11 @@ PT_HD void trav_node6(const BvhNode* __restrict__ nodes, TravState& ts, Traversa
     while (others) {
       const uint32_t k = (uint32_t)__builtin_ctz(others);
       others &= others - 1u;
-      ts.st.push<kLdsStack6>(n.base_node + k);
+      ts.st.push<Walk6>(n.base_node + k);
     }
     ts.cur = n.base_node + best_k;
   } else {
-    ts.cur = ts.st.sp == 0 ? kInvalidRef : ts.st.pop<kLdsStack6>();
+    ts.cur = ts.st.sp == 0 ? kInvalidRef : ts.st.pop<Walk6>();
   }
 }
 
@@ -573,7 +616,7 @@ PT_HD void trav_leave(TravState& ts) {
     ts.cnegx = ts.negx; ts.cnegy = ts.negy; ts.cnegz = ts.negz;
     ts.sx = ts.sy = ts.sz = 0.0f;
     ts.tri_base = 0u;
-    ts.cur = ts.st.sp == 0 ? kInvalidRef : ts.st.pop();
+    ts.cur = ts.st.sp == 0 ? kInvalidRef : ts.st.pop<WalkTwoLevel>();
   }
 }
 PT_HD void trav_resolve(const DeviceScene& S, TravState& ts) {
@@ -583,17 +626,17 @@ PT_HD void trav_resolve(const DeviceScene& S, TravState& ts) {
       ts.cnegx = ts.negx; ts.cnegy = ts.negy; ts.cnegz = ts.negz;
       ts.sx = ts.sy = ts.sz = 0.0f;
       ts.tri_base = 0u;
-      ts.cur = ts.st.sp == 0 ? kInvalidRef : ts.st.pop();
+      ts.cur = ts.st.sp == 0 ? kInvalidRef : ts.st.pop<WalkTwoLevel>();
       continue;
     }
     if (ts.cur == kInvalidRef || !(ts.cur & kInstBit)) return;
-    if (ts.st.npend > kPendLeaves - 4) return;  // (no room in the leaf queue: the caller runs a triangle round first)
+    if (ts.st.npend > WalkTwoLevel::kPendRows - WalkTwoLevel::kRoom) return;  // (no room in the leaf queue: the caller runs a triangle round first)
     const InstanceTrav it = ldg(&S.inst_trav[ts.cur & ~kInstBit]);
     const MeshTrav mt = ldg(&S.mesh_trav[it.mesh]);
     if (mt.root_ref == kInvalidRef || (mt.root_ref & kLeafBit)) {
       // a mesh without triangles, or with one: that one is the candidate (no nodes to walk, the ray stays where it is)
       if (mt.root_ref != kInvalidRef) ts.st.push_leaf(kLeafBit | (it.tri_base + (mt.root_ref & ~kLeafBit)));
-      ts.cur = ts.st.sp == 0 ? kInvalidRef : ts.st.pop();
+      ts.cur = ts.st.sp == 0 ? kInvalidRef : ts.st.pop<WalkTwoLevel>();
       continue;
     }
     const vec3 p = ts.o - v3(it.c[0], it.c[1], it.c[2]);
@@ -618,7 +661,7 @@ PT_HD void trav_resolve(const DeviceScene& S, TravState& ts) {
     if (!(e <= 1e30f)) e = 1e30f;
     ts.sx = e * fabsf(ts.cinv.x); ts.sy = e * fabsf(ts.cinv.y); ts.sz = e * fabsf(ts.cinv.z);
     ts.tri_base = it.tri_base;
-    ts.st.push(kExitMarker);
+    ts.st.push<WalkTwoLevel>(kExitMarker);
     ts.cur = mt.root_ref;
   }
 }
@@ -631,19 +674,20 @@ PT_HD bool trav_pending_leaf(const DeviceScene& S, TravState& ts, TraversalCount
   return finished;
 }
 
+template <bool COUNT> PT_HD void Walk4::node(const BvhNode* __restrict__ nodes, TravState& ts, TraversalCount* cnt) { trav_node<COUNT, Walk4>(nodes, ts, cnt); }
+template <bool COUNT> PT_HD void Walk6::node(const BvhNode* __restrict__ nodes, TravState& ts, TraversalCount* cnt) { trav_node6<COUNT>(nodes, ts, cnt); }
+template <bool COUNT> PT_HD void WalkTwoLevel::node(const BvhNode* __restrict__ nodes, TravState& ts, TraversalCount* cnt) { trav_node<COUNT, WalkTwoLevel>(nodes, ts, cnt); }
+template <bool ANY, bool COUNT> PT_HD bool Walk4::leaf(const DeviceScene& S, TravState& ts, TraversalCount* cnt) { return trav_pending_leaf<ANY, COUNT>(S, ts, cnt); }
+template <bool ANY, bool COUNT> PT_HD bool Walk6::leaf(const DeviceScene& S, TravState& ts, TraversalCount* cnt) { return trav_pending_leaf6<ANY, COUNT>(S, ts, cnt); }
+template <bool ANY, bool COUNT> PT_HD bool WalkTwoLevel::leaf(const DeviceScene& S, TravState& ts, TraversalCount* cnt) { return trav_pending_leaf<ANY, COUNT>(S, ts, cnt); }
+
 // One node, then its leaves at once (the scalar formulation: tests/emu, and the reference for the wave-cooperative
-// scheduling in kernels.hip — the answer does not depend on the order in which candidates are tested).
-template <bool ANY, bool COUNT>
+// scheduling in kernels.hip — the answer does not depend on the order in which candidates are tested).  One-BVH structures only.
+template <class W, bool ANY, bool COUNT>
 PT_HD bool trav_step(const DeviceScene& S, TravState& ts, TraversalCount* cnt) {
-  if (S.wide6) {
-    trav_node6<COUNT>(S.nodes, ts, cnt);
-    while (ts.st.npend > 0)
-      if (trav_pending_leaf6<ANY, COUNT>(S, ts, cnt)) return true;
-    return ts.cur == kInvalidRef;
-  }
-  trav_node<COUNT>(S.nodes, ts, cnt);
+  W::template node<COUNT>(S.nodes, ts, cnt);
   while (ts.st.npend > 0)
-    if (trav_pending_leaf<ANY, COUNT>(S, ts, cnt)) return true;
+    if (W::template leaf<ANY, COUNT>(S, ts, cnt)) return true;
   return ts.cur == kInvalidRef;
 }
 
@@ -652,7 +696,7 @@ PT_HD RayHit traverse(const DeviceScene& S, vec3 o, vec3 d, float tmin, float tm
                       TraversalCount* cnt) {
   TravState ts;
   if (trav_init(S, ts, o, d, tmin, tmax, payload, st, ANY, COUNT ? cnt : nullptr)) return ts.best;
-  while (!trav_step<ANY, COUNT>(S, ts, cnt)) {}
+  while (!(S.wide6 ? trav_step<Walk6, ANY, COUNT>(S, ts, cnt) : trav_step<Walk4, ANY, COUNT>(S, ts, cnt))) {}
   return ts.best;
 }
 

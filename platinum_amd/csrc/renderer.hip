@@ -330,10 +330,10 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   if (const char* e = getenv("PTAMD_SEG_BANDS")) r->seg_bands = (uint32_t)std::max(1, std::min(64, atoi(e)));
   if (const char* e = getenv("PTAMD_TWO_LEVEL")) r->two_level_override = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("PTAMD_BLOCKS_PER_CU")) r->blocks_per_cu = (uint32_t)std::max(1, std::min(8, atoi(e)));
-  if (const char* e = getenv("PTAMD_CLOSEST_BLOCKS_PER_CU")) r->closest_blocks_per_cu = (uint32_t)std::max(1, std::min(8, atoi(e)));
+  if (const char* e = getenv("PTAMD_CLOSEST_BLOCKS_PER_CU")) r->closest_blocks_asked = (uint32_t)std::max(1, std::min(8, atoi(e)));
   if (const char* e = getenv("PTAMD_NO_CAMERA_LISTS")) r->no_camera_lists = atoi(e) != 0;
   if (const char* e = getenv("PTAMD_TEST_CAMLIST_CAP")) r->cam_cap_override = (uint32_t)std::max(1, std::min((int)kCamListMaxCapacity, atoi(e)));
-  if (const char* e = getenv("PTAMD_SHADOW_BLOCKS_PER_CU")) r->shadow_blocks_per_cu = (uint32_t)std::max(1, std::min(8, atoi(e)));
+  if (const char* e = getenv("PTAMD_SHADOW_BLOCKS_PER_CU")) r->shadow_blocks_asked = (uint32_t)std::max(1, std::min(8, atoi(e)));
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, r->device) == hipSuccess) r->num_cu = prop.multiProcessorCount;
   int rc = PT_OK;
@@ -519,8 +519,9 @@ int build_accel(pt_renderer* r, const pt_render_params* p, HostScene* hs) {
   float ms = 0;
   PT_HIP(watch.stop(&ms));
   r->bvh_ms = ms;
-  // traversal stack: <= 3 pushes per 4-wide level; 4-wide depth = ceil(binary depth / 2)
-  if (r->bvh.depth4 * (r->bvh.wide6 ? 5u : 3u) + (r->two_level ? 1 : 0) > (uint32_t)(kLdsStack + kSpillStack))
+  // traversal stack: <= 3 pushes per 4-wide level (5 per 6-wide one); 4-wide depth = ceil(binary depth / 2)
+  r->walk = trace_walk(r->two_level, r->bvh.wide6);
+  if (r->bvh.depth4 * r->walk.pushes_per_level + r->walk.exit_entries > (uint32_t)kStackTotal)
     return fail(PT_ERR_UNSUPPORTED, "BVH too deep for the traversal stack (degenerate geometry: thousands of coincident triangles?)");
   S.nodes = r->bvh.nodes;
   S.tris = r->bvh.tris;
@@ -622,8 +623,8 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
   r->grid = (uint32_t)r->num_cu * r->blocks_per_cu;                 // raygen, hit records: 256-thread blocks
   r->shade_grid = (uint32_t)r->num_cu * shade_blocks_per_cu();     // as many blocks as k_shade's registers / LDS keep resident
   r->primary_grid = (uint32_t)r->num_cu * primary_blocks_per_cu();
-  r->closest_grid = (uint32_t)r->num_cu * (r->two_level ? trace_blocks_per_cu_two_level() : r->closest_blocks_per_cu);
-  r->shadow_grid = (uint32_t)r->num_cu * (r->two_level ? trace_blocks_per_cu_two_level() : r->shadow_blocks_per_cu);
+  r->closest_grid = (uint32_t)r->num_cu * (r->walk.blocks_tunable && r->closest_blocks_asked ? r->closest_blocks_asked : r->walk.closest_blocks_per_cu);
+  r->shadow_grid = (uint32_t)r->num_cu * (r->walk.blocks_tunable && r->shadow_blocks_asked ? r->shadow_blocks_asked : r->walk.shadow_blocks_per_cu);
   r->nstats = std::max(std::max(r->grid, r->primary_grid) * (kBlock / 64), r->shade_grid * (shade_block_threads() / 64));
   for (int k = 0; k < 2; k++) {
     PT_HIP(r->st_rayO[k].alloc(r->capacity)); PT_HIP(r->st_rayD[k].alloc(r->capacity));
@@ -641,7 +642,7 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
   // (max_bounces + 1 rows: the table pass after the LAST bounce's k_shade still sorts for a bounce nobody runs, and reads that row)
   PT_HIP(r->shade_cost.alloc((size_t)r->nseg * (r->S.max_bounces + 1u)));
   PT_HIP(hipMemsetAsync(r->shade_cost.p, 0, sizeof(uint32_t) * r->shade_cost.n, r->stream));   // no batch of this render has been shaded yet
-  PT_HIP(r->spill.alloc((size_t)std::max(r->closest_grid, r->shadow_grid) * trace_block_threads(r->two_level) * kSpillStack));  // per-thread HBM stack slab behind the LDS stack
+  PT_HIP(r->spill.alloc((size_t)std::max(r->closest_grid, r->shadow_grid) * r->walk.block_threads * kSpillStack));  // per-thread HBM stack slab behind the LDS stack
   PT_HIP(hipMemsetAsync(r->wave_stats.p, 0, sizeof(WaveStats) * r->nstats, r->stream));
   if (p->external_accumulator) {
     r->acc = (vec4*)p->external_accumulator;

@@ -10,7 +10,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCRIPT = os.path.join(ROOT, "tools", "kernel_resources.sh")
-# the name is whatever the script prints before " VGPRs": a template instantiation ("void k_trace_closest<false, false, true>") has blanks in it
+# the name is whatever the script prints before " VGPRs": a template instantiation ("void k_trace_closest<Walk6, false>") has blanks in it
 LINE = re.compile(r"(.+?) VGPRs (\d+) scratch (\d+) spill (\d+) occ (\d+) LDS (\d+)$")
 Row = collections.namedtuple("Row", "line vgprs scratch spill occ lds")
 _lines = None

@@ -22,8 +22,8 @@ K = 1024
 FULL_OCCUPANCY = Budget(vgprs=64, scratch=0, spill=0, occ=8, lds=0)   # 256 threads, no LDS: 64 VGPRs is what 8 waves per SIMD leave a lane
 TABLE = {
     # ---- the path tracer's hot kernels (test_hot_kernels_...) ----
-    "void k_trace_closest<false, false, true>": Budget(vgprs=80, scratch=0, occ=6, lds=23 * K),   # 6 blocks of 256 threads per CU
-    "void k_trace_shadow<false, false, true>": Budget(vgprs=72, scratch=0, occ=7, lds=23 * K),    # 7 blocks per CU
+    "void k_trace_closest<Walk6, false>": Budget(vgprs=80, scratch=0, occ=6, lds=23 * K),   # 6 blocks of 256 threads per CU
+    "void k_trace_shadow<Walk6, false>": Budget(vgprs=72, scratch=0, occ=7, lds=23 * K),    # 7 blocks per CU
     "k_shade": Budget(vgprs=128, scratch=0, occ=4, lds=32 * K),                                     # 4 waves per SIMD
     # (the line: what a render without adaptive sampling, a region or camera lists launches is left as it was; the adaptive, region and
     # fused-camera tests)
@@ -130,7 +130,7 @@ def unchanged(*names):
 
 
 def test_hot_kernels_stay_inside_their_register_scratch_and_lds_budgets():
-    inside_budget("void k_trace_closest<false, false, true>", "void k_trace_shadow<false, false, true>", "k_shade", "k_raygen", "k_accumulate")
+    inside_budget("void k_trace_closest<Walk6, false>", "void k_trace_shadow<Walk6, false>", "k_shade", "k_raygen", "k_accumulate")
 
 
 def test_adaptive_kernels_stay_inside_the_budgets_of_the_kernels_they_mirror():
