@@ -806,6 +806,45 @@ typedef struct pt_view_inputs {   /* any pointer the view does not read may be N
 int pt_debug_view(pt_renderer* r, const pt_view_inputs* in, uint32_t width, uint32_t height, const uint32_t* rect,
                   const pt_view_options* options, uint8_t* rgba8_out, pt_view_stats* stats_out);
 
+/* ---- camera projections (NEW, an additive extension of ABI 5: new entry points and one new struct, no existing struct changed) ----
+ * How the camera rays of a render are made.  The projection is read at pt_start_render; under the default, PT_PROJ_PERSPECTIVE, every
+ * output and every launch is what it is without this block, bit for bit.  pt_camera, pt_camera_data and pt_constants do not change, and
+ * pt_get_constants returns under every projection what it returns under PERSPECTIVE.
+ * With u, v, w the normalised columns 0..2 of pt_camera.world (its scale removed, as for the perspective camera; the camera looks down -w),
+ * pos its column 3, and (fx, fy) = (px + jitter.x, py + jitter.y) the sample position in pixels (Halton dimensions 0-1, formed in fp32):
+ *   PT_PROJ_ORTHOGRAPHIC  the view volume is ortho_height high and ortho_height * W / H wide, centred on pos: o = pos + (fx / W - 1/2) * width * u
+ *                         - (fy / H - 1/2) * ortho_height * v, d = -w.  No near or far plane: the ray starts on the camera's plane.
+ *   PT_PROJ_EQUIRECT      phi = (fx / W - 1/2) * fov_x, theta = pi/2 + (fy / H - 1/2) * fov_y,
+ *                         d = sin(theta) sin(phi) u + cos(theta) v - sin(theta) cos(phi) w, o = pos.  With the defaults and a camera with
+ *                         u = +z, v = +y, w = -x (looking along +x, y up) the image has the layout of an environment map, pixel for texel.
+ *   PT_PROJ_FISHEYE       equidistant: half = min(W, H) / 2, x = (fx - W/2) / half, y = (H/2 - fy) / half, r = |(x, y)|,
+ *                         theta = min(r * fisheye_fov / 2, pi), d = sin(theta) (x/r) u + sin(theta) (y/r) v - cos(theta) w (r = 0: d = -w),
+ *                         o = pos.  Every pixel gets a ray: the corners continue the mapping beyond the image circle.
+ * The image centre looks down -w, x grows to the right and y grows down, as under PERSPECTIVE.  Every kind other than PERSPECTIVE is a
+ * pinhole: pt_camera.aperture (and sensor_size, focal_length, focus_distance) is IGNORED, Halton dimensions 2-3 are consumed and not
+ * evaluated, so a path draws from bounce 1 on what it draws under a perspective pinhole.  A render under such a kind builds no camera-ray
+ * leaf lists (pt_camera_list_stats.built = 0) and walks the tree at bounce 0; AOVs, mattes, the film, adaptive sampling, regions and pass
+ * views work as ever, and pt_trace_primary, pt_debug_sample and pt_measure_traversal follow the projection.
+ * PT_ERR_INVALID_ARGUMENT (checked before the renderer): an unknown kind; of the fields of the chosen kind (the others are ignored) one that
+ * is not finite, ortho_height <= 0, fov_x outside (0, 2 pi], fov_y outside (0, pi], fisheye_fov outside (0, 2 pi] (the bounds are the
+ * fp32 values of 2 pi and pi).  PT_ERR_UNSUPPORTED: a kind other than PERSPECTIVE on a device group. */
+enum { PT_PROJ_PERSPECTIVE = 0, PT_PROJ_ORTHOGRAPHIC = 1, PT_PROJ_EQUIRECT = 2, PT_PROJ_FISHEYE = 3 };
+typedef struct pt_camera_projection {
+  uint32_t kind;        /* PT_PROJ_*; default PERSPECTIVE */
+  float ortho_height;   /* ORTHOGRAPHIC: height of the view volume in world units, > 0; the width follows the image's aspect; default 1 */
+  float fov_x, fov_y;   /* EQUIRECT: radians covered horizontally (0, 2 pi] and vertically (0, pi]; defaults 2 pi, pi */
+  float fisheye_fov;    /* FISHEYE (equidistant): full angle reached at the shorter side's edge, (0, 2 pi]; default pi */
+  uint32_t _pad[3];
+} pt_camera_projection;
+void pt_default_camera_projection(pt_camera_projection* p);
+int pt_set_camera_projection(pt_renderer* r, const pt_camera_projection* p);   /* read at the next pt_start_render */
+/* What the current render was started with.  PT_ERR_BAD_STATE before pt_start_render. */
+int pt_get_camera_projection(pt_renderer* r, pt_camera_projection* out);
+/* The camera rays of sample `sample_idx` of every pixel, W*H*3 floats each, row-major: the ray-generation kernel a full-frame render batch
+ * of one sample launches under the current render's projection (PERSPECTIVE: k_raygen), its queue scattered back to pixel order.  Either
+ * pointer may be NULL.  Full-frame like pt_trace_primary; blocks.  PT_ERR_BAD_STATE before pt_start_render. */
+int pt_debug_camera_rays(pt_renderer* r, uint32_t sample_idx, float* origins /* W*H*3 */, float* directions /* W*H*3 */);
+
 const char* pt_last_error(void);
 
 /* ---------------------------------------------------------------------------------------------------------- */

@@ -55,6 +55,9 @@
  *   (no counterpart; "film transparent" of other path tracers)   pt_film_options& filmOptions() / setFilmOptions(...), readbackFilm(): the foreground
  *                                                                with alpha, and the backdrop a target shows behind it (ptamd.h, ABI 5 extension);
  *                                                                `enabled` is handed over at startRender, the backdrop whenever a target is asked for
+ *   (no counterpart; the camera type of a scene editor)           pt_camera_projection& projection() / setProjection(...), renderProjection(): orthographic,
+ *                                                                panoramic and fisheye cameras beside the perspective one (ptamd.h, ABI 5 extension);
+ *                                                                handed over at startRender
  *   (no counterpart; the "render pass" drop-down of a viewport)    pt_view_options& viewOptions(), viewStats(): what the target shows of the AOVs, the
  *                                                                mattes, the film's alpha and the sampling (ptamd.h, ABI 5 extension); handed
  *                                                                over whenever a target is asked for
@@ -135,6 +138,7 @@ public:
     if (!check(pt_set_render_region(m_pt, &m_region))) return;       // (read here)
     if (!check(pt_set_matte_options(m_pt, &m_matte))) return;        // (read here)
     if (!check(pt_set_film_options(m_pt, &m_film))) return;          // (`enabled` is read here)
+    if (!check(pt_set_camera_projection(m_pt, &m_projection))) return;   // (read here)
     if (!check(pt_start_render(m_pt, &scene, &p))) return;
     m_size = uint2{p.width, p.height};
     m_started = true;
@@ -189,6 +193,18 @@ public:
   pt_colorspace& outputColorspace() { return m_outputSpace; }
 
   // ---- what the reference fixes at compile time or does not have (ptamd.h "NEW") ----
+  // Camera projections (ptamd.h pt_camera_projection, no counterpart in the reference): how the next startRender makes its camera rays —
+  // PT_PROJ_PERSPECTIVE (the reference's camera, the default), _ORTHOGRAPHIC (ortho_height), _EQUIRECT (fov_x, fov_y) or _FISHEYE
+  // (fisheye_fov).  Edited in place like filmOptions(); read at startRender, which fails on options outside their ranges.
+  [[nodiscard]] constexpr pt_camera_projection& projection() { return m_projection; }
+  void setProjection(const pt_camera_projection& p) { m_projection = p; }
+  // The projection the current render was started with; the default one when no render is.
+  [[nodiscard]] pt_camera_projection renderProjection() const {
+    pt_camera_projection out;
+    pt_default_camera_projection(&out);
+    if (m_pt && m_started) (void)check(pt_get_camera_projection(m_pt, &out));
+    return out;
+  }
   void setMaxBounces(uint32_t b) { m_maxBounces = b; }              // kernel.metal:5 MAX_BOUNCES = 50 (the default here too)
   void setFirstSample(uint32_t s) { m_firstSample = s; }            // frameIdx of the first sample: sample-range shards
   void setSamplesInFlight(uint32_t s) { m_samplesInFlight = s; }    // 0 = automatic
@@ -342,6 +358,7 @@ private:
     pt_default_selection_options(&m_selection);
     pt_default_film_options(&m_film);
     pt_default_view_options(&m_view);
+    pt_default_camera_projection(&m_projection);
     std::vector<int32_t> ord(devices, devices + count);
     pt_create_info ci{};
     ci.abi_version = PT_ABI_VERSION;
@@ -394,6 +411,7 @@ private:
   pt_selection_options m_selection{};
   pt_film_options m_film{};
   pt_view_options m_view{};
+  pt_camera_projection m_projection{};
   mutable void* m_presentStream = nullptr;
   mutable std::string m_lastError;
 };

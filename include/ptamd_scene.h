@@ -26,7 +26,13 @@ extern "C" {
 typedef struct pt_scene pt_scene; /* assets (textures, meshes, materials) + node hierarchy: core/scene.hpp without the ECS */
 
 /* loaders/gltf.hpp:20-25 LoadOptions */
-enum { PT_GLTF_NONE = 0, PT_GLTF_SKIP_EMPTY_NODES = 1 << 0, PT_GLTF_CREATE_SCENE_NODES = 1 << 1 };
+enum { PT_GLTF_NONE = 0, PT_GLTF_SKIP_EMPTY_NODES = 1 << 0, PT_GLTF_CREATE_SCENE_NODES = 1 << 1,
+       /* no reference counterpart: also load cameras[i].orthographic (ortho_height = 2 * ymag; xmag, znear and zfar are read and ignored:
+        * the width follows the image's aspect and the projection has no near or far plane).  With the bit the loader's camera table holds
+        * every camera in file order, so node.camera indexes line up (an entry with neither object keeps its place and is still skipped:
+        * only a node that names it fails, with the message below).  Without it ingestion is the reference's: orthographic cameras are
+        * dropped and a node that names one fails with "node.camera does not name a perspective camera" or gets another camera's data. */
+       PT_GLTF_ORTHOGRAPHIC_CAMERAS = 1 << 2 };
 
 /* MTL::PixelFormat raw values stored in scene.json ("format", core/scene.cpp:733) */
 enum { PT_MTL_R8UNORM = 10, PT_MTL_RG8UNORM = 30, PT_MTL_RGBA8UNORM = 70, PT_MTL_RGBA8UNORM_SRGB = 71, PT_MTL_RGBA32FLOAT = 125 };
@@ -54,6 +60,12 @@ int pt_scene_get_camera(const pt_scene* s, uint32_t i, uint64_t* node_id, char* 
  * Camera::withFocalLength(focal_mm) with a tracking transform. Returns its node id. */
 int pt_scene_add_camera(pt_scene* s, const char* name, const float position[3], const float target[3], float focal_length_mm,
                         uint64_t* node_id);
+
+/* The projection to render through `camera_node` with (ptamd.h pt_set_camera_projection): PT_PROJ_ORTHOGRAPHIC with ortho_height = 2 * ymag
+ * for a glTF orthographic camera loaded under PT_GLTF_ORTHOGRAPHIC_CAMERAS, pt_default_camera_projection's PERSPECTIVE for every other
+ * camera.  The snapshot's pt_camera of an orthographic camera node holds the defaults of a perspective one, which that projection ignores.
+ * (An orthographic camera does not survive pt_scene_save_json: the reference's file format has no field for it.) */
+int pt_scene_get_camera_projection(const pt_scene* s, uint64_t camera_node, pt_camera_projection* out);
 
 /* Builds (or rebuilds) the flat snapshot for rendering through `camera_node`.  The returned pointer and every array it
  * references are owned by the scene and stay valid until the next build/import/destroy. */

@@ -266,6 +266,16 @@ class FilmOptions(C.Structure):
     _fields_ = [("enabled", C.c_uint32), ("backdrop", C.c_uint32), ("backdrop_rgb", C.c_float * 3)]
 
 
+PROJ_PERSPECTIVE, PROJ_ORTHOGRAPHIC, PROJ_EQUIRECT, PROJ_FISHEYE = range(4)
+PROJ_NAMES = ("perspective", "ortho", "equirect", "fisheye")
+
+
+class CameraProjection(C.Structure):
+    """pt_camera_projection: how the camera rays of a render are made (read at pt_start_render); PERSPECTIVE is the reference's camera."""
+    _fields_ = [("kind", C.c_uint32), ("ortho_height", C.c_float), ("fov_x", C.c_float), ("fov_y", C.c_float), ("fisheye_fov", C.c_float),
+                ("_pad", C.c_uint32 * 3)]
+
+
 (VIEW_BEAUTY, VIEW_ALBEDO, VIEW_NORMAL, VIEW_DEPTH, VIEW_ALPHA, VIEW_MATTE, VIEW_SAMPLES, VIEW_NOISE, VIEW_COUNT) = range(9)
 VIEW_NAMES = ("beauty", "albedo", "normal", "depth", "alpha", "matte", "samples", "noise")
 RAMP_GREY, RAMP_HEAT = 0, 1
@@ -385,6 +395,10 @@ SYMBOLS = [
     ("pt_read_view_stats", C.c_int, [C.c_void_p, C.POINTER(ViewStats)]),
     ("pt_debug_view", C.c_int, [C.c_void_p, C.POINTER(ViewInputs), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(ViewOptions), C.c_void_p,
                                 C.POINTER(ViewStats)]),
+    ("pt_default_camera_projection", None, [C.POINTER(CameraProjection)]),
+    ("pt_set_camera_projection", C.c_int, [C.c_void_p, C.POINTER(CameraProjection)]),
+    ("pt_get_camera_projection", C.c_int, [C.c_void_p, C.POINTER(CameraProjection)]),
+    ("pt_debug_camera_rays", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("pt_last_error", C.c_char_p, []),
     ("pt_get_constants", C.c_int, [C.c_void_p, C.POINTER(Constants)]),
     ("pt_get_lights", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),

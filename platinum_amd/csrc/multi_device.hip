@@ -799,6 +799,23 @@ int pt_read_film(pt_renderer* r, float* rgba_out) {
   return fail(PT_ERR_BAD_STATE, "pt_read_film: a device group does not keep a film");
 }
 
+// A group's members would all render the same projection, but its checks (merged image against the single-device render) cover the
+// perspective camera only: any other kind is refused, as AOVs are.  The options are checked first, as on a single device.
+int pt_set_camera_projection(pt_renderer* r, const pt_camera_projection* p) {
+  if (is_group(r)) {
+    if (!p) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_camera_projection: null options");
+    if (const char* why = projection_error(*p)) return fail(PT_ERR_INVALID_ARGUMENT, std::string("pt_set_camera_projection: ") + why);
+    if (p->kind != PT_PROJ_PERSPECTIVE) return fail(PT_ERR_UNSUPPORTED, "pt_set_camera_projection: a device group renders the perspective camera only");
+  }
+  return on_members(r, dev_set_camera_projection, p);
+}
+
+int pt_get_camera_projection(pt_renderer* r, pt_camera_projection* out) { return on_first_started(r, dev_get_camera_projection, out); }
+
+int pt_debug_camera_rays(pt_renderer* r, uint32_t sample_idx, float* origins, float* directions) {
+  return on_first_started(r, dev_debug_camera_rays, sample_idx, origins, directions);
+}
+
 // The selection overlay draws from the ID mattes, which a group does not keep: its merged path shows no overlay.  The options go to every
 // member (never enabled); the set is held by the first member.
 int pt_set_selection_options(pt_renderer* r, const pt_selection_options* o) {

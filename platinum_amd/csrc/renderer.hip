@@ -84,6 +84,15 @@ size_t free_device_bytes() {
 
 enum BatchMode { BATCH_RENDER, BATCH_DEBUG, BATCH_MEASURE };
 
+// The camera rays of a batch into state buffer 0: k_raygen / k_raygen_adaptive under PT_PROJ_PERSPECTIVE, exactly as before the projections;
+// under any other kind of this render their counterpart in projection.hip.  Render, debug and measuring batches all come through here.
+void launch_camera_raygen(pt_renderer* r, Segments seg, uint32_t first, uint32_t ns, const TileSet* tiles) {
+  if (r->proj.kind == PT_PROJ_PERSPECTIVE)
+    launch_raygen(r->stream, r->grid, r->S, r->path_state(0), r->Lbuf.p, seg, r->ctr.p, first, ns, tiles);
+  else
+    launch_raygen_projected(r->stream, r->grid, r->S, r->proj_constants, r->path_state(0), r->Lbuf.p, seg, first, ns, tiles);
+}
+
 // One batch: `ns` samples of every pixel, first sample index `first`, `n0` samples already in the accumulator.
 int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, BatchMode mode, int32_t* hitlog) {
   const DeviceScene& S = r->S;
@@ -128,7 +137,7 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
   } else {
     {
       ScopedTimer t(r, K_RAYGEN);
-      launch_raygen(s, r->grid, S, r->path_state(0), r->Lbuf.p, seg, ctr, first, ns, tiles);
+      launch_camera_raygen(r, seg, first, ns, tiles);
       launch_chunk_tables(s, seg, 0, ctr, 0, 0, false);
     }
     ScopedTimer t(r, K_CLOSEST);
@@ -323,6 +332,8 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   pt_default_matte_options(&r->matte_opts);
   pt_default_selection_options(&r->selection);
   pt_default_film_options(&r->film_opts);
+  pt_default_camera_projection(&r->proj_opts);
+  r->proj = r->proj_opts;
   pt_default_view_options(&r->view_opts);
   r->device = device_ordinal;
   if (const char* e = getenv("PTAMD_REFILL")) r->refill_threshold = (uint32_t)atoi(e);
@@ -555,7 +566,8 @@ int build_records(pt_renderer* r) {
 int build_camera_lists(pt_renderer* r, const pt_render_params* p) {
   const DeviceScene& S = r->S;
   r->cam_stats = pt_camera_list_stats{};
-  const bool want = camera_lists_wanted(r->no_camera_lists, r->two_level, r->bvh.wide6, S.root_ref, S.camera.apertureRadius,
+  const bool want = camera_lists_projection(r->proj_opts.kind) &&
+                    camera_lists_wanted(r->no_camera_lists, r->two_level, r->bvh.wide6, S.root_ref, S.camera.apertureRadius,
                                         r->adaptive_opts.enabled != 0, r->region_opts.enabled != 0);
   const uint32_t cap = r->cam_cap_override ? r->cam_cap_override : kCamListCapacity;
   const size_t slots = (size_t)tile_count(p->width, p->height) * 64;
@@ -715,6 +727,7 @@ void reset_progress(pt_renderer* r, const pt_render_params* p) {
   r->region = r->region_opts.enabled != 0;
   r->vtiles = r->adaptive || r->region;
   r->rect = render_rect(r, p);
+  r->proj = r->proj_opts;   // (proj_constants: dev_start_render, from the snapshot's camera)
   r->ad_cur = 0;
   r->ad_event_valid = false;
   r->ad_next = r->adaptive_opts.min_spp;   // the first checkpoint (none when min_spp >= spp)
@@ -746,6 +759,7 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   };
   HostScene hs;
   if ((rc = flatten_scene(r, scene, p, &hs)) != PT_OK) return rc;
+  const ProjectionConstants proj_constants = derive_projection(scene->camera, p->width, p->height, r->proj_opts);
   r->material_base.resize(hs.instances.size());
   for (size_t i = 0; i < hs.instances.size(); i++) r->material_base[i] = hs.instances[i].material_base;
   phase("host flatten + light table");
@@ -762,6 +776,7 @@ int dev_start_render(pt_renderer* r, const pt_scene_snapshot* scene, const pt_re
   if ((rc = allocate_buffers(r, p)) != PT_OK) return rc;
   phase("queues + accumulator");
   reset_progress(r, p);
+  r->proj_constants = proj_constants;
   return PT_OK;
 }
 
@@ -1192,7 +1207,7 @@ int dev_trace_primary(pt_renderer* r, uint32_t sample_idx, pt_hit_record* out) {
   PT_HIP(hipMemsetAsync(r->ctr.p, 0, sizeof(BatchCounters), s));
   Segments seg = r->segments();
   seg.nsamples = 1;
-  launch_raygen(s, r->grid, r->S, r->path_state(0), r->Lbuf.p, seg, r->ctr.p, sample_idx, 1, nullptr);
+  launch_camera_raygen(r, seg, sample_idx, 1, nullptr);
   launch_chunk_tables(s, seg, 0, r->ctr.p, 0, 0, false);
   launch_trace_closest(s, r->closest_grid, r->S, r->path_state(0), r->hit.p, seg, 0, r->ctr.p, 0, r->spill.p, nullptr, npix, false);
   launch_hit_records(s, r->grid, r->S, r->path_state(0), r->hit.p, seg, rec.p);
@@ -1200,6 +1215,54 @@ int dev_trace_primary(pt_renderer* r, uint32_t sample_idx, pt_hit_record* out) {
   PT_HIP(hipGetLastError());
   PT_HIP(hipStreamSynchronize(s));
   PT_HIP(hipMemcpy(out, rec.p, sizeof(pt_hit_record) * npix, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+extern "C" void pt_default_camera_projection(pt_camera_projection* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->kind = PT_PROJ_PERSPECTIVE;
+  p->ortho_height = 1.0f;
+  p->fov_x = 2.0f * kPi; p->fov_y = kPi;
+  p->fisheye_fov = kPi;
+}
+
+// (the options are checked before the renderer, as dev_set_despeckle_options)
+int dev_set_camera_projection(pt_renderer* r, const pt_camera_projection* p) {
+  if (!p) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_camera_projection: null options");
+  if (const char* why = projection_error(*p)) return fail(PT_ERR_INVALID_ARGUMENT, std::string("pt_set_camera_projection: ") + why);
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_camera_projection: null renderer");
+  r->proj_opts = *p;
+  return PT_OK;
+}
+
+int dev_get_camera_projection(pt_renderer* r, pt_camera_projection* out) {
+  if (!r || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (!r->started) return fail(PT_ERR_BAD_STATE, "pt_get_camera_projection before pt_start_render");
+  *out = r->proj;
+  return PT_OK;
+}
+
+int dev_debug_camera_rays(pt_renderer* r, uint32_t sample_idx, float* origins, float* directions) {
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+  if (!r->started) return fail(PT_ERR_BAD_STATE, "pt_debug_camera_rays before pt_start_render");
+  PT_HIP(hipSetDevice(r->device));
+  { const int rc = flush_pending(r, true); if (rc != PT_OK) return rc; }
+  const size_t n = 3 * (size_t)r->S.width * r->S.height;
+  DevBuf<float> o, d;
+  if (origins) PT_HIP(o.alloc(n));
+  if (directions) PT_HIP(d.alloc(n));
+  hipStream_t s = r->stream;
+  PT_HIP(hipMemsetAsync(r->ctr.p, 0, sizeof(BatchCounters), s));
+  Segments seg = r->segments();
+  seg.nsamples = 1;
+  launch_camera_raygen(r, seg, sample_idx, 1, nullptr);
+  launch_camera_rays(s, r->grid, r->S.width, r->path_state(0), seg, o.p, d.p);
+  launch_fold_counters(s, r->ctr.p, r->totals.p + 1, seg, false);  // clears the per-wave statistics (scratch slot), as pt_trace_primary
+  PT_HIP(hipGetLastError());
+  PT_HIP(hipStreamSynchronize(s));
+  if (origins) PT_HIP(hipMemcpy(origins, o.p, sizeof(float) * n, hipMemcpyDeviceToHost));
+  if (directions) PT_HIP(hipMemcpy(directions, d.p, sizeof(float) * n, hipMemcpyDeviceToHost));
   return PT_OK;
 }
 

@@ -18,6 +18,7 @@
 #include "math_probe.h"
 #include "film.h"
 #include "matte.h"
+#include "projection.h"
 #include "pt_math_probe.h"
 #include "selection.h"
 #include "view.h"
@@ -163,6 +164,11 @@ struct pt_renderer {
   DevBuf<uint32_t> Fbuf;            // 1: the camera ray hit, 0: it missed, per Lbuf entry
   DevBuf<vec4> film_img;            // [pixel] {premultiplied foreground, coverage} running means
   DevBuf<vec4> film_src;            // the film over the backdrop: what the display chain starts from
+  // camera projection (projection.hip): proj_opts is what pt_set_camera_projection holds for the NEXT start; proj and the constants
+  // derived from it and the snapshot's camera belong to the current render.  Under PT_PROJ_PERSPECTIVE nothing of projection.hip is launched.
+  pt_camera_projection proj_opts{};
+  pt_camera_projection proj{};
+  ProjectionConstants proj_constants{};
   // pass views (view.hip): nothing is allocated or launched under PT_VIEW_BEAUTY.  The record (the depth view's range) is
   // allocated by the first target read under DEPTH with auto_range, or the first pt_read_view_stats, and outlives pt_start_render like exp_rec.
   pt_view_options view_opts{};
@@ -326,6 +332,9 @@ int dev_read_matte_slots(pt_renderer* r, uint32_t layer, pt_matte_slot* out);
 int dev_read_matte(pt_renderer* r, uint32_t layer, const uint32_t* ids, uint32_t id_count, float* coverage_out);
 int dev_pick(pt_renderer* r, uint32_t x, uint32_t y, pt_pick_result* out);
 int dev_read_film(pt_renderer* r, float* rgba_out);
+int dev_set_camera_projection(pt_renderer* r, const pt_camera_projection* p);
+int dev_get_camera_projection(pt_renderer* r, pt_camera_projection* out);
+int dev_debug_camera_rays(pt_renderer* r, uint32_t sample_idx, float* origins, float* directions);
 
 // ---- display (display.hip): the stages' options, and the chain from an HDR image to the RGBA8 target.  `merged`: a device group's merged
 //      image on this renderer's device, which the group has waited for; NULL = the renderer's own image ----

@@ -557,6 +557,7 @@ struct Importer {
   std::vector<uint64_t> material_ids, mesh_ids;
   std::map<uint64_t, std::vector<uint64_t>> mesh_materials;
   std::vector<Camera> cameras;
+  std::vector<char> camera_usable;   // per entry of `cameras`: 0 = a placeholder that keeps the indexes in step (PT_GLTF_ORTHOGRAPHIC_CAMERAS)
   struct TexUse { int type = TT_SRGB; std::vector<std::pair<uint64_t, int>> users; };
   std::vector<std::pair<size_t, TexUse>> textures_to_load;  // insertion-ordered map keyed by glTF texture index
   TexUse& tex_use(size_t idx) {
@@ -706,7 +707,7 @@ struct Importer {
     const size_t idx = scene.create_node(sname(n), parent, kNoId);
     if (cam) {
       const size_t ci = (size_t)cam->u64();
-      if (ci >= cameras.size()) fail("gltf: node.camera does not name a perspective camera");
+      if (ci >= cameras.size() || !camera_usable[ci]) fail("gltf: node.camera does not name a perspective camera");
       scene.nodes[idx].camera = cameras[ci]; scene.nodes[idx].has_camera = true;
     }
     float t[3] = {0, 0, 0}, q[4] = {0, 0, 0, 1}, s[3] = {1, 1, 1};
@@ -782,15 +783,34 @@ void import_gltf(Scene& scene, const std::string& path, int options) {  // loade
     }
   }
   for (size_t i = 0; i < g.count("meshes"); i++) im.load_mesh(g.item("meshes", i));
+  // PT_GLTF_ORTHOGRAPHIC_CAMERAS (no reference counterpart): cameras[i].orthographic is loaded too, and the table holds EVERY camera in file
+  // order, so that node.camera indexes line up.  ortho_height = 2 * ymag; xmag (the width follows the image's aspect), znear and zfar (the
+  // orthographic projection has no near or far plane) are read and ignored.  Without the bit: as the reference, perspective cameras only.
+  const bool load_ortho = (options & PT_GLTF_ORTHOGRAPHIC_CAMERAS) != 0;
   for (size_t i = 0; i < g.count("cameras"); i++) {  // :83-91: perspective cameras only, Camera::withFov(yfov, {24*aspect, 24})
     const JV& c = g.item("cameras", i);
     const JV* p = c.find("perspective");
+    if (!p && load_ortho) {
+      const JV* o = c.find("orthographic");
+      // neither object: skipped as ever, but its place in the table is kept; only a node that names it fails, with the message above
+      if (!o) { im.cameras.push_back(Camera{}); im.camera_usable.push_back(0); continue; }
+      const float ymag = (float)o->at("ymag").num();
+      (void)o->at("xmag").num(); (void)o->at("znear").num(); (void)o->at("zfar").num();   // required by glTF; not used
+      if (!(ymag > 0.0f) || !std::isfinite(ymag)) fail("gltf: orthographic camera " + std::to_string(i) + ": ymag must be finite and > 0");
+      Camera cam;
+      cam.orthographic = true;
+      cam.ortho_height = 2.0f * ymag;
+      im.cameras.push_back(cam);
+      im.camera_usable.push_back(1);
+      continue;
+    }
     if (!p) continue;
     Camera cam;
     const float aspect = p->find("aspectRatio") ? (float)p->at("aspectRatio").num() : 1.5f;
     cam.sensor_size[0] = 24.0f * aspect; cam.sensor_size[1] = 24.0f;
     cam.focal_length = cam.sensor_size[1] / (2.0f * tanf((float)p->at("yfov").num() * 0.5f));  // core/camera.hpp:32-42
     im.cameras.push_back(cam);
+    im.camera_usable.push_back(1);
   }
   size_t local_root = scene.root_index;
   const size_t nscenes = g.count("scenes");

@@ -772,6 +772,19 @@ int pt_scene_add_camera(pt_scene* s, const char* name, const float position[3], 
     if (node_id) *node_id = n.id;
   });
 }
+int pt_scene_get_camera_projection(const pt_scene* s, uint64_t camera_node, pt_camera_projection* out) {
+  if (!s || !out) { ptio::g_error = "null argument"; return PT_ERR_INVALID_ARGUMENT; }
+  return guarded([&] {
+    const ptio::Node* cam = nullptr;
+    for (const ptio::Node& n : s->s->nodes) if (n.id == camera_node && n.has_camera) cam = &n;
+    if (!cam) throw std::runtime_error("scene: node " + std::to_string(camera_node) + " is not a camera node");
+    // pt_default_camera_projection's values (renderer.hip), written here: the scene code is host-only C++ and calls nothing of the driver
+    memset(out, 0, sizeof(*out));
+    out->kind = cam->camera.orthographic ? PT_PROJ_ORTHOGRAPHIC : PT_PROJ_PERSPECTIVE;
+    out->ortho_height = cam->camera.orthographic ? cam->camera.ortho_height : 1.0f;
+    out->fov_x = 6.28318530717958647692f; out->fov_y = 3.14159265358979323846f; out->fisheye_fov = 3.14159265358979323846f;
+  });
+}
 int pt_scene_build_snapshot(pt_scene* s, uint64_t camera_node, const pt_scene_snapshot** out) {
   if (!s || !out) { ptio::g_error = "null argument"; return PT_ERR_INVALID_ARGUMENT; }
   return guarded([&] { *out = s->s->build_snapshot(camera_node); });

@@ -50,6 +50,9 @@ struct Camera {  // core/camera.hpp:10-18
   float focal_length = 50.0f, aperture = 0.0f;
   uint32_t aperture_blades = 7;
   float roundness = 1.0f, bokeh_power = 0.0f, focus_distance = 1.0f;
+  // no reference counterpart: a glTF orthographic camera loaded under PT_GLTF_ORTHOGRAPHIC_CAMERAS (pt_scene_get_camera_projection)
+  bool orthographic = false;
+  float ortho_height = 1.0f;
 };
 struct Material {  // core/material.hpp:15-49
   std::string name;

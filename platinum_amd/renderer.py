@@ -440,6 +440,38 @@ class Renderer:
         abi.check(self._lib, self._lib.pt_read_film(self._h, out.ctypes.data))
         return out
 
+    # camera projections (include/ptamd.h, an additive extension of ABI 5): no counterpart in the reference's path tracer
+    def projection(self):
+        """The projection the NEXT startRender will use (pt_default_camera_projection until setProjection is called)."""
+        if getattr(self, "_projection", None) is None:
+            self._projection = abi.CameraProjection()
+            self._lib.pt_default_camera_projection(C.byref(self._projection))
+        o = abi.CameraProjection()
+        C.memmove(C.byref(o), C.byref(self._projection), C.sizeof(o))
+        return o
+
+    def setProjection(self, o=None, **fields):
+        """Sets `o` (default: the current projection) with `fields` overriding it, e.g. setProjection(kind=abi.PROJ_EQUIRECT) or
+        setProjection(kind=abi.PROJ_ORTHOGRAPHIC, ortho_height=2.5).  Takes effect at the next startRender."""
+        o = self.projection() if o is None else o
+        for k, v in fields.items():
+            setattr(o, k, v)
+        abi.check(self._lib, self._lib.pt_set_camera_projection(self._h, C.byref(o)))
+        self._projection = o
+
+    def renderProjection(self):
+        """The projection the current render was started with."""
+        o = abi.CameraProjection()
+        abi.check(self._lib, self._lib.pt_get_camera_projection(self._h, C.byref(o)))
+        return o
+
+    def debugCameraRays(self, sample_idx=0):
+        """(origins, directions), each (H, W, 3) float32: the camera rays of one sample as the render's own ray-generation kernel makes them."""
+        w, h = self.size
+        o, d = np.empty((h, w, 3), np.float32), np.empty((h, w, 3), np.float32)
+        abi.check(self._lib, self._lib.pt_debug_camera_rays(self._h, sample_idx, o.ctypes.data, d.ctypes.data))
+        return o, d
+
     # pass views (include/ptamd.h, an additive extension of ABI 5): no counterpart in the reference's path tracer
     def viewOptions(self):
         """The options in effect (pt_default_view_options until setViewOptions is called)."""

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import abi
 
-GLTF_NONE, GLTF_SKIP_EMPTY_NODES, GLTF_CREATE_SCENE_NODES = 0, 1, 2
+GLTF_NONE, GLTF_SKIP_EMPTY_NODES, GLTF_CREATE_SCENE_NODES, GLTF_ORTHOGRAPHIC_CAMERAS = 0, 1, 2, 4
 MTL_R8UNORM, MTL_RG8UNORM, MTL_RGBA8UNORM, MTL_RGBA8UNORM_SRGB, MTL_RGBA32FLOAT = 10, 30, 70, 71, 125
 
 
@@ -28,6 +28,7 @@ SCENE_SYMBOLS = [
     ("pt_scene_get_counts", C.c_int, [C.c_void_p, C.POINTER(SceneCounts)]),
     ("pt_scene_get_camera", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.c_char_p, C.c_uint32]),
     ("pt_scene_add_camera", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_uint64)]),
+    ("pt_scene_get_camera_projection", C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(abi.CameraProjection)]),
     ("pt_scene_build_snapshot", C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.POINTER(abi.SceneSnapshot))]),
     ("pt_generate_tangents", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     ("pt_decode_image_rgba8", C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64]),
@@ -115,6 +116,19 @@ class SceneFile:
         _check(_lib().pt_scene_add_camera(self._h, name.encode(), p, t, focal_length, C.byref(nid)))
         self.camera = nid.value
         return nid.value
+
+    def camera_projection(self, camera_node=None):
+        """abi.CameraProjection to render through the camera node with (default: the scene's current camera): ORTHOGRAPHIC for a glTF
+        orthographic camera imported under GLTF_ORTHOGRAPHIC_CAMERAS, PERSPECTIVE otherwise.  Renderer.setProjection takes it."""
+        cam = self.camera if camera_node is None else camera_node
+        if cam is None:
+            cams = self.cameras()
+            if not cams:
+                raise abi.PtamdError("scene has no camera node: add_camera() first")
+            cam = cams[0][0]
+        out = abi.CameraProjection()
+        _check(_lib().pt_scene_get_camera_projection(self._h, cam, C.byref(out)))
+        return out
 
     def snapshot(self):
         cam = self.camera

@@ -16,6 +16,9 @@ tracing (GMoN optional), fused post-process + tonemap — to an 8-bit PNG.
     python tools/render_scene.py builtin:c5 studio.png --size 960 540 --spp 64 --film 0.18,0.18,0.18  (the objects over a flat colour)
     python tools/render_scene.py builtin:c3 ids.png --size 960 540 --spp 32 --view matte --matte instance   (the picture itself shows the ids)
     python tools/render_scene.py builtin:c3 heat.png --size 960 540 --spp 256 --adaptive 0.05 --view samples --ramp heat
+    python tools/render_scene.py builtin:c5 probe.png --size 1024 512 --spp 64 --projection equirect     (a light probe of the scene)
+    python tools/render_scene.py builtin:c5 dome.png --size 1024 1024 --spp 64 --projection fisheye --fisheye-fov 3.14159
+    python tools/render_scene.py plan.gltf plan.png --projection ortho --ortho-height 12     (a glTF orthographic camera is used as it is)
 """
 import argparse, os, struct, sys, time, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -81,7 +84,18 @@ def main():
                     help="what the picture shows (the render target's pass view, drawn on the device): the beauty, or the albedo, normals, depth, "
                          "film alpha, ID mattes (the layer of --matte, default instance), sample counts or noise estimate; what the view needs is kept")
     ap.add_argument("--ramp", choices=("grey", "heat"), default="grey", help="with --view depth / samples / noise: grey, or blue-cyan-green-yellow-red")
+    ap.add_argument("--projection", choices=abi.PROJ_NAMES, default=None,
+                    help="the camera's projection: perspective (the default, unless the scene's camera is a glTF orthographic one), ortho, equirect "
+                         "(a panorama: 2:1 with the default --pano-fov is a light probe of the scene) or fisheye (equidistant)")
+    ap.add_argument("--ortho-height", type=float, default=None, metavar="H", help="with --projection ortho: height of the view volume in world units")
+    ap.add_argument("--pano-fov", type=float, nargs=2, default=None, metavar=("X", "Y"),
+                    help="with --projection equirect: radians covered horizontally (0, 2 pi] and vertically (0, pi]")
+    ap.add_argument("--fisheye-fov", type=float, default=None, metavar="A",
+                    help="with --projection fisheye: full angle in radians reached at the edge of the image's shorter side, (0, 2 pi]")
     a = ap.parse_args()
+    for flag, value, kind in (("--ortho-height", a.ortho_height, "ortho"), ("--pano-fov", a.pano_fov, "equirect"), ("--fisheye-fov", a.fisheye_fov, "fisheye")):
+        if value is not None and a.projection != kind:
+            ap.error("%s needs --projection %s" % (flag, kind))
     view = abi.VIEW_NAMES.index(a.view)
     backdrop = None
     if a.film is not None and a.film != "transparent":
@@ -116,7 +130,8 @@ def main():
         factory, *_ = scenes.CONFIGS[a.scene.split(":", 1)[1]]
         sc = factory()
     else:
-        sc = scene_io.SceneFile.load(a.scene) if a.scene.endswith(".json") else scene_io.SceneFile.empty().import_gltf(a.scene, scene_io.GLTF_SKIP_EMPTY_NODES)
+        sc = scene_io.SceneFile.load(a.scene) if a.scene.endswith(".json") else scene_io.SceneFile.empty().import_gltf(
+            a.scene, scene_io.GLTF_SKIP_EMPTY_NODES | scene_io.GLTF_ORTHOGRAPHIC_CAMERAS)
         if a.env == "sky":
             sc.set_environment(scenes.sky_environment(1024, 512))
         elif a.env != "none":
@@ -126,6 +141,20 @@ def main():
         c = sc.counts()
         print(f"scene: {c.instances} instances, {c.triangles} triangles, {c.textures} textures, {c.materials} materials, cameras {sc.cameras()}")
     r = Renderer(device=0)
+    # the projection: the scene camera's own (a glTF orthographic camera), with the command line over it
+    proj = sc.camera_projection() if isinstance(sc, scene_io.SceneFile) else r.projection()
+    if a.projection is not None:
+        proj.kind = abi.PROJ_NAMES.index(a.projection)
+    if a.ortho_height is not None:
+        proj.ortho_height = a.ortho_height
+    if a.pano_fov is not None:
+        proj.fov_x, proj.fov_y = a.pano_fov
+    if a.fisheye_fov is not None:
+        proj.fisheye_fov = a.fisheye_fov
+    try:
+        r.setProjection(proj)
+    except abi.PtamdError as e:
+        ap.error(str(e))
     if a.denoise:
         r.setDenoiseOptions(enabled=1, apply_to_target=1)
     if a.despeckle is not None:
