@@ -540,6 +540,36 @@ enum {
 };
 int pt_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const void* b, void* out0, void* out1);
 
+/* ---- light probe (NEW, an additive extension of ABI 5: one entry point, one struct and two enums) ----
+ * Parity surface: the light-sampling part of the shading stage, evaluated on the device on its own against the scene of the STARTED render
+ * (its light records, cumulative table, environment texture and alias table).  One elementwise launch on the renderer's stream; upload and
+ * read-back inside the call; the render's state is left alone.  `in` holds n records of 4-byte words, `out` receives n records:
+ *   PT_LIGHT_SAMPLE    in:  8 floats  hit position x y z, the three NEE draws rl.x rl.y rz, 2 unused
+ *                      out: 12 words  lit (uint32), Li r g b, lwi x y z, lpdf, pLight, dist, dim (uint32), 0
+ *                      = shade_nee_light for a hit at that position of a material with args->roughness / metallic / transmission, whose sampler
+ *                      cursor is args->dim, with the render's integrator.  args->tables picks the light table the search and the record load
+ *                      read: PT_LIGHT_TABLES_HBM the scene's own, PT_LIGHT_TABLES_LDS a copy staged per block as the shade kernel stages it
+ *                      (at most 64 lights).  Both give the same bits.
+ *   PT_LIGHT_ENV_MISS  in:  4 floats  direction x y z, lastPdf
+ *                      out: 4 floats  the radiance a miss in that direction adds for attenuation 1 at bounce args->bounce after a sample
+ *                      that was specular or not (args->lastSpecular), 0
+ * PT_ERR_INVALID_ARGUMENT, before the renderer is looked at: fn >= PT_LIGHT_COUNT, n = 0 or n > 2^24, a null args / in / out, args->tables
+ * not one of the two; then a null renderer.  PT_ERR_BAD_STATE before pt_start_render.  PT_ERR_UNSUPPORTED: PT_LIGHT_TABLES_LDS with more than
+ * 64 lights, PT_LIGHT_ENV_MISS on a render without an environment. */
+enum { PT_LIGHT_SAMPLE = 0, PT_LIGHT_ENV_MISS = 1, PT_LIGHT_COUNT = 2 };
+enum { PT_LIGHT_TABLES_HBM = 0, PT_LIGHT_TABLES_LDS = 1 };
+#define PT_LIGHT_SAMPLE_IN_WORDS 8u
+#define PT_LIGHT_SAMPLE_OUT_WORDS 12u
+#define PT_LIGHT_ENV_MISS_IN_WORDS 4u
+#define PT_LIGHT_ENV_MISS_OUT_WORDS 4u
+typedef struct pt_light_probe_args {
+  float roughness, metallic, transmission;   /* PT_LIGHT_SAMPLE: the material terms that gate NEE */
+  uint32_t dim;                              /* PT_LIGHT_SAMPLE: the sampler cursor at the hit */
+  uint32_t tables;                           /* PT_LIGHT_SAMPLE: PT_LIGHT_TABLES_* */
+  uint32_t bounce, lastSpecular;             /* PT_LIGHT_ENV_MISS */
+} pt_light_probe_args;
+int pt_debug_lights(pt_renderer* r, uint32_t fn, uint32_t n, const pt_light_probe_args* args, const void* in, void* out);
+
 /* ---- tile-adaptive sampling (NEW, an additive extension of ABI 5: new entry points and one new struct, no existing struct changed) ----
  * A render started while `enabled` is set stops sampling an 8x8 tile of the accumulator once it has converged; pt_render_params.spp
  * becomes the per-pixel maximum.  Checkpoints are at the sample counts c_k = min_spp + k * interval with c_k < spp.  At each, every

@@ -1223,6 +1223,52 @@ LightSample sampleEnvironmentLight(const orc_scene& sc, float2 r) {
   return ls;
 }
 
+// The miss branch of both integrators (kernel.metal:517-539; :299-311 for the simple one, which has no MIS weight): what a ray that leaves
+// the scene in direction `dir` adds to the path's radiance.  Needs an environment.
+float3 missRadiance(const orc_scene& sc, float3 dir, float3 attenuation, uint32_t bounce, float lastPdf, bool lastSpecular) {
+  const bool mis = sc.params.integrator == PT_INTEGRATOR_MIS;
+  const Tex& texture = sc.textures[sc.env_texture];
+  float2 uv = rayDirToUv(dir);
+  float4 t = tex_sample(texture, uv);
+  const float3 Le = f3(t.x, t.y, t.z);
+  if (!mis || bounce == 0 || lastSpecular) return attenuation * Le;
+  // uint32_t x = w * uv.x (kernel.metal:530-531): uv.x is negative for half the sphere (atan2 range); the
+  // float->uint conversion of a negative value is defined here as 0, and indices are clamped into the table
+  uint32_t w = (uint32_t)texture.w, h = (uint32_t)texture.h;
+  float fxw = (float)w * uv.x, fyh = (float)h * uv.y;
+  uint32_t x = fxw > 0.0f ? (uint32_t)fxw : 0u, y = fyh > 0.0f ? (uint32_t)fyh : 0u;
+  x = std::min(x, w - 1); y = std::min(y, h - 1);
+  float lightPdf = sc.env_alias[(size_t)y * w + x].pdf * 0.25f * 0.318309886183790671538f;  // M_1_PI_F
+  float bsdfWeight = lastPdf / (lastPdf + lightPdf);
+  return attenuation * bsdfWeight * Le;
+}
+
+// kernel.metal:587: which hits run next-event estimation
+inline bool neeGate(bool mis, float roughness, float metallic, float transmission) {
+  return mis && (roughness > 0.0f || metallic + transmission < 1.0f);
+}
+
+// kernel.metal:590-616: the choice between the environment and the area lights by rz, and the sample on the chosen light.  With neither
+// area lights nor an environment the reference indexes envLights[0] out of bounds (UB); NEE is skipped then (false), the dimension
+// schedule is kept by the caller.
+bool chooseLight(const orc_scene& sc, const Hit& hit, float2 rl, float rz, LightSample& lightSample, float& pLight) {
+  const pt_constants& C = sc.constants;
+  const uint32_t envCount = C.envLightCount;
+  if (!(C.lightCount > 0 || envCount > 0)) return false;
+  const float pInfinite = C.lightCount == 0 ? 1.0f : (float)envCount / (float)(envCount + 1);
+  if (rz < pInfinite) {
+    rz /= pInfinite;  // (selects among envCount lights; there is one)
+    pLight = pInfinite / (float)envCount;
+    lightSample = sampleEnvironmentLight(sc, rl);
+  } else {
+    rz = (rz - pInfinite) / (1.0f - pInfinite);
+    const pt_area_light& light = sampleLightPower(sc, rz);
+    pLight = (1.0f - pInfinite) * light.power / C.totalLightPower;
+    lightSample = sampleAreaLight(sc, hit, light, rl);
+  }
+  return true;
+}
+
 struct PathLog { int32_t* hits; uint32_t stride; uint32_t pixel; };  // hits[(bounce*stride + pixel)*2 + {0,1}]
 
 struct ThreadStats { uint64_t closest = 0, shadow = 0, shaded = 0, nonfinite = 0; TraversalCounters tc_closest, tc_shadow; bool verbose = false; };
@@ -1256,25 +1302,7 @@ float3 trace_path(const orc_scene& sc, uint32_t px, uint32_t py, uint32_t frameI
       h[1] = isect.hit ? (int32_t)isect.primitive_id : -1;
     }
     if (!isect.hit) {  // kernel.metal:517-543 (simple integrator :299-311: no MIS weight)
-      if (sc.env_texture >= 0) {
-        const Tex& texture = sc.textures[sc.env_texture];
-        float2 uv = rayDirToUv(ray.direction);
-        float4 t = tex_sample(texture, uv);
-        const float3 Le = f3(t.x, t.y, t.z);
-        if (!mis || bounce == 0 || (lastSample.flags & Sample_Specular)) {
-          L += attenuation * Le;
-        } else {
-          // uint32_t x = w * uv.x (kernel.metal:530-531): uv.x is negative for half the sphere (atan2 range); the
-          // float->uint conversion of a negative value is defined here as 0, and indices are clamped into the table
-          uint32_t w = (uint32_t)texture.w, h = (uint32_t)texture.h;
-          float fxw = (float)w * uv.x, fyh = (float)h * uv.y;
-          uint32_t x = fxw > 0.0f ? (uint32_t)fxw : 0u, y = fyh > 0.0f ? (uint32_t)fyh : 0u;
-          x = std::min(x, w - 1); y = std::min(y, h - 1);
-          float lightPdf = sc.env_alias[(size_t)y * w + x].pdf * 0.25f * 0.318309886183790671538f;  // M_1_PI_F
-          float bsdfWeight = lastSample.pdf / (lastSample.pdf + lightPdf);
-          L += attenuation * bsdfWeight * Le;
-        }
-      }
+      if (sc.env_texture >= 0) L += missRadiance(sc, ray.direction, attenuation, bounce, lastSample.pdf, (lastSample.flags & Sample_Specular) != 0);
       L += attenuation * backgroundColor;
       break;
     }
@@ -1307,27 +1335,12 @@ float3 trace_path(const orc_scene& sc, uint32_t px, uint32_t py, uint32_t frameI
 
     ray.origin = hit.pos;  // kernel.metal:582
 
-    if (mis && (ctx.roughness > 0.0f || ctx.metallic + ctx.transmission < 1.0f)) {  // kernel.metal:587-639
+    if (neeGate(mis, ctx.roughness, ctx.metallic, ctx.transmission)) {  // kernel.metal:587-639
       float2 rl = halton.sample2d();
       float rz = halton.sample1d();
-      // kernel.metal:590-616. With neither area lights nor an environment the reference indexes envLights[0] out of
-      // bounds (UB); we skip NEE then but keep the dimension schedule.
-      const uint32_t envCount = C.envLightCount;
-      if (C.lightCount > 0 || envCount > 0) {
-        const float pInfinite = C.lightCount == 0 ? 1.0f : (float)envCount / (float)(envCount + 1);
-        LightSample lightSample;
-        float pLight = 0;
-        if (rz < pInfinite) {
-          rz /= pInfinite;  // (selects among envCount lights; there is one)
-          pLight = pInfinite / (float)envCount;
-          lightSample = sampleEnvironmentLight(sc, rl);
-        } else {
-          rz = (rz - pInfinite) / (1.0f - pInfinite);
-          const pt_area_light& light = sampleLightPower(sc, rz);
-          pLight = (1.0f - pInfinite) * light.power / C.totalLightPower;
-          lightSample = sampleAreaLight(sc, hit, light, rl);
-        }
-
+      LightSample lightSample;
+      float pLight = 0;
+      if (chooseLight(sc, hit, rl, rz, lightSample, pLight)) {
         const float3 wi = hit.frame.worldToLocal(lightSample.wi);
         const Eval bsdfEval = bsdf.eval(hit.wo, wi);
         if (length_squared(bsdfEval.f) > 0.0f) {
@@ -1733,6 +1746,45 @@ void orc_math_batch(uint32_t fn, uint32_t n, const void* a_, const void* b_, voi
       default: break;
     }
   }
+}
+// The oracle's twins of pt_debug_lights (include/ptamd.h): the same records in, the same records out, on the oracle's own scene.
+// PT_LIGHT_SAMPLE: in 8 floats (hit position, rl.x, rl.y, rz, 2 unused), out 12 words (lit, Li, lwi, lpdf, pLight, dist, dim, 0).
+void orc_light_sample(const orc_scene* sc, uint32_t n, const pt_light_probe_args* args, const void* in_, void* out_) {
+  const float* in = (const float*)in_;
+  uint32_t* out = (uint32_t*)out_;
+  auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
+  const bool mis = sc->params.integrator == PT_INTEGRATOR_MIS;
+  for (uint32_t i = 0; i < n; i++) {
+    const float* e = in + (size_t)i * PT_LIGHT_SAMPLE_IN_WORDS;
+    uint32_t* o = out + (size_t)i * PT_LIGHT_SAMPLE_OUT_WORDS;
+    for (uint32_t k = 0; k < PT_LIGHT_SAMPLE_OUT_WORDS; k++) o[k] = 0u;   // (+0.0f is all zero bits)
+    o[10] = args->dim + 6;   // the six dimensions of the BSDF sample come before NEE's in the schedule
+    if (!neeGate(mis, args->roughness, args->metallic, args->transmission)) continue;
+    o[10] = args->dim + 9;   // rl and rz are drawn whether a light exists or not
+    Hit hit{};
+    hit.pos = f3(e[0], e[1], e[2]);
+    LightSample ls;
+    float pLight = 0;
+    if (!chooseLight(*sc, hit, float2{e[3], e[4]}, e[5], ls, pLight)) continue;
+    o[0] = 1u;
+    o[1] = bits(ls.Li.x); o[2] = bits(ls.Li.y); o[3] = bits(ls.Li.z);
+    o[4] = bits(ls.wi.x); o[5] = bits(ls.wi.y); o[6] = bits(ls.wi.z);
+    o[7] = bits(ls.pdf); o[8] = bits(pLight);
+    o[9] = bits(length(ls.pos - hit.pos));   // the shadow ray's reach before its 1e-3 margin (kernel.metal:623)
+  }
+}
+// PT_LIGHT_ENV_MISS: in 4 floats (direction, lastPdf), out 4 floats (the radiance for attenuation 1, 0).  Needs an environment.
+int orc_env_miss(const orc_scene* sc, uint32_t n, const pt_light_probe_args* args, const void* in_, void* out_) {
+  if (sc->env_texture < 0) return -1;
+  const float* in = (const float*)in_;
+  float* out = (float*)out_;
+  for (uint32_t i = 0; i < n; i++) {
+    const float* e = in + (size_t)i * PT_LIGHT_ENV_MISS_IN_WORDS;
+    const float3 L = missRadiance(*sc, f3(e[0], e[1], e[2]), f3(1.0f), args->bounce, e[3], args->lastSpecular != 0);
+    float* o = out + (size_t)i * PT_LIGHT_ENV_MISS_OUT_WORDS;
+    o[0] = L.x; o[1] = L.y; o[2] = L.z; o[3] = 0.0f;
+  }
+  return 0;
 }
 // ---- LUT generator restatement (pins A7-A9 against reference-held data) -------------------------------------------------
 // The eight energy tables the renderer loads (resource/lut/*.exr -> platinum_amd/data/ggx_luts.bin) are Monte-Carlo integrals

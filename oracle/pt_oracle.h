@@ -61,6 +61,10 @@ float orc_lut_texel(const orc_scene* sc, int which, int x, int y, int z);
 void orc_bsdf_sample(const orc_scene* sc, const pt_material_gpu* mat, const float wo[3], const float r[4], const float rc[2],
                      float out_sample[11]);
 void orc_bsdf_eval(const orc_scene* sc, const pt_material_gpu* mat, const float wo[3], const float wi[3], float out_eval[4]);
+// The twins of pt_debug_lights (include/ptamd.h): PT_LIGHT_SAMPLE and PT_LIGHT_ENV_MISS records in and out, through the oracle's own
+// sampleLightPower, sampleAreaLight, sampleEnvironmentLight and miss branch.  orc_env_miss returns -1 for a scene without an environment.
+void orc_light_sample(const orc_scene* sc, uint32_t n, const pt_light_probe_args* args, const void* in, void* out);
+int orc_env_miss(const orc_scene* sc, uint32_t n, const pt_light_probe_args* args, const void* in, void* out);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,14 @@ PT_ABI_VERSION = 5
 (PT_MATH_SINCOS, PT_MATH_COS, PT_MATH_ATAN2, PT_MATH_ACOS, PT_MATH_LOG2, PT_MATH_EXP2, PT_MATH_POWR, PT_MATH_PP_LOG2, PT_MATH_PP_EXP2,
  PT_MATH_PP_EXP2S, PT_MATH_PP_POWR, PT_MATH_DN_EXP2, PT_MATH_DN_POWR, PT_MATH_SAMPLE_DISK, PT_MATH_SAMPLE_COSINE_HEMISPHERE,
  PT_MATH_SAMPLE_TRI_UNIFORM, PT_MATH_HALTON, PT_MATH_HALTON_OFFSET, PT_MATH_BOKEH_POWR, PT_MATH_COUNT) = range(20)
+# pt_debug_lights' functions, tables and record sizes in 4-byte words (include/ptamd.h PT_LIGHT_*)
+PT_LIGHT_SAMPLE, PT_LIGHT_ENV_MISS, PT_LIGHT_COUNT = range(3)
+PT_LIGHT_TABLES_HBM, PT_LIGHT_TABLES_LDS = 0, 1
+PT_LIGHT_IN_WORDS = {PT_LIGHT_SAMPLE: 8, PT_LIGHT_ENV_MISS: 4}
+PT_LIGHT_OUT_WORDS = {PT_LIGHT_SAMPLE: 12, PT_LIGHT_ENV_MISS: 4}
+# numpy views of pt_debug_lights' result records
+LIGHT_SAMPLE_DTYPE = [("lit", "u4"), ("Li", "f4", 3), ("lwi", "f4", 3), ("lpdf", "f4"), ("pLight", "f4"), ("dist", "f4"), ("dim", "u4"), ("_pad", "u4")]
+ENV_MISS_DTYPE = [("L", "f4", 3), ("_pad", "u4")]
 
 # renderer_pt.hpp:21-26
 STATUS_BLOCKED, STATUS_READY, STATUS_BUSY, STATUS_DONE = 0, 1, 4, 8
@@ -207,6 +215,12 @@ class BloomOptions(C.Structure):
 BLOOM_MAX_LEVELS = 12
 
 
+class LightProbeArgs(C.Structure):
+    """pt_light_probe_args: the per-call arguments of pt_debug_lights."""
+    _fields_ = [("roughness", C.c_float), ("metallic", C.c_float), ("transmission", C.c_float), ("dim", C.c_uint32), ("tables", C.c_uint32),
+                ("bounce", C.c_uint32), ("lastSpecular", C.c_uint32)]
+
+
 class BloomPlan(C.Structure):
     """pt_bloom_plan: the levels of the bloom pyramid ([0] is the frame) and where each starts in the pyramid buffer."""
     _fields_ = [("levels", C.c_uint32), ("total_texels", C.c_uint32),
@@ -366,6 +380,7 @@ SYMBOLS = [
     ("pt_debug_exposure", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(ExposureOptions),
                                     C.POINTER(ExposureMeter), C.c_void_p]),
     ("pt_debug_math", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pt_debug_lights", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(LightProbeArgs), C.c_void_p, C.c_void_p]),
     ("pt_default_bloom_options", None, [C.POINTER(BloomOptions)]),
     ("pt_set_bloom_options", C.c_int, [C.c_void_p, C.POINTER(BloomOptions)]),
     ("pt_plan_bloom", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(BloomPlan)]),

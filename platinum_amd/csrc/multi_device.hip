@@ -728,6 +728,11 @@ int pt_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const 
   return dev_debug_math(is_group(r) ? r->group->shards[0] : r, fn, n, a, b, out0, out1);
 }
 
+// every member of a group holds the whole scene: the first one answers
+int pt_debug_lights(pt_renderer* r, uint32_t fn, uint32_t n, const pt_light_probe_args* args, const void* in, void* out) {
+  return dev_debug_lights(is_group(r) ? r->group->shards[0] : r, fn, n, args, in, out);
+}
+
 // Bloom: as auto exposure, every member holds the options and the member that displays the merged image does the work.
 int pt_set_bloom_options(pt_renderer* r, const pt_bloom_options* o) { return on_members(r, dev_set_bloom_options, o); }
 

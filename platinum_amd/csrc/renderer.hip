@@ -25,6 +25,8 @@
 #include "queue_plan.h"
 #include "runtime_identity.h"
 #include "renderer_state.h"
+#include "light_probe.h"
+#include "pt_light_probe.h"
 
 using namespace pt;
 
@@ -982,6 +984,43 @@ int dev_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const
   PT_HIP(hipStreamSynchronize(r->stream));
   PT_HIP(hipMemcpy(out0, d0.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
   if (writes_1) PT_HIP(hipMemcpy(out1, d1.p, sizeof(uint32_t) * n1, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+// one elementwise launch of light_probe.hip on uploaded records against the started render's scene table; the render's state is untouched.
+// The draws and directions are checked on the host first: shade_nee_light and stage_miss index tables with them, and a draw outside [0, 1)
+// (a NaN too) would walk the light search or the alias table out of bounds.
+int dev_debug_lights(pt_renderer* r, uint32_t fn, uint32_t n, const pt_light_probe_args* args, const void* in, void* out) {
+  if (fn >= PT_LIGHT_COUNT) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_lights: unknown function");
+  if (n == 0 || n > (1u << 24)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_lights: n must be 1..2^24");
+  if (!args || !in || !out) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_lights: null argument");
+  if (fn == PT_LIGHT_SAMPLE && args->tables != PT_LIGHT_TABLES_HBM && args->tables != PT_LIGHT_TABLES_LDS)
+    return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_lights: tables must be PT_LIGHT_TABLES_HBM or PT_LIGHT_TABLES_LDS");
+  if (fn == PT_LIGHT_SAMPLE && args->dim > kMetaDimMask) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_lights: dim must fit a path's cursor (0..1023)");
+  const uint32_t wi = light_probe_in_words(fn), wo = light_probe_out_words(fn);
+  const float* f = (const float*)in;
+  for (size_t i = 0; i < n; i++) {
+    const float* e = f + i * wi;
+    if (fn == PT_LIGHT_SAMPLE) {
+      for (int k = 3; k < 6; k++)
+        if (!(e[k] >= 0.0f && e[k] < 1.0f)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_lights: a draw lies outside [0, 1)");
+    } else {
+      for (int k = 0; k < 3; k++)
+        if (!(e[k] >= -1.0f && e[k] <= 1.0f)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_lights: a direction component lies outside [-1, 1]");
+    }
+  }
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_lights: null renderer");
+  if (!r->started) return fail(PT_ERR_BAD_STATE, "pt_debug_lights before pt_start_render");
+  if (const char* why = light_probe_unsupported(r->S, fn, *args, kLightProbeStaged)) return fail(PT_ERR_UNSUPPORTED, why);
+  PT_HIP(hipSetDevice(r->device));
+  DevBuf<float> din;
+  DevBuf<uint32_t> dout;
+  PT_HIP(din.alloc((size_t)n * wi)); PT_HIP(dout.alloc((size_t)n * wo));
+  PT_HIP(hipMemcpyAsync(din.p, in, sizeof(float) * (size_t)n * wi, hipMemcpyHostToDevice, r->stream));
+  launch_light_probe(r->stream, r->scene_d.p, fn, n, *args, din.p, dout.p);
+  PT_HIP(hipGetLastError());
+  PT_HIP(hipStreamSynchronize(r->stream));
+  PT_HIP(hipMemcpy(out, dout.p, sizeof(uint32_t) * (size_t)n * wo, hipMemcpyDeviceToHost));
   return PT_OK;
 }
 

@@ -244,6 +244,23 @@ class Renderer:
                                                      None if out1 is None else out1.ctypes.data))
         return out0, out1
 
+    def debugLights(self, fn, records, roughness=1.0, metallic=0.0, transmission=0.0, dim=0, tables=abi.PT_LIGHT_TABLES_HBM, bounce=1,
+                    lastSpecular=False):
+        """pt_debug_lights on the scene of the started render.  fn = abi.PT_LIGHT_SAMPLE: `records` is (n, 6) float32, a hit position and the
+        three NEE draws (rl.x, rl.y, rz); returns n records of abi.LIGHT_SAMPLE_DTYPE, shade_nee_light for a material with the given roughness /
+        metallic / transmission at sampler cursor `dim`, its light table in HBM or staged in LDS (`tables`).  fn = abi.PT_LIGHT_ENV_MISS:
+        `records` is (n, 4), a direction and lastPdf; returns n records of abi.ENV_MISS_DTYPE, stage_miss with attenuation 1 at `bounce`."""
+        rec = np.ascontiguousarray(records, dtype=np.float32)
+        wi, wo = abi.PT_LIGHT_IN_WORDS[fn], abi.PT_LIGHT_OUT_WORDS[fn]
+        assert rec.ndim == 2 and rec.shape[1] == (6 if fn == abi.PT_LIGHT_SAMPLE else 4)
+        n = rec.shape[0]
+        buf = np.zeros((n, wi), np.float32)
+        buf[:, :rec.shape[1]] = rec
+        out = np.empty(n * wo, np.uint32)
+        args = abi.LightProbeArgs(roughness, metallic, transmission, dim, tables, bounce, 1 if lastSpecular else 0)
+        abi.check(self._lib, self._lib.pt_debug_lights(self._h, fn, n, C.byref(args), buf.ctypes.data, out.ctypes.data))
+        return out.view(abi.LIGHT_SAMPLE_DTYPE if fn == abi.PT_LIGHT_SAMPLE else abi.ENV_MISS_DTYPE)
+
     # bloom (include/ptamd.h, an additive extension of ABI 5): no reference counterpart
     def bloomOptions(self):
         """The options in effect (pt_default_bloom_options until setBloomOptions is called)."""

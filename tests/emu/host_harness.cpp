@@ -9,4 +9,5 @@
 #include "region_emu.cpp"     // rg_*:  pt_render_region's layout, the rectangle test
 #include "layout_probe.cpp"   // lp_*:  the tile / segment / radiance-buffer index maps, plan_queues
 #include "math_emu.cpp"       // emu_math_batch: the math layer as pt_debug_math evaluates it
+#include "light_emu.cpp"      // emu_light_probe: the light sampling as pt_debug_lights evaluates it
 #include "start_plan_probe.cpp"  // sp_*: the decisions of pt_start_render (host_scene.h): structure, camera lists, queue budget

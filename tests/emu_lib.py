@@ -32,9 +32,17 @@ def bind(L):
     return L
 
 
+def bind_lights(L):
+    """The functions of tests/emu/light_emu.cpp, which only the whole harness holds."""
+    L.emu_light_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(abi.LightProbeArgs), C.c_void_p, C.c_void_p]
+    L.emu_get_env_alias.restype = C.c_uint64
+    L.emu_get_env_alias.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    return L
+
+
 @functools.lru_cache(maxsize=None)
 def lib():
-    return bind(host_build.load())
+    return bind_lights(bind(host_build.load()))
 
 
 class EmuScene:
@@ -63,6 +71,22 @@ class EmuScene:
         arr = (abi.AreaLight * 65536)()
         n = self.L.emu_get_lights(self.h, arr, 65536)
         return list(arr)[:n]
+
+    def envAlias(self):
+        n = self.L.emu_get_env_alias(self.h, None, 0)
+        arr = np.zeros(n, dtype=abi.ALIAS_DTYPE)
+        if n:
+            self.L.emu_get_env_alias(self.h, arr.ctypes.data, n)
+        return arr
+
+    def debugLights(self, fn, records, **args):
+        """emu_light_probe, the host build of pt_light_probe.h: Renderer.debugLights' arguments and result (light_lib.probe)"""
+        import light_lib
+
+        def call(n, a, i, o):
+            if self.L.emu_light_probe(self.h, fn, n, a, i, o) != 0:
+                raise RuntimeError("emu_light_probe refused the call")
+        return light_lib.probe(call, fn, records, **args)
 
     def debug_sample(self, sample_idx):
         B = self.params.max_bounces

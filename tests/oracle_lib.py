@@ -104,6 +104,9 @@ def lib():
     L.orc_lut_texel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
     L.orc_bsdf_sample.argtypes = [C.c_void_p, C.POINTER(abi.MaterialGPU), C.c_float * 3, C.c_float * 4, C.c_float * 2, C.c_float * 11]
     L.orc_bsdf_eval.argtypes = [C.c_void_p, C.POINTER(abi.MaterialGPU), C.c_float * 3, C.c_float * 3, C.c_float * 4]
+    L.orc_light_sample.restype = None
+    L.orc_light_sample.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(abi.LightProbeArgs), C.c_void_p, C.c_void_p]
+    L.orc_env_miss.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(abi.LightProbeArgs), C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -158,6 +161,12 @@ class OracleScene:
         if n.value:
             self.L.orc_get_env_alias(self.h, arr.ctypes.data, n.value, C.byref(n))
         return arr
+
+    def debugLights(self, fn, records, **args):
+        """orc_light_sample / orc_env_miss: Renderer.debugLights' arguments and result (light_lib.probe)"""
+        import light_lib
+        return light_lib.probe(lambda n, a, i, o: (self.L.orc_light_sample if fn == abi.PT_LIGHT_SAMPLE else self.L.orc_env_miss)(self.h, n, a, i, o),
+                               fn, records, **args)
 
     def render(self, first_sample, nsamples, acc=None, acc_n0=0, threads=None, count_traversal=False):
         if acc is None:
