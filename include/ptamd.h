@@ -875,6 +875,45 @@ int pt_get_camera_projection(pt_renderer* r, pt_camera_projection* out);
  * pointer may be NULL.  Full-frame like pt_trace_primary; blocks.  PT_ERR_BAD_STATE before pt_start_render. */
 int pt_debug_camera_rays(pt_renderer* r, uint32_t sample_idx, float* origins /* W*H*3 */, float* directions /* W*H*3 */);
 
+/* ---- ambient occlusion (NEW, an additive extension of ABI 5: new entry points and new structs, no existing struct changed) ----
+ * A render started while `enabled` is set traces, for every camera ray that hit geometry, ONE more ray from the hit and keeps per pixel two
+ * integers: `hits`, the camera rays of the pixel's samples that hit, and `open`, those of them whose AO ray met nothing.  The AO ray:
+ *   origin     o + d * t of the camera ray and its first hit, in fp32 (the point shading starts from)
+ *   normal     the hit triangle's world-space GEOMETRIC normal normalize(M * n) through the instance's forward matrix (the reference's
+ *              definition: under a non-uniform scale it is not the true normal), turned to face the viewer: -n when dot(n, d) > 0
+ *   direction  cosine-weighted about that normal, from a Halton stream of AO's own: index pcg4d(offset, salt, 0, 0).x of the path's
+ *              offset, dimensions 0-1 (dimension 2: the alpha-test draw of a scene with cut-outs).  No draw of the path itself moves.
+ *   range      [1e-3, distance], any hit; cut-outs are tested as for shadow rays.  distance = +inf is allowed.
+ * pt_read_ao gives open / hits per pixel (1 where hits = 0).  The counts are integers: they do not depend on samples_in_flight, on the
+ * sequence of pt_render_step calls or on the queue layout.  A region render leaves {0, 0} (AO 1) outside the rectangle; an adaptive
+ * render's tile holds the counts of its own samples.  Thin-lens and projected cameras work as ever (the origin is the queue's).  Every other
+ * output of the render, pt_stats' ray counters included, is the bits it is without AO; the AO trace and fold are timed on their own
+ * (pt_ao_stats), not in pt_stats' classes.  There is no AO pass view.
+ * Memory: 4 B per path slot and 8 B per pixel, held only by a render that enabled AO.
+ * PT_ERR_INVALID_ARGUMENT (checked before the renderer): enabled > 1, a distance that is NaN or <= 0.  PT_ERR_UNSUPPORTED: enabled = 1, the
+ * reads and pt_debug_ao on a device group. */
+typedef struct pt_ao_options {
+  uint32_t enabled;    /* keep AO for renders started from now on (read at pt_start_render); default 0 */
+  float distance;      /* the AO rays' far limit in world units, > 0, +inf allowed; default 1 */
+  uint32_t _pad[2];
+} pt_ao_options;
+void pt_default_ao_options(pt_ao_options* o);
+int pt_set_ao_options(pt_renderer* r, const pt_ao_options* o);
+/* open / hits per pixel, W*H floats.  Blocks like pt_read_aov.  PT_ERR_BAD_STATE before pt_start_render and for a render started without AO. */
+int pt_read_ao(pt_renderer* r, float* out /* W*H */);
+/* {hits, open} per pixel, W*H*2 words.  Blocks; errors as pt_read_ao. */
+int pt_read_ao_counts(pt_renderer* r, uint32_t* out /* W*H*2 */);
+/* One sample of every pixel in pixel order: the batch pt_trace_primary runs, then the AO trace of a render batch, which also logs its rays.
+ * state: 0 the camera ray missed (origin and direction 0), 1 hit and AO ray occluded, 2 hit and AO ray unoccluded.  Any pointer may be
+ * NULL.  Full-frame; blocks; leaves the render's accumulated state alone.  Errors as pt_read_ao. */
+int pt_debug_ao(pt_renderer* r, uint32_t sample_idx, float* origins /* W*H*3 */, float* directions /* W*H*3 */, uint32_t* state /* W*H */);
+typedef struct pt_ao_stats {
+  uint64_t rays;             /* AO rays traced since pt_start_render (= the sum of hits over the frame) */
+  float ms_trace, ms_fold;   /* device time of the AO trace / the AO fold since pt_start_render, under pt_set_profiling */
+} pt_ao_stats;
+/* Blocks (it sums the counts).  Errors as pt_read_ao. */
+int pt_get_ao_stats(pt_renderer* r, pt_ao_stats* out);
+
 const char* pt_last_error(void);
 
 /* ---------------------------------------------------------------------------------------------------------- */

@@ -55,6 +55,10 @@
  *   (no counterpart; "film transparent" of other path tracers)   pt_film_options& filmOptions() / setFilmOptions(...), readbackFilm(): the foreground
  *                                                                with alpha, and the backdrop a target shows behind it (ptamd.h, ABI 5 extension);
  *                                                                `enabled` is handed over at startRender, the backdrop whenever a target is asked for
+ *   (no counterpart; the "ambient occlusion" pass of a compositor) pt_ao_options& ambientOcclusionOptions() / setAmbientOcclusionOptions(...),
+ *                                                                readbackAmbientOcclusion(), readbackAmbientOcclusionCounts(), debugAmbientOcclusion():
+ *                                                                one occlusion ray from every camera ray's first hit (ptamd.h, ABI 5 extension);
+ *                                                                handed over at startRender
  *   (no counterpart; the camera type of a scene editor)           pt_camera_projection& projection() / setProjection(...), renderProjection(): orthographic,
  *                                                                panoramic and fisheye cameras beside the perspective one (ptamd.h, ABI 5 extension);
  *                                                                handed over at startRender
@@ -139,6 +143,7 @@ public:
     if (!check(pt_set_matte_options(m_pt, &m_matte))) return;        // (read here)
     if (!check(pt_set_film_options(m_pt, &m_film))) return;          // (`enabled` is read here)
     if (!check(pt_set_camera_projection(m_pt, &m_projection))) return;   // (read here)
+    if (!check(pt_set_ao_options(m_pt, &m_ao))) return;              // (read here)
     if (!check(pt_start_render(m_pt, &scene, &p))) return;
     m_size = uint2{p.width, p.height};
     m_started = true;
@@ -327,6 +332,38 @@ public:
     if (!check(pt_read_film(m_pt, out.data()))) out.clear();
     return out;
   }
+  // Ambient occlusion (ptamd.h, an additive extension of ABI 5): a render started with enabled set traces one cosine-weighted occlusion ray of
+  // at most `distance` from every camera ray's first hit and keeps per pixel how many camera rays hit and how many of their AO rays were open.
+  // Edited in place like filmOptions(); read at startRender.
+  [[nodiscard]] constexpr pt_ao_options& ambientOcclusionOptions() { return m_ao; }
+  void setAmbientOcclusionOptions(const pt_ao_options& o) { m_ao = o; }
+  // open / hits per pixel, W*H floats (1 where no camera ray hit); empty for a render started without AO.  Blocks.
+  [[nodiscard]] std::vector<float> readbackAmbientOcclusion() const {
+    std::vector<float> out;
+    if (!m_pt || !m_started) return out;
+    out.resize((size_t)m_size.x * m_size.y);
+    if (!check(pt_read_ao(m_pt, out.data()))) out.clear();
+    return out;
+  }
+  // {hits, open} per pixel, W*H*2 words; empty for a render started without AO.  Blocks.
+  [[nodiscard]] std::vector<uint32_t> readbackAmbientOcclusionCounts() const {
+    std::vector<uint32_t> out;
+    if (!m_pt || !m_started) return out;
+    out.resize((size_t)m_size.x * m_size.y * 2);
+    if (!check(pt_read_ao_counts(m_pt, out.data()))) out.clear();
+    return out;
+  }
+  // The AO rays of one sample of every pixel, in pixel order: origins and directions (W*H*3 floats each) and the state per camera ray
+  // (0 missed, 1 occluded, 2 open).  false, with the vectors empty, for a render started without AO.  Blocks.
+  bool debugAmbientOcclusion(uint32_t sampleIdx, std::vector<float>& origins, std::vector<float>& directions, std::vector<uint32_t>& state) const {
+    origins.clear(); directions.clear(); state.clear();
+    if (!m_pt || !m_started) return false;
+    const size_t n = (size_t)m_size.x * m_size.y;
+    origins.resize(3 * n); directions.resize(3 * n); state.resize(n);
+    if (check(pt_debug_ao(m_pt, sampleIdx, origins.data(), directions.data(), state.data()))) return true;
+    origins.clear(); directions.clear(); state.clear();
+    return false;
+  }
   // Pass views (ptamd.h, an additive extension of ABI 5): `view` chooses what presentRenderTarget / readbackRenderTarget show: the beauty,
   // or the albedo, the normals, the depth, the film's alpha, the ID mattes, the sample counts or the noise estimate the render keeps.  A view
   // whose data the render does not keep silently shows the beauty.  Edited in place like bloomOptions(); read whenever a target is asked for.
@@ -357,6 +394,7 @@ private:
     pt_default_matte_options(&m_matte);
     pt_default_selection_options(&m_selection);
     pt_default_film_options(&m_film);
+    pt_default_ao_options(&m_ao);
     pt_default_view_options(&m_view);
     pt_default_camera_projection(&m_projection);
     std::vector<int32_t> ord(devices, devices + count);
@@ -410,6 +448,7 @@ private:
   pt_matte_options m_matte{};
   pt_selection_options m_selection{};
   pt_film_options m_film{};
+  pt_ao_options m_ao{};
   pt_view_options m_view{};
   pt_camera_projection m_projection{};
   mutable void* m_presentStream = nullptr;

@@ -280,6 +280,18 @@ class FilmOptions(C.Structure):
     _fields_ = [("enabled", C.c_uint32), ("backdrop", C.c_uint32), ("backdrop_rgb", C.c_float * 3)]
 
 
+class AoOptions(C.Structure):
+    """pt_ao_options: the ambient-occlusion pass (`enabled` and `distance`, read at pt_start_render)."""
+    _fields_ = [("enabled", C.c_uint32), ("distance", C.c_float), ("_pad", C.c_uint32 * 2)]
+
+
+class AoStats(C.Structure):
+    """pt_ao_stats: AO rays traced since pt_start_render, and the device time of the AO trace and fold under profiling."""
+    _fields_ = [("rays", C.c_uint64), ("ms_trace", C.c_float), ("ms_fold", C.c_float)]
+
+
+AO_MISS, AO_OCCLUDED, AO_OPEN = 0, 1, 2   # pt_debug_ao's state per camera ray
+
 PROJ_PERSPECTIVE, PROJ_ORTHOGRAPHIC, PROJ_EQUIRECT, PROJ_FISHEYE = range(4)
 PROJ_NAMES = ("perspective", "ortho", "equirect", "fisheye")
 
@@ -414,6 +426,12 @@ SYMBOLS = [
     ("pt_set_camera_projection", C.c_int, [C.c_void_p, C.POINTER(CameraProjection)]),
     ("pt_get_camera_projection", C.c_int, [C.c_void_p, C.POINTER(CameraProjection)]),
     ("pt_debug_camera_rays", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("pt_default_ao_options", None, [C.POINTER(AoOptions)]),
+    ("pt_set_ao_options", C.c_int, [C.c_void_p, C.POINTER(AoOptions)]),
+    ("pt_read_ao", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("pt_read_ao_counts", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("pt_debug_ao", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pt_get_ao_stats", C.c_int, [C.c_void_p, C.POINTER(AoStats)]),
     ("pt_last_error", C.c_char_p, []),
     ("pt_get_constants", C.c_int, [C.c_void_p, C.POINTER(Constants)]),
     ("pt_get_lights", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),

@@ -485,13 +485,13 @@ inline bool camera_lists_fit(uint64_t bytes, uint64_t free_bytes, uint64_t lists
 // What plan_queues may count on (0: unknown).  What the previous render's queues occupy is reused, i.e. available.  The camera-ray lists were
 // taken first; the queues are planned as if they had not been — a quarter of the free memory is the queues' budget, and a render sizes its
 // batches the same with and without lists.  AOVs add 32 B per path slot (Abuf) to the ~200 B of queue state the automatic choice assumes,
-// ID mattes 8 B (Mbuf), the film 4 B (Fbuf).
+// ID mattes 8 B (Mbuf), the film 4 B (Fbuf), ambient occlusion 4 B (Obuf).
 inline uint64_t queue_budget(uint64_t free_bytes, uint64_t queues_held, uint64_t lists_held, bool aov, uint64_t abuf_held, bool matte = false,
-                             uint64_t mbuf_held = 0, bool film = false, uint64_t fbuf_held = 0) {
+                             uint64_t mbuf_held = 0, bool film = false, uint64_t fbuf_held = 0, bool ao = false, uint64_t obuf_held = 0) {
   if (free_bytes == 0) return 0;
   const uint64_t b = free_bytes + queues_held + lists_held;
-  const uint64_t extra = (aov ? 32u : 0u) + (matte ? 8u : 0u) + (film ? 4u : 0u);
-  return extra ? (b + (aov ? abuf_held : 0u) + (matte ? mbuf_held : 0u) + (film ? fbuf_held : 0u)) / (200u + extra) * 200u : b;
+  const uint64_t extra = (aov ? 32u : 0u) + (matte ? 8u : 0u) + (film ? 4u : 0u) + (ao ? 4u : 0u);
+  return extra ? (b + (aov ? abuf_held : 0u) + (matte ? mbuf_held : 0u) + (film ? fbuf_held : 0u) + (ao ? obuf_held : 0u)) / (200u + extra) * 200u : b;
 }
 
 }  // namespace pt

@@ -73,6 +73,12 @@ void launch_shade(hipStream_t s, uint32_t grid, const DeviceScene* S_device, Pat
                   ShadowQueue sq, vec4* Lbuf, Segments seg, uint32_t cur, BatchCounters* ctr, uint32_t bounce);
 void launch_trace_shadow(hipStream_t s, uint32_t grid, const DeviceScene& S, ShadowQueue sq, vec4* Lbuf, Segments seg,
                          BatchCounters* ctr, uint32_t bounce, uint32_t* spill, bool count);
+// The AO trace of a render batch (k_trace_ao, pt_ao.h): one any-hit ray of at most `distance` per camera ray of the bounce-0 queue, between the
+// camera trace (and its table pass) and k_shade(0); Obuf[pid] = 0 camera miss, 1 occluded, 2 open.  `grid_closest`: the closest-hit
+// kernel's persistent grid, whose occupancy the kernel is built for.  raylog (may be null; one-sample batches): 2 * 3 * log_stride floats, the AO rays'
+// origins then directions in pixel order.
+void launch_trace_ao(hipStream_t s, uint32_t grid_closest, const DeviceScene& S, PathState st, const vec4* hit, Segments seg, BatchCounters* ctr,
+                     uint32_t* spill, uint32_t* Obuf, float distance, float* raylog, uint32_t log_stride);
 // Over a tile set it also folds the per-pixel running means of (lum, lum^2) into `mom` (unless null) and writes n0 + nsamples to
 // tile_n[image tile]; a full-frame batch reads neither.
 void launch_accumulate(hipStream_t s, vec4* acc, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,

@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "pt_ao.h"
 #include "pt_camlist.h"
 #include "pt_denoise.h"
 #include "pt_post.h"
@@ -946,6 +947,49 @@ k_trace_shadow(DeviceScene S, ShadowQueue sq, vec4* __restrict__ Lbuf, Segments 
                                 &ctr->tris_shadow, begin, finish);
 }
 
+// ---- ambient occlusion (any hit; pt_ao.h) ---------------------------------------------------------------------------------
+// One AO ray per camera ray, between the camera trace of a render batch and k_shade(0): a consumer of the bounce-0 queue over the shared ray
+// loop.  It claims the chunks of bounce 0's closest-hit table (which every branch of the camera trace leaves behind) on a cursor of its own:
+// bounces stop at 50 and kUnlistedCursor is 63.  begin reads the queue entry and its hit record: a camera miss writes state 0 and drops
+// the ray, a hit becomes stage_ao's ray; finish writes 1 (occluded) or 2 (open).  Reads the queue only, writes Obuf[pid] only (pid as
+// walk_bounce0 forms it).  `raylog` (pt_debug_ao, one-sample batches): the AO rays in pixel order, origins then directions log_stride
+// pixels apart.  Built and launched at the closest-hit kernel's occupancy: with stage_ao fused into begin it needs that kernel's 80 VGPRs (at the
+// shadow kernel's 72 it spilled 10 of them; tests/test_ao_kernel_resources.py holds the bound and the report to each other).
+constexpr uint32_t kAoCursor = 62;
+template <class W>
+__global__ void __launch_bounds__(W::kThreads, W::kClosestBlocksPerCu)
+k_trace_ao(DeviceScene S, PathState st, const vec4* __restrict__ hit, Segments seg, BatchCounters* __restrict__ ctr, uint32_t* __restrict__ spill,
+           uint32_t* __restrict__ Obuf, float tmax, float* __restrict__ raylog, uint32_t log_stride) {
+  uint32_t pid = 0;
+  auto begin = [&](uint32_t& ray, TravState& ts, const TraversalStack& stack, TraversalCount* tc) {
+    const vec4 d4 = st.rayD[ray];
+    const vec4 h4 = hit[ray];
+    pid = segment_lbuf_base(seg, slot_segment(seg.nseg, ray)) + (f2u(d4.w) >> kMetaPidShift);
+    if (hit_word_miss(f2u(h4.w))) {
+      Obuf[pid] = kAoMiss;
+      ray = kInvalidRef;
+      return false;
+    }
+    const vec4 o4 = st.rayO[ray];
+    const AoRay a = stage_ao(S, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), h4.x, f2u(h4.w), f2u(st.att[ray].w));
+    if (raylog) {
+      const size_t p = 3 * (size_t)pixel_of_pid_1spp(pid, S.width);
+      float* o = raylog + p;
+      float* d = raylog + 3 * (size_t)log_stride + p;
+      o[0] = a.o.x; o[1] = a.o.y; o[2] = a.o.z;
+      d[0] = a.d.x; d[1] = a.d.y; d[2] = a.d.z;
+    }
+    return trav_init(S, ts, a.o, a.d, kAoTmin, tmax, a.payload, stack, true, tc);
+  };
+  auto finish = [&](uint32_t& ray, TravState& ts) {
+    Obuf[pid] = ts.best.tri == kInvalidRef ? kAoOpen : kAoOccluded;
+    ray = kInvalidRef;
+  };
+  // (`bounce` only names the tail probe's row: there is none for this launch)
+  trace_rays<W, true, false, 2>(S, seg, seg.table_closest, ctr->chunks_closest[0], &ctr->work_closest[kAoCursor], spill, ctr, kAoCursor, nullptr, nullptr,
+                                begin, finish);
+}
+
 // ---- accumulate (kernel.metal:672-684): running mean, one sample at a time, in sample order --------------------------
 // One wave per 8x8 tile (pt_tilefold.h: fold_tile places it, fold_stage turns eight samples of its 64 pixels through LDS per round); every
 // lane then folds the samples of ITS pixel in sample order — the running mean is a sequential recurrence per pixel (kernel.metal:672-684).
@@ -1234,6 +1278,13 @@ void launch_trace_shadow(hipStream_t s, uint32_t grid, const DeviceScene& S, Sha
   launch_walk(S, count, [&](auto walk, auto counted) {
     using W = decltype(walk);
     hipLaunchKernelGGL((k_trace_shadow<W, decltype(counted)::value>), dim3(grid), dim3(W::kThreads), 0, s, S, sq, Lbuf, seg, ctr, bounce, spill);
+  });
+}
+void launch_trace_ao(hipStream_t s, uint32_t grid_closest, const DeviceScene& S, PathState st, const vec4* hit, Segments seg, BatchCounters* ctr,
+                     uint32_t* spill, uint32_t* Obuf, float distance, float* raylog, uint32_t log_stride) {
+  launch_walk(S, false, [&](auto walk, auto) {
+    using W = decltype(walk);
+    hipLaunchKernelGGL((k_trace_ao<W>), dim3(grid_closest), dim3(W::kThreads), 0, s, S, st, hit, seg, ctr, spill, Obuf, distance, raylog, log_stride);
   });
 }
 void launch_accumulate(hipStream_t s, vec4* acc, const vec4* Lbuf, uint32_t npixels, uint32_t width, uint32_t nsamples, uint32_t n0,

@@ -804,6 +804,32 @@ int pt_read_film(pt_renderer* r, float* rgba_out) {
   return fail(PT_ERR_BAD_STATE, "pt_read_film: a device group does not keep a film");
 }
 
+// Ambient occlusion is per device as well: a group merges accumulators only
+int pt_set_ao_options(pt_renderer* r, const pt_ao_options* o) {
+  if (o) if (const char* why = ao_options_error(*o)) return fail(PT_ERR_INVALID_ARGUMENT, std::string("pt_set_ao_options: ") + why);
+  return set_unless_enabled(r, dev_set_ao_options, o, "pt_set_ao_options: a device group does not keep ambient occlusion");
+}
+
+int pt_read_ao(pt_renderer* r, float* out) {
+  if (!is_group(r)) return dev_read_ao(r, out);
+  return fail(PT_ERR_UNSUPPORTED, "pt_read_ao: a device group does not keep ambient occlusion");
+}
+
+int pt_read_ao_counts(pt_renderer* r, uint32_t* out) {
+  if (!is_group(r)) return dev_read_ao_counts(r, out);
+  return fail(PT_ERR_UNSUPPORTED, "pt_read_ao_counts: a device group does not keep ambient occlusion");
+}
+
+int pt_debug_ao(pt_renderer* r, uint32_t sample_idx, float* origins, float* directions, uint32_t* state) {
+  if (!is_group(r)) return dev_debug_ao(r, sample_idx, origins, directions, state);
+  return fail(PT_ERR_UNSUPPORTED, "pt_debug_ao: a device group does not keep ambient occlusion");
+}
+
+int pt_get_ao_stats(pt_renderer* r, pt_ao_stats* out) {
+  if (!is_group(r)) return dev_get_ao_stats(r, out);
+  return fail(PT_ERR_UNSUPPORTED, "pt_get_ao_stats: a device group does not keep ambient occlusion");
+}
+
 // A group's members would all render the same projection, but its checks (merged image against the single-device render) cover the
 // perspective camera only: any other kind is refused, as AOVs are.  The options are checked first, as on a single device.
 int pt_set_camera_projection(pt_renderer* r, const pt_camera_projection* p) {

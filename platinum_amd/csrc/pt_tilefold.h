@@ -1,7 +1,9 @@
 // pt_tilefold.h — what every per-sample side channel of a batch shares, defined ONCE (DESIGN.md §3 "Tile folds and queue walks"): how a
 // fold kernel places its tile in the image, the order in which a round of eight samples goes through LDS, and the walk over a segment of the
-// bounce-0 queue that fills a side channel.  kernels.hip (Lbuf), denoise.hip (Abuf), matte.hip (Mbuf) and film.hip (Fbuf) call it; a new side channel starts
-// here.  The first two are plain integer functions (PT_HD) that tests/emu also compiles for the host; the walk is device code.
+// bounce-0 queue that fills a side channel.  kernels.hip (Lbuf), denoise.hip (Abuf), matte.hip (Mbuf), film.hip (Fbuf) and ao.hip (Obuf) call it; a new
+// side channel starts here.  One that needs a trace of its own (Obuf: ambient occlusion, pt_ao.h) is filled by a consumer of the bounce-0 chunk
+// table over the trace kernels' ray loop instead of the walk (k_trace_ao, kernels.hip), forms its pid as the walk does, and folds like the
+// others.  The first two are plain integer functions (PT_HD) that tests/emu also compiles for the host; the walk is device code.
 #pragma once
 #include "pt_device.h"
 #include "pt_layout.h"

@@ -160,6 +160,11 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
       ScopedTimer t(r, K_ACCUM);
       launch_film_flags(s, r->grid, r->path_state(0), r->hit.p, seg, r->Fbuf.p);
     }
+    // ambient occlusion of a render that keeps it (k_trace_ao): one any-hit ray from each of the same hits, in a timer class of its own
+    if (r->ao) {
+      ScopedTimer t(r, K_AO_TRACE);
+      launch_trace_ao(s, r->closest_grid, S, r->path_state(0), r->hit.p, seg, ctr, r->spill.p, r->Obuf.p, r->ao_distance, nullptr, 0u);
+    }
   }
   // The bounces: bounce b's closest hits (bounce 0's are in hit[] already), k_shade, and the shadow rays it queued.
   int cur = 0;
@@ -202,6 +207,10 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
                             r->params.nonfinite_policy, tiles);
     if (r->matte) launch_accumulate_matte(s, r->matte_slots.p, r->Mbuf.p, S.width, S.height, ns, tiles);
     if (r->film) launch_accumulate_film(s, r->film_img.p, r->Lbuf.p, r->Fbuf.p, S.width, S.height, ns, n0, r->params.nonfinite_policy, tiles);
+  }
+  if (mode == BATCH_RENDER && r->ao) {
+    ScopedTimer t(r, K_AO_FOLD);
+    launch_accumulate_ao(s, r->ao_counts.p, r->Obuf.p, S.width, S.height, ns, tiles);
   }
   // a batch that ends at a checkpoint (flush_pending never lets one straddle it): test the active tiles, compact the list into the other
   // buffer, and send the new count to pinned host memory
@@ -334,6 +343,7 @@ int dev_create(const pt_create_info* info, int device_ordinal, pt_renderer** out
   pt_default_matte_options(&r->matte_opts);
   pt_default_selection_options(&r->selection);
   pt_default_film_options(&r->film_opts);
+  pt_default_ao_options(&r->ao_opts);
   pt_default_camera_projection(&r->proj_opts);
   r->proj = r->proj_opts;
   pt_default_view_options(&r->view_opts);
@@ -612,6 +622,8 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
   if (!matte) { r->Mbuf.release(); r->matte_slots.release(); r->matte_ids.release(); r->matte_cov.release(); }   // (nor does a matte-off render)
   const bool film = r->film_opts.enabled != 0;
   if (!film) { r->Fbuf.release(); r->film_img.release(); r->film_src.release(); }   // (nor a film-off render)
+  const bool ao = r->ao_opts.enabled != 0;
+  if (!ao) { r->Obuf.release(); r->ao_counts.release(); }   // (nor an AO-off render)
   const bool adaptive = r->adaptive_opts.enabled != 0;
   const bool region = r->region_opts.enabled != 0;
   if (!adaptive) r->release_checkpoints();                  // (nor does an adaptive-off render;
@@ -622,7 +634,7 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
   // so every grid is sized for its own kernel's occupancy.
   {
     const uint64_t budget = queue_budget(free_device_bytes(), r->queue_bytes_held(), r->cam_entries.bytes_held() + r->cam_count.bytes_held(), aov,
-                                         r->Abuf.bytes_held(), matte, r->Mbuf.bytes_held(), film, r->Fbuf.bytes_held());
+                                         r->Abuf.bytes_held(), matte, r->Mbuf.bytes_held(), film, r->Fbuf.bytes_held(), ao, r->Obuf.bytes_held());
     pt_queue_plan plan{};
     const char* why = "";
     const int rc = plan_queues(p->width, p->height, p->spp, p->samples_in_flight, budget, r->tiles_per_seg_override, r->seg_bands, &plan, &why);
@@ -686,6 +698,11 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
     PT_HIP(r->film_img.alloc(npix));
     PT_HIP(hipMemsetAsync(r->film_img.p, 0, sizeof(vec4) * npix, r->stream));
   }
+  if (ao) {
+    PT_HIP(r->Obuf.alloc(r->Lbuf.n));
+    PT_HIP(r->ao_counts.alloc(npix));
+    PT_HIP(hipMemsetAsync(r->ao_counts.p, 0, sizeof(uint2) * npix, r->stream));
+  }
   if (adaptive || region) {  // every tile the rectangle touches starts active (the whole frame: [0, tiles)), ascending (adaptive.hip)
     const Rect rect = render_rect(r, p);
     const uint32_t tiles = tile_count(p->width, p->height);
@@ -725,6 +742,8 @@ void reset_progress(pt_renderer* r, const pt_render_params* p) {
   r->aov = r->denoise.enabled != 0;
   r->matte = r->matte_opts.enabled != 0;
   r->film = r->film_opts.enabled != 0;
+  r->ao = r->ao_opts.enabled != 0;
+  r->ao_distance = r->ao_opts.distance;
   r->adaptive = r->adaptive_opts.enabled != 0;
   r->region = r->region_opts.enabled != 0;
   r->vtiles = r->adaptive || r->region;
@@ -961,6 +980,96 @@ int dev_read_film(pt_renderer* r, float* rgba_out) {
   int rc = dev_wait(r);
   if (rc != PT_OK) return rc;
   PT_HIP(hipMemcpy(rgba_out, r->film_img.p, sizeof(vec4) * (size_t)r->S.width * r->S.height, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+// ---- ambient occlusion (pt_ao.h, k_trace_ao in kernels.hip, ao.hip) --------------------------------------------------------------------------
+extern "C" void pt_default_ao_options(pt_ao_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->distance = 1.0f;
+}
+
+// (the options are checked before the renderer, as dev_set_film_options)
+int dev_set_ao_options(pt_renderer* r, const pt_ao_options* o) {
+  if (!o) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_ao_options: null options");
+  if (const char* why = ao_options_error(*o)) return fail(PT_ERR_INVALID_ARGUMENT, std::string("pt_set_ao_options: ") + why);
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_set_ao_options: null renderer");
+  r->ao_opts = *o;
+  return PT_OK;
+}
+
+namespace {
+
+// what every AO read checks first, in this order: the arguments, then the render's state; then it waits for the render
+int ao_read_counts(pt_renderer* r, const void* out, const char* who, std::vector<uint2>* counts) {
+  if (!r || !out) return fail(PT_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+  if (!r->started || !r->ao) return fail(PT_ERR_BAD_STATE, std::string(who) + ": the render was not started with ambient occlusion enabled");
+  const int rc = dev_wait(r);
+  if (rc != PT_OK) return rc;
+  counts->resize((size_t)r->S.width * r->S.height);
+  PT_HIP(hipMemcpy(counts->data(), r->ao_counts.p, sizeof(uint2) * counts->size(), hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+}  // namespace
+
+int dev_read_ao_counts(pt_renderer* r, uint32_t* out) {
+  std::vector<uint2> c;
+  const int rc = ao_read_counts(r, out, "pt_read_ao_counts", &c);
+  if (rc != PT_OK) return rc;
+  for (size_t p = 0; p < c.size(); p++) { out[2 * p] = c[p].x; out[2 * p + 1] = c[p].y; }
+  return PT_OK;
+}
+
+int dev_read_ao(pt_renderer* r, float* out) {
+  std::vector<uint2> c;
+  const int rc = ao_read_counts(r, out, "pt_read_ao", &c);
+  if (rc != PT_OK) return rc;
+  for (size_t p = 0; p < c.size(); p++) out[p] = ao_value(c[p].x, c[p].y);
+  return PT_OK;
+}
+
+int dev_get_ao_stats(pt_renderer* r, pt_ao_stats* out) {
+  std::vector<uint2> c;
+  const int rc = ao_read_counts(r, out, "pt_get_ao_stats", &c);
+  if (rc != PT_OK) return rc;
+  memset(out, 0, sizeof(*out));
+  for (const uint2& v : c) out->rays += v.x;   // one AO ray per camera ray that hit
+  out->ms_trace = (float)r->ms_class[K_AO_TRACE];
+  out->ms_fold = (float)r->ms_class[K_AO_FOLD];
+  return PT_OK;
+}
+
+// One sample of every pixel: pt_trace_primary's batch (camera rays, table pass, tree walk), then the AO trace of a render batch with its ray log,
+// and the states scattered to pixel order.  Obuf is the render's own (each batch rewrites it before its fold); the counts are not touched.
+int dev_debug_ao(pt_renderer* r, uint32_t sample_idx, float* origins, float* directions, uint32_t* state) {
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_ao: null renderer");
+  if (!r->started || !r->ao) return fail(PT_ERR_BAD_STATE, "pt_debug_ao: the render was not started with ambient occlusion enabled");
+  PT_HIP(hipSetDevice(r->device));
+  { const int rc = flush_pending(r, true); if (rc != PT_OK) return rc; }
+  const uint32_t npix = r->S.width * r->S.height;
+  DevBuf<float> log;
+  DevBuf<uint32_t> st;
+  PT_HIP(log.alloc(6 * (size_t)npix));
+  PT_HIP(st.alloc(npix));
+  hipStream_t s = r->stream;
+  PT_HIP(hipMemsetAsync(log.p, 0, sizeof(float) * log.n, s));      // a pixel whose camera ray missed: zero origin and direction, state 0
+  PT_HIP(hipMemsetAsync(st.p, 0, sizeof(uint32_t) * st.n, s));
+  PT_HIP(hipMemsetAsync(r->ctr.p, 0, sizeof(BatchCounters), s));
+  Segments seg = r->segments();
+  seg.nsamples = 1;
+  launch_camera_raygen(r, seg, sample_idx, 1, nullptr);
+  launch_chunk_tables(s, seg, 0, r->ctr.p, 0, 0, false);
+  launch_trace_closest(s, r->closest_grid, r->S, r->path_state(0), r->hit.p, seg, 0, r->ctr.p, 0, r->spill.p, nullptr, npix, false);
+  launch_trace_ao(s, r->closest_grid, r->S, r->path_state(0), r->hit.p, seg, r->ctr.p, r->spill.p, r->Obuf.p, r->ao_distance, log.p, npix);
+  launch_ao_scatter(s, r->grid, r->S.width, r->path_state(0), r->hit.p, seg, r->Obuf.p, st.p);
+  launch_fold_counters(s, r->ctr.p, r->totals.p + 1, seg, false);  // clears the per-wave statistics (scratch slot), as pt_trace_primary
+  PT_HIP(hipGetLastError());
+  PT_HIP(hipStreamSynchronize(s));
+  if (origins) PT_HIP(hipMemcpy(origins, log.p, sizeof(float) * 3 * (size_t)npix, hipMemcpyDeviceToHost));
+  if (directions) PT_HIP(hipMemcpy(directions, log.p + 3 * (size_t)npix, sizeof(float) * 3 * (size_t)npix, hipMemcpyDeviceToHost));
+  if (state) PT_HIP(hipMemcpy(state, st.p, sizeof(uint32_t) * npix, hipMemcpyDeviceToHost));
   return PT_OK;
 }
 

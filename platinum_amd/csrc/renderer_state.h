@@ -11,6 +11,7 @@
 
 #include "host_scene.h"
 #include "adaptive.h"
+#include "ao.h"
 #include "bloom.h"
 #include "camera_lists.h"
 #include "denoise.h"
@@ -74,7 +75,8 @@ struct DevBuf {
   ~DevBuf() { release(); }
 };
 
-enum KernelClass { K_RAYGEN = 0, K_CLOSEST, K_SHADE, K_SHADOW, K_ACCUM, K_CLASSES };
+// (K_AO_TRACE, K_AO_FOLD: the ambient-occlusion pass, reported by pt_get_ao_stats alone; the five classes of pt_stats keep their meaning)
+enum KernelClass { K_RAYGEN = 0, K_CLOSEST, K_SHADE, K_SHADOW, K_ACCUM, K_AO_TRACE, K_AO_FOLD, K_CLASSES };
 
 struct TimedLaunch { int cls; hipEvent_t start, stop; };
 
@@ -164,6 +166,12 @@ struct pt_renderer {
   DevBuf<uint32_t> Fbuf;            // 1: the camera ray hit, 0: it missed, per Lbuf entry
   DevBuf<vec4> film_img;            // [pixel] {premultiplied foreground, coverage} running means
   DevBuf<vec4> film_src;            // the film over the backdrop: what the display chain starts from
+  // ambient occlusion (k_trace_ao in kernels.hip, ao.hip): only a render started with ao_opts.enabled allocates or launches any of it
+  pt_ao_options ao_opts{};
+  bool ao = false;                  // this render keeps AO counts
+  float ao_distance = 1.0f;         // of this render (ao_opts is what the NEXT start reads)
+  DevBuf<uint32_t> Obuf;            // 0: the camera ray missed, 1: hit and AO ray occluded, 2: hit and AO ray open, per Lbuf entry
+  DevBuf<uint2> ao_counts;          // [pixel] {hits, open}
   // camera projection (projection.hip): proj_opts is what pt_set_camera_projection holds for the NEXT start; proj and the constants
   // derived from it and the snapshot's camera belong to the current render.  Under PT_PROJ_PERSPECTIVE nothing of projection.hip is launched.
   pt_camera_projection proj_opts{};
@@ -244,8 +252,8 @@ struct pt_renderer {
   // measurement
   bool profiling = false;
   std::vector<TimedLaunch> timed;
-  double ms_class[K_CLASSES] = {0, 0, 0, 0, 0};
-  uint64_t launches[K_CLASSES] = {0, 0, 0, 0, 0};
+  double ms_class[K_CLASSES] = {};
+  uint64_t launches[K_CLASSES] = {};
   double upload_ms = 0, bvh_ms = 0;
 
   TileSet tile_set() { return TileSet{ad_list[ad_cur].p, ad_count.p + ad_cur, ad_tiles0, rect}; }   // of a render with `vtiles`: the current list
@@ -265,6 +273,7 @@ struct pt_renderer {
     aov = false;
     matte = false;
     film = false;
+    ao = false;
     cam_lists = false;
     adaptive = false;
     region = false;
@@ -333,6 +342,11 @@ int dev_read_matte_slots(pt_renderer* r, uint32_t layer, pt_matte_slot* out);
 int dev_read_matte(pt_renderer* r, uint32_t layer, const uint32_t* ids, uint32_t id_count, float* coverage_out);
 int dev_pick(pt_renderer* r, uint32_t x, uint32_t y, pt_pick_result* out);
 int dev_read_film(pt_renderer* r, float* rgba_out);
+int dev_set_ao_options(pt_renderer* r, const pt_ao_options* o);
+int dev_read_ao(pt_renderer* r, float* out);
+int dev_read_ao_counts(pt_renderer* r, uint32_t* out);
+int dev_debug_ao(pt_renderer* r, uint32_t sample_idx, float* origins, float* directions, uint32_t* state);
+int dev_get_ao_stats(pt_renderer* r, pt_ao_stats* out);
 int dev_set_camera_projection(pt_renderer* r, const pt_camera_projection* p);
 int dev_get_camera_projection(pt_renderer* r, pt_camera_projection* out);
 int dev_debug_camera_rays(pt_renderer* r, uint32_t sample_idx, float* origins, float* directions);

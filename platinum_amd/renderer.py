@@ -489,6 +489,52 @@ class Renderer:
         abi.check(self._lib, self._lib.pt_debug_camera_rays(self._h, sample_idx, o.ctypes.data, d.ctypes.data))
         return o, d
 
+    # ambient occlusion (include/ptamd.h, an additive extension of ABI 5): no counterpart in the reference's path tracer
+    def ambientOcclusionOptions(self):
+        """The options in effect (pt_default_ao_options until setAmbientOcclusionOptions is called)."""
+        if getattr(self, "_ao", None) is None:
+            self._ao = abi.AoOptions()
+            self._lib.pt_default_ao_options(C.byref(self._ao))
+        o = abi.AoOptions()
+        C.memmove(C.byref(o), C.byref(self._ao), C.sizeof(o))
+        return o
+
+    def setAmbientOcclusionOptions(self, o=None, **fields):
+        """Sets `o` (default: the current options) with `fields` overriding it, e.g. setAmbientOcclusionOptions(enabled=1, distance=2.0);
+        distance may be float("inf").  Takes effect at the next startRender."""
+        o = self.ambientOcclusionOptions() if o is None else o
+        for k, v in fields.items():
+            setattr(o, k, v)
+        abi.check(self._lib, self._lib.pt_set_ao_options(self._h, C.byref(o)))
+        self._ao = o
+
+    def readbackAmbientOcclusion(self):
+        """(H, W) float32: open / hits per pixel (1 where no camera ray hit) of a render started with ambient occlusion enabled."""
+        w, h = self.size
+        out = np.empty((h, w), dtype=np.float32)
+        abi.check(self._lib, self._lib.pt_read_ao(self._h, out.ctypes.data))
+        return out
+
+    def readbackAmbientOcclusionCounts(self):
+        """(H, W, 2) uint32 {hits, open}: the camera rays of the pixel's samples that hit, and those of them whose AO ray met nothing."""
+        w, h = self.size
+        out = np.empty((h, w, 2), dtype=np.uint32)
+        abi.check(self._lib, self._lib.pt_read_ao_counts(self._h, out.ctypes.data))
+        return out
+
+    def debugAmbientOcclusion(self, sample_idx=0):
+        """(origins, directions, state): (H, W, 3) float32 twice and (H, W) uint32 (abi.AO_MISS / AO_OCCLUDED / AO_OPEN): the AO rays of one
+        sample of every pixel as the render's own trace kernel makes them; zero origin and direction where the camera ray missed."""
+        w, h = self.size
+        o, d, st = np.empty((h, w, 3), np.float32), np.empty((h, w, 3), np.float32), np.empty((h, w), np.uint32)
+        abi.check(self._lib, self._lib.pt_debug_ao(self._h, sample_idx, o.ctypes.data, d.ctypes.data, st.ctypes.data))
+        return o, d, st
+
+    def ambientOcclusionStats(self):
+        s = abi.AoStats()
+        abi.check(self._lib, self._lib.pt_get_ao_stats(self._h, C.byref(s)))
+        return s
+
     # pass views (include/ptamd.h, an additive extension of ABI 5): no counterpart in the reference's path tracer
     def viewOptions(self):
         """The options in effect (pt_default_view_options until setViewOptions is called)."""

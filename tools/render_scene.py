@@ -14,6 +14,7 @@ tracing (GMoN optional), fused post-process + tonemap — to an 8-bit PNG.
     python tools/render_scene.py builtin:c3 out.png --size 960 540 --spp 32 --select 497,498,530 --outline-width 3
     python tools/render_scene.py builtin:c5 cutout.png --size 960 540 --spp 64 --film transparent     (an RGBA PNG with straight alpha)
     python tools/render_scene.py builtin:c5 studio.png --size 960 540 --spp 64 --film 0.18,0.18,0.18  (the objects over a flat colour)
+    python tools/render_scene.py builtin:c1 clay.png --size 640 640 --spp 64 --ao 2      (writes clay_ao.png beside clay.png: dark corners, white walls)
     python tools/render_scene.py builtin:c3 ids.png --size 960 540 --spp 32 --view matte --matte instance   (the picture itself shows the ids)
     python tools/render_scene.py builtin:c3 heat.png --size 960 540 --spp 256 --adaptive 0.05 --view samples --ramp heat
     python tools/render_scene.py builtin:c5 probe.png --size 1024 512 --spp 64 --projection equirect     (a light probe of the scene)
@@ -80,6 +81,9 @@ def main():
     ap.add_argument("--film", default=None, metavar="transparent|R,G,B",
                     help="keep the transparent film and show the objects without the environment behind them: 'transparent' writes straight alpha "
                          "into the PNG, R,G,B (scene-linear, >= 0) puts that flat colour behind them; the environment still lights the scene")
+    ap.add_argument("--ao", type=float, nargs="?", const=1.0, default=None, metavar="DISTANCE",
+                    help="keep the ambient-occlusion pass (one occlusion ray of at most DISTANCE world units, default 1, 'inf' allowed, from every "
+                         "camera ray's first hit) and write it in grey beside the picture: OUTPUT_ao.png, white = open")
     ap.add_argument("--view", choices=abi.VIEW_NAMES, default="beauty",
                     help="what the picture shows (the render target's pass view, drawn on the device): the beauty, or the albedo, normals, depth, "
                          "film alpha, ID mattes (the layer of --matte, default instance), sample counts or noise estimate; what the view needs is kept")
@@ -113,6 +117,8 @@ def main():
             select = []
         if not select or min(select) < 0 or max(select) > 0xFFFFFFFF or not 1.0 <= a.outline_width <= 16.0:
             ap.error("--select takes ID[,ID...] (0xFFFFFFFF = the background) and --outline-width a width from 1 to 16")
+    if a.ao is not None and not a.ao > 0.0:
+        ap.error("--ao takes a distance > 0 (inf allowed)")
     if a.despeckle is not None and not a.denoise:
         ap.error("--despeckle is a stage of the denoiser: it needs --denoise")
     region = None
@@ -176,6 +182,8 @@ def main():
     if select:
         r.setSelectionOptions(enabled=1, layer=abi.MATTE_INSTANCE if a.select_layer == "instance" else abi.MATTE_MATERIAL, width=a.outline_width)
         r.setSelection(select)
+    if a.ao is not None:
+        r.setAmbientOcclusionOptions(enabled=1, distance=a.ao)
     if a.film is not None:
         r.setFilmOptions(enabled=1, backdrop=abi.BACKDROP_TRANSPARENT if backdrop is None else abi.BACKDROP_COLOR, backdrop_rgb=backdrop or (0.0, 0.0, 0.0))
     elif view == abi.VIEW_ALPHA:
@@ -203,6 +211,13 @@ def main():
         alpha = r.readbackFilm()[..., 3]
         print(f"film: coverage 1 on {int((alpha == 1).sum())} pixels, 0 on {int((alpha == 0).sum())}, fractional on {int(((alpha > 0) & (alpha < 1)).sum())}; "
               + ("straight alpha written" if backdrop is None else "backdrop %g, %g, %g" % backdrop))
+    if a.ao is not None:
+        ao = r.readbackAmbientOcclusion()
+        path = os.path.splitext(a.output)[0] + "_ao.png"
+        g = np.round(np.clip(ao, 0.0, 1.0) * 255.0).astype(np.uint8)     # linear grey: a data pass, not a picture
+        write_png_rgba8(path, np.stack([g, g, g, np.full_like(g, 255)], axis=-1))
+        s_ao = r.ambientOcclusionStats()
+        print(f"ambient occlusion: wrote {path}; distance {a.ao:g}, {s_ao.rays} AO rays, mean {float(ao.mean()):.3f}, {int((ao == 1).sum())} pixels fully open")
     if select:
         cov = r.readbackMatte(r.selectionOptions().layer, select)
         print(f"selection: {len(r.selection())} {a.select_layer} ids cover {int((cov > 0).sum())} pixels ({float(cov.sum()):.1f} in all), outline {a.outline_width:g} px")
