@@ -570,6 +570,24 @@ typedef struct pt_light_probe_args {
 } pt_light_probe_args;
 int pt_debug_lights(pt_renderer* r, uint32_t fn, uint32_t n, const pt_light_probe_args* args, const void* in, void* out);
 
+/* ---- shading-frame probe (NEW, an additive extension of ABI 5: one entry point) ----
+ * Parity surface: the stage between a hit record and the BSDF — the interpolation of normals, tangents and UVs, the instance transform, the
+ * tangent frame with and without a normal map, wo, and the shading context with its texture taps — evaluated on the device on its own
+ * against the scene of the STARTED render, exactly as the shade and AOV kernels evaluate it.  One elementwise launch on the renderer's
+ * stream; upload and read-back inside the call; the render's state is left alone.  `in` holds n records of PT_SHADE_PROBE_IN_WORDS 4-byte
+ * words, `out` receives n records of PT_SHADE_PROBE_OUT_WORDS:
+ *   in:  instance (uint32), primitive (uint32: the triangle inside the instance's mesh), u, v, ray origin x y z, ray direction x y z, t, 0
+ *   out: hitPos x y z, frame.x x y z, frame.y x y z, frame.z x y z, wo x y z, albedo r g b, emission r g b, roughness, metallic,
+ *        transmission, clearcoat, clearcoatRoughness, anisotropy, ior, flags (int32), material class (uint32, 0..3), 0, 0
+ * u, v, the ray and t are taken as they come: any float is answered (the stage indexes nothing with them but the textures, whose
+ * addressing wraps).
+ * PT_ERR_INVALID_ARGUMENT, before the renderer is looked at: n = 0 or n > 2^24, a null in / out; then a null renderer.  PT_ERR_BAD_STATE
+ * before pt_start_render.  PT_ERR_INVALID_ARGUMENT for a record whose (instance, primitive) names no triangle of the scene: such a batch
+ * is refused on the host and nothing is launched. */
+#define PT_SHADE_PROBE_IN_WORDS 12u
+#define PT_SHADE_PROBE_OUT_WORDS 32u
+int pt_debug_shading(pt_renderer* r, uint32_t n, const void* in, void* out);
+
 /* ---- tile-adaptive sampling (NEW, an additive extension of ABI 5: new entry points and one new struct, no existing struct changed) ----
  * A render started while `enabled` is set stops sampling an 8x8 tile of the accumulator once it has converged; pt_render_params.spp
  * becomes the per-pixel maximum.  Checkpoints are at the sample counts c_k = min_spp + k * interval with c_k < spp.  At each, every

@@ -233,8 +233,10 @@ float4 tex_sample(const Tex& t, float2 uv) {
   const float fx = uv.x * (float)t.w - 0.5f, fy = uv.y * (float)t.h - 0.5f;
   const float x0f = floorf(fx), y0f = floorf(fy);
   const float wx = fx - x0f, wy = fy - y0f;
-  const int x0 = wrapi((int)x0f, t.w), x1 = wrapi((int)x0f + 1, t.w);
-  const int y0 = wrapi((int)y0f, t.h), y1 = wrapi((int)y0f + 1, t.h);
+  // the tap index is defined for every float: floor(x) clamped to [-2^31, 2^31 - 128] before the conversion (a NaN clamps to -2^31)
+  const int xi = (int)fminf(fmaxf(x0f, -2147483648.0f), 2147483520.0f), yi = (int)fminf(fmaxf(y0f, -2147483648.0f), 2147483520.0f);
+  const int x0 = wrapi(xi, t.w), x1 = wrapi(xi + 1, t.w);
+  const int y0 = wrapi(yi, t.h), y1 = wrapi(yi + 1, t.h);
   const float* p00 = &t.px[4 * ((size_t)y0 * t.w + x0)];
   const float* p01 = &t.px[4 * ((size_t)y0 * t.w + x1)];
   const float* p10 = &t.px[4 * ((size_t)y1 * t.w + x0)];
@@ -1786,6 +1788,41 @@ int orc_env_miss(const orc_scene* sc, uint32_t n, const pt_light_probe_args* arg
   }
   return 0;
 }
+// The twin of pt_debug_shading: getIntersectionData and the ShadingContext constructor for the hit a record describes, written out in
+// the probe's record layout.  The material class is restated from the material (which lobes BSDF::sample can take): 3 = clearcoat or a
+// texture that may switch lobes per texel, 2 = transmission, 1 = metallic, 0 = opaque dielectric only.
+int orc_shade_probe(const orc_scene* sc, uint32_t n, const void* in_, void* out_) {
+  const uint32_t* in = (const uint32_t*)in_;
+  float* out = (float*)out_;
+  auto f = [](uint32_t u) { float x; memcpy(&x, &u, 4); return x; };
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t* e = in + (size_t)i * PT_SHADE_PROBE_IN_WORDS;
+    if (e[0] >= sc->instances.size()) return -1;
+    if (e[1] >= sc->meshes[sc->instances[e[0]].accelerationStructureIndex].slots.size()) return -1;
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t* e = in + (size_t)i * PT_SHADE_PROBE_IN_WORDS;
+    Ray ray;
+    ray.origin = f3(f(e[4]), f(e[5]), f(e[6]));
+    ray.direction = f3(f(e[7]), f(e[8]), f(e[9]));
+    Intersection isect;
+    isect.hit = true; isect.instance_id = e[0]; isect.primitive_id = e[1]; isect.u = f(e[2]); isect.v = f(e[3]); isect.distance = f(e[10]);
+    const Hit hit = getIntersectionData(*sc, ray, isect);
+    const pt_material_gpu& m = *hit.material;
+    const ShadingContext ctx(m, hit.uv, sc->idt, sc->textures);
+    float* o = out + (size_t)i * PT_SHADE_PROBE_OUT_WORDS;
+    const float3 v[7] = {hit.pos, hit.frame.x, hit.frame.y, hit.frame.z, hit.wo, ctx.albedo, ctx.emission};
+    for (int k = 0; k < 7; k++) { o[3 * k] = v[k].x; o[3 * k + 1] = v[k].y; o[3 * k + 2] = v[k].z; }
+    o[21] = ctx.roughness; o[22] = ctx.metallic; o[23] = ctx.transmission; o[24] = ctx.clearcoat;
+    o[25] = ctx.clearcoatRoughness; o[26] = ctx.anisotropy; o[27] = ctx.ior;
+    const uint32_t cls = (m.clearcoat > 0.0f || m.clearcoatTextureId >= 0 || m.rmTextureId >= 0 || m.transmissionTextureId >= 0) ? 3u
+                         : m.transmission > 0.0f ? 2u : m.metallic > 0.0f ? 1u : 0u;
+    const uint32_t words[4] = {(uint32_t)ctx.flags, cls, 0u, 0u};
+    memcpy(o + 28, words, sizeof(words));
+  }
+  return 0;
+}
+
 // ---- LUT generator restatement (pins A7-A9 against reference-held data) -------------------------------------------------
 // The eight energy tables the renderer loads (resource/lut/*.exr -> platinum_amd/data/ggx_luts.bin) are Monte-Carlo integrals
 // of the reference's own lobes, produced by its tool /root/reference/src/frontend/windows/tools/shaders/ms_lut_gen.metal:

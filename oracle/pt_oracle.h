@@ -65,6 +65,9 @@ void orc_bsdf_eval(const orc_scene* sc, const pt_material_gpu* mat, const float 
 // sampleLightPower, sampleAreaLight, sampleEnvironmentLight and miss branch.  orc_env_miss returns -1 for a scene without an environment.
 void orc_light_sample(const orc_scene* sc, uint32_t n, const pt_light_probe_args* args, const void* in, void* out);
 int orc_env_miss(const orc_scene* sc, uint32_t n, const pt_light_probe_args* args, const void* in, void* out);
+// The twin of pt_debug_shading: the same records through the oracle's own getIntersectionData and ShadingContext.  -1 for a record whose
+// (instance, primitive) is out of range.
+int orc_shade_probe(const orc_scene* sc, uint32_t n, const void* in, void* out);
 
 #ifdef __cplusplus
 }

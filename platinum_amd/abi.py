@@ -20,6 +20,13 @@ PT_LIGHT_OUT_WORDS = {PT_LIGHT_SAMPLE: 12, PT_LIGHT_ENV_MISS: 4}
 # numpy views of pt_debug_lights' result records
 LIGHT_SAMPLE_DTYPE = [("lit", "u4"), ("Li", "f4", 3), ("lwi", "f4", 3), ("lpdf", "f4"), ("pLight", "f4"), ("dist", "f4"), ("dim", "u4"), ("_pad", "u4")]
 ENV_MISS_DTYPE = [("L", "f4", 3), ("_pad", "u4")]
+# pt_debug_shading's record sizes in 4-byte words and numpy views of its records (include/ptamd.h PT_SHADE_PROBE_*)
+PT_SHADE_PROBE_IN_WORDS, PT_SHADE_PROBE_OUT_WORDS = 12, 32
+SHADE_PROBE_IN_DTYPE = [("instance", "u4"), ("primitive", "u4"), ("u", "f4"), ("v", "f4"), ("o", "f4", 3), ("d", "f4", 3), ("t", "f4"), ("_pad", "u4")]
+SHADE_PROBE_OUT_DTYPE = [("hitPos", "f4", 3), ("x", "f4", 3), ("y", "f4", 3), ("z", "f4", 3), ("wo", "f4", 3), ("albedo", "f4", 3),
+                         ("emission", "f4", 3), ("roughness", "f4"), ("metallic", "f4"), ("transmission", "f4"), ("clearcoat", "f4"),
+                         ("clearcoatRoughness", "f4"), ("anisotropy", "f4"), ("ior", "f4"), ("flags", "i4"), ("material_class", "u4"),
+                         ("_pad", "u4", 2)]
 
 # renderer_pt.hpp:21-26
 STATUS_BLOCKED, STATUS_READY, STATUS_BUSY, STATUS_DONE = 0, 1, 4, 8
@@ -393,6 +400,7 @@ SYMBOLS = [
                                     C.POINTER(ExposureMeter), C.c_void_p]),
     ("pt_debug_math", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pt_debug_lights", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(LightProbeArgs), C.c_void_p, C.c_void_p]),
+    ("pt_debug_shading", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("pt_default_bloom_options", None, [C.POINTER(BloomOptions)]),
     ("pt_set_bloom_options", C.c_int, [C.c_void_p, C.POINTER(BloomOptions)]),
     ("pt_plan_bloom", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(BloomPlan)]),

@@ -733,6 +733,11 @@ int pt_debug_lights(pt_renderer* r, uint32_t fn, uint32_t n, const pt_light_prob
   return dev_debug_lights(is_group(r) ? r->group->shards[0] : r, fn, n, args, in, out);
 }
 
+// as pt_debug_lights: the first member answers
+int pt_debug_shading(pt_renderer* r, uint32_t n, const void* in, void* out) {
+  return dev_debug_shading(is_group(r) ? r->group->shards[0] : r, n, in, out);
+}
+
 // Bloom: as auto exposure, every member holds the options and the member that displays the merged image does the work.
 int pt_set_bloom_options(pt_renderer* r, const pt_bloom_options* o) { return on_members(r, dev_set_bloom_options, o); }
 

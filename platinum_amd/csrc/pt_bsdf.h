@@ -104,13 +104,20 @@ PT_HD vec4 tex_bilerp(const vec4& p00, const vec4& p01, const vec4& p10, const v
   { const float a = p00.w + (p01.w - p00.w) * wx, b = p10.w + (p11.w - p10.w) * wx; o.w = a + (b - a) * wy; }
   return o;
 }
+// Total over the floats, as lut_axis is: the tap index is taken from floor(x) clamped to [-2^31, 2^31 - 128] FIRST (a NaN clamps to -2^31;
+// 2^31 - 128 is the largest float below 2^31), so the float -> int conversion and the + 1 after it are always defined.  A bare (int) of
+// a floor at or beyond 2^31 gave INT_MIN on the x86 host and INT_MAX on the device, and the two wrapped to different texels
+// (profiles/r23_shading_witness.md).  For every coordinate whose conversion was defined before, the taps and weights are what they were
+// (the weights come from the unclamped floor).
+PT_HD int tex_tap(float fl) { return (int)fminf(fmaxf(fl, -2147483648.0f), 2147483520.0f); }
 PT_HD vec4 tex_sample(const DeviceScene& S, int id, vec2 uv) {
   const TexInfo t = ldg(&S.textures[id]);
   const float fx = uv.x * (float)t.w - 0.5f, fy = uv.y * (float)t.h - 0.5f;
   const float x0f = floorf(fx), y0f = floorf(fy);
   const float wx = fx - x0f, wy = fy - y0f;
-  const int x0 = tex_wrap((int)x0f, (int)t.w), x1 = tex_wrap((int)x0f + 1, (int)t.w);
-  const int y0 = tex_wrap((int)y0f, (int)t.h), y1 = tex_wrap((int)y0f + 1, (int)t.h);
+  const int xi = tex_tap(x0f), yi = tex_tap(y0f);
+  const int x0 = tex_wrap(xi, (int)t.w), x1 = tex_wrap(xi + 1, (int)t.w);
+  const int y0 = tex_wrap(yi, (int)t.h), y1 = tex_wrap(yi + 1, (int)t.h);
   const size_t i00 = (size_t)y0 * t.w + x0, i01 = (size_t)y0 * t.w + x1, i10 = (size_t)y1 * t.w + x0, i11 = (size_t)y1 * t.w + x1;
   if (!S.tex_native) {
     const vec4* texels = reinterpret_cast<const vec4*>(S.tex_data + (size_t)t.offset16 * 16u);

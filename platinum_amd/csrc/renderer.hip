@@ -27,6 +27,8 @@
 #include "renderer_state.h"
 #include "light_probe.h"
 #include "pt_light_probe.h"
+#include "shade_probe.h"
+#include "pt_shade_probe.h"
 
 using namespace pt;
 
@@ -1130,6 +1132,39 @@ int dev_debug_lights(pt_renderer* r, uint32_t fn, uint32_t n, const pt_light_pro
   PT_HIP(hipGetLastError());
   PT_HIP(hipStreamSynchronize(r->stream));
   PT_HIP(hipMemcpy(out, dout.p, sizeof(uint32_t) * (size_t)n * wo, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+// pt_debug_shading: the (instance, primitive) pairs of every triangle come back from the device first (one launch over the leaf slots), the
+// host resolves each record's triangle against them and refuses the batch if one names none; then one elementwise launch of
+// shade_probe.hip on the resolved records against the started render's scene table.  The render's state is untouched.
+int dev_debug_shading(pt_renderer* r, uint32_t n, const void* in, void* out) {
+  if (n == 0 || n > (1u << 24)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_shading: n must be 1..2^24");
+  if (!in || !out) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_shading: null argument");
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_shading: null renderer");
+  if (!r->started) return fail(PT_ERR_BAD_STATE, "pt_debug_shading before pt_start_render");
+  PT_HIP(hipSetDevice(r->device));
+  const uint32_t n_tri = 2u * r->slot_count;
+  std::vector<int32_t> ids(2 * (size_t)n_tri);
+  if (n_tri) {
+    DevBuf<int32_t> dids;
+    PT_HIP(dids.alloc(ids.size()));
+    launch_shade_probe_ids(r->stream, r->scene_d.p, n_tri, dids.p);
+    PT_HIP(hipGetLastError());
+    PT_HIP(hipStreamSynchronize(r->stream));
+    PT_HIP(hipMemcpy(ids.data(), dids.p, sizeof(int32_t) * ids.size(), hipMemcpyDeviceToHost));
+  }
+  std::vector<uint32_t> rec((size_t)n * PT_SHADE_PROBE_IN_WORDS);
+  memcpy(rec.data(), in, sizeof(uint32_t) * rec.size());
+  if (!shade_probe_resolve(ids.data(), n_tri, rec.data(), n))
+    return fail(PT_ERR_INVALID_ARGUMENT, "pt_debug_shading: a record's (instance, primitive) names no triangle of the scene");
+  DevBuf<uint32_t> din, dout;
+  PT_HIP(din.alloc(rec.size())); PT_HIP(dout.alloc((size_t)n * PT_SHADE_PROBE_OUT_WORDS));
+  PT_HIP(hipMemcpyAsync(din.p, rec.data(), sizeof(uint32_t) * rec.size(), hipMemcpyHostToDevice, r->stream));
+  launch_shade_probe(r->stream, r->scene_d.p, n, din.p, dout.p);
+  PT_HIP(hipGetLastError());
+  PT_HIP(hipStreamSynchronize(r->stream));
+  PT_HIP(hipMemcpy(out, dout.p, sizeof(uint32_t) * (size_t)n * PT_SHADE_PROBE_OUT_WORDS, hipMemcpyDeviceToHost));
   return PT_OK;
 }
 

@@ -333,6 +333,7 @@ int dev_get_stats(pt_renderer* r, pt_stats* out);
 int dev_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out);
 int dev_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const void* b, void* out0, void* out1);
 int dev_debug_lights(pt_renderer* r, uint32_t fn, uint32_t n, const pt_light_probe_args* args, const void* in, void* out);
+int dev_debug_shading(pt_renderer* r, uint32_t n, const void* in, void* out);
 int dev_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o);
 int dev_read_sample_counts(pt_renderer* r, uint32_t* out);
 int dev_set_render_region(pt_renderer* r, const pt_render_region* o);

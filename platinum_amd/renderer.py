@@ -261,6 +261,15 @@ class Renderer:
         abi.check(self._lib, self._lib.pt_debug_lights(self._h, fn, n, C.byref(args), buf.ctypes.data, out.ctypes.data))
         return out.view(abi.LIGHT_SAMPLE_DTYPE if fn == abi.PT_LIGHT_SAMPLE else abi.ENV_MISS_DTYPE)
 
+    def debugShading(self, records):
+        """pt_debug_shading on the scene of the started render.  `records` is an array of abi.SHADE_PROBE_IN_DTYPE: a hit (instance, primitive,
+        u, v) and its ray (o, d, t); returns as many records of abi.SHADE_PROBE_OUT_DTYPE: hitPos, the shading frame, wo and the shading context
+        as the shade and AOV kernels compute them for that hit, and the triangle's material class."""
+        rec = np.ascontiguousarray(records, dtype=abi.SHADE_PROBE_IN_DTYPE).reshape(-1)
+        out = np.empty(len(rec) * abi.PT_SHADE_PROBE_OUT_WORDS, np.uint32)
+        abi.check(self._lib, self._lib.pt_debug_shading(self._h, len(rec), rec.ctypes.data, out.ctypes.data))
+        return out.view(abi.SHADE_PROBE_OUT_DTYPE)
+
     # bloom (include/ptamd.h, an additive extension of ABI 5): no reference counterpart
     def bloomOptions(self):
         """The options in effect (pt_default_bloom_options until setBloomOptions is called)."""

@@ -10,4 +10,5 @@
 #include "layout_probe.cpp"   // lp_*:  the tile / segment / radiance-buffer index maps, plan_queues
 #include "math_emu.cpp"       // emu_math_batch: the math layer as pt_debug_math evaluates it
 #include "light_emu.cpp"      // emu_light_probe: the light sampling as pt_debug_lights evaluates it
+#include "shade_emu.cpp"      // emu_shade_probe: the shading frame and context as pt_debug_shading evaluates them
 #include "start_plan_probe.cpp"  // sp_*: the decisions of pt_start_render (host_scene.h): structure, camera lists, queue budget

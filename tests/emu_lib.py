@@ -37,6 +37,7 @@ def bind_lights(L):
     L.emu_light_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(abi.LightProbeArgs), C.c_void_p, C.c_void_p]
     L.emu_get_env_alias.restype = C.c_uint64
     L.emu_get_env_alias.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.emu_shade_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]      # tests/emu/shade_emu.cpp
     return L
 
 
@@ -87,6 +88,14 @@ class EmuScene:
             if self.L.emu_light_probe(self.h, fn, n, a, i, o) != 0:
                 raise RuntimeError("emu_light_probe refused the call")
         return light_lib.probe(call, fn, records, **args)
+
+    def debugShading(self, records):
+        """emu_shade_probe, the host build of pt_shade_probe.h: Renderer.debugShading's argument and result"""
+        rec = np.ascontiguousarray(records, dtype=abi.SHADE_PROBE_IN_DTYPE).reshape(-1)
+        out = np.full(len(rec) * abi.PT_SHADE_PROBE_OUT_WORDS, 0xdeadbeef, np.uint32)
+        if self.L.emu_shade_probe(self.h, len(rec), rec.ctypes.data, out.ctypes.data) != 0:
+            raise RuntimeError("emu_shade_probe refused the call")
+        return out.view(abi.SHADE_PROBE_OUT_DTYPE)
 
     def debug_sample(self, sample_idx):
         B = self.params.max_bounces

@@ -107,6 +107,7 @@ def lib():
     L.orc_light_sample.restype = None
     L.orc_light_sample.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(abi.LightProbeArgs), C.c_void_p, C.c_void_p]
     L.orc_env_miss.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(abi.LightProbeArgs), C.c_void_p, C.c_void_p]
+    L.orc_shade_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -167,6 +168,14 @@ class OracleScene:
         import light_lib
         return light_lib.probe(lambda n, a, i, o: (self.L.orc_light_sample if fn == abi.PT_LIGHT_SAMPLE else self.L.orc_env_miss)(self.h, n, a, i, o),
                                fn, records, **args)
+
+    def debugShading(self, records):
+        """orc_shade_probe: Renderer.debugShading's argument and result"""
+        rec = np.ascontiguousarray(records, dtype=abi.SHADE_PROBE_IN_DTYPE).reshape(-1)
+        out = np.full(len(rec) * abi.PT_SHADE_PROBE_OUT_WORDS, 0xdeadbeef, np.uint32)
+        if self.L.orc_shade_probe(self.h, len(rec), rec.ctypes.data, out.ctypes.data) != 0:
+            raise RuntimeError("orc_shade_probe refused the call")
+        return out.view(abi.SHADE_PROBE_OUT_DTYPE)
 
     def render(self, first_sample, nsamples, acc=None, acc_n0=0, threads=None, count_traversal=False):
         if acc is None:
