@@ -10,7 +10,8 @@
 //   k_karras    ... or the Karras 2012 radix tree ($PTAMD_RADIX_TREE, or PLOC gave up): one thread per internal node, duplicate codes split by position
 //   k_refit     its bottom-up AABB union, second arrival at a node proceeds (agent-scope fences around the counter)
 //   k_emit_sah_head, k_emit_sah_dev   surface-area-guided collapse of either binary tree to 6- or 4-wide 64-byte nodes (8-bit quantised,
-//               inflated child boxes), dense in BFS order (collapse_dev) + triangles in leaf order
+//               inflated child boxes), dense in BFS order (collapse_dev) + triangles in leaf order.  6-wide: by least area-weighted node count
+//               (pt_collapse.h; its table is filled where the PLOC kernels create a node) unless $PTAMD_COLLAPSE_AREA; 4-wide: by the area rule
 //   k_emit      the even-depth 4-wide collapse: only for a radix tree whose guided collapse is deeper than the traversal stack
 //
 // Not on the per-sample hot path: runs once per pt_start_render; timed separately (pt_stats.bvh_build_ms).
@@ -21,6 +22,7 @@
 
 
 #include "kernels.h"
+#include "pt_collapse.h"
 #include "pt_shade.h"
 
 namespace pt {
@@ -28,6 +30,7 @@ namespace pt {
 namespace {
 
 struct alignas(16) Box { float lo[3]; float hi[3]; float _pad[2]; };
+static_assert(kCollapseLeafBit == kLeafBit, "pt_collapse.h reads binary refs");
 
 __device__ __forceinline__ int float_to_ordered(float f) {
   int i = __float_as_int(f);
@@ -284,10 +287,7 @@ template <int W>
 __device__ __forceinline__ int open_by_area(uint32_t i, const uint2* __restrict__ children, const Box* __restrict__ leaf_boxes,
                                             const uint32_t* __restrict__ order, const Box* __restrict__ node_boxes, uint32_t (&refs)[W], Box (&bx)[W]) {
   auto box_of = [&](uint32_t ref) { return (ref & kLeafBit) ? leaf_boxes[order[ref & ~kLeafBit]] : node_boxes[ref]; };
-  auto half_area = [](const Box& b) {
-    const float x = b.hi[0] - b.lo[0], y = b.hi[1] - b.lo[1], z = b.hi[2] - b.lo[2];
-    return x * y + y * z + z * x;
-  };
+  auto half_area = [](const Box& b) { return collapse_half_area(b.lo, b.hi); };
   const uint2 ch = children[i];
   refs[0] = ch.x; bx[0] = box_of(ch.x);
   refs[1] = ch.y; bx[1] = box_of(ch.y);
@@ -344,23 +344,41 @@ __device__ __forceinline__ void emit_sah_node(uint32_t t, const uint2* __restric
   }
   nodes[dense] = quantize_node4(boxes, refs, count);
 }
-// The 6-wide form (BvhNode6; one-BVH structure, device-driven build): open the internal child with the largest surface area until six
-// slots are used; internal children first, then the leaves.  One reservation of consecutive node records AND one of consecutive triangle
+// The 6-wide form (BvhNode6; one-BVH structure, device-driven build): the children the cost table chose (kForm6Cost: pt_collapse.h, words[] =
+// the decisions PLOC left per binary node), or, by the area rule (kForm6Area), the internal child with the largest surface area opened until six
+// slots are used; internal children first, then the leaves.  kForm6AreaLevels is the area rule counting its levels for build_tree: it queues
+// the children and writes neither nodes nor tri_perm.  One reservation of consecutive node records AND one of consecutive triangle
 // slots per node: the leaf children of a node become base_leaf + 0, 1, ... (tri_perm[slot] = the triangle's position in the Morton
 // order; k_reorder_tris6 places the triangles accordingly).
+enum : int { kForm4 = 0, kForm6Area = 1, kForm6AreaLevels = 2, kForm6Cost = 3 };
+template <int FORM>
 __device__ __forceinline__ void emit_sah_node6(uint32_t t, const uint2* __restrict__ q_in, uint2* __restrict__ q_out, uint32_t* n_out, uint32_t* leaf_out,
                                                uint32_t next_base, const uint2* __restrict__ children, const Box* __restrict__ leaf_boxes,
-                                               const uint32_t* __restrict__ order, const Box* __restrict__ node_boxes, uint32_t* __restrict__ tri_perm,
-                                               BvhNode* __restrict__ nodes) {
+                                               const uint32_t* __restrict__ order, const Box* __restrict__ node_boxes,
+                                               const uint32_t* __restrict__ words, uint32_t* __restrict__ tri_perm, BvhNode* __restrict__ nodes) {
   const uint32_t i = q_in[t].x, dense = q_in[t].y;
   uint32_t refs[6];
   Box bx[6];
-  const int count = open_by_area<6>(i, children, leaf_boxes, order, node_boxes, refs, bx);
+  int count;
+  if constexpr (FORM == kForm6Cost) {
+    count = collapse_expand(i, children, words, refs);
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+      if (k < count) bx[k] = (refs[k] & kLeafBit) ? leaf_boxes[order[refs[k] & ~kLeafBit]] : node_boxes[refs[k]];
+  } else {
+    count = open_by_area<6>(i, children, leaf_boxes, order, node_boxes, refs, bx);
+  }
   uint32_t n_int = 0;
   for (int k = 0; k < count; k++) n_int += (refs[k] & kLeafBit) ? 0u : 1u;
   const uint32_t n_leaf = (uint32_t)count - n_int;
   const uint32_t p_node = n_int ? atomicAdd(n_out, n_int) : 0u;
   const uint32_t p_leaf = n_leaf ? atomicAdd(leaf_out, n_leaf) : 0u;
+  if constexpr (FORM == kForm6AreaLevels) {
+    uint32_t a_int = 0;
+    for (int k = 0; k < count; k++)
+      if (!(refs[k] & kLeafBit)) { q_out[p_node + a_int] = make_uint2(refs[k], next_base + p_node + a_int); a_int++; }
+    return;
+  }
   Box3 boxes[6];
   uint32_t a_int = 0, a_leaf = 0;
   for (int k = 0; k < count; k++) {
@@ -403,17 +421,18 @@ __global__ void k_state_init(BuildState* st, uint32_t n, uint32_t tree_ok) {
 // The first kHeadLevels collapse levels (level l holds at most 4^l nodes: <= 1 024 up to level 5) in one single-block launch, block barriers
 // between the levels: a level is a chain of ~6 dependent loads whatever its size, so a launch per tiny level cost ~27 us each.
 constexpr uint32_t kHeadLevels = 6;
-template <bool W6>
+template <int FORM>
 __global__ void __launch_bounds__(1024) k_emit_sah_head(BuildState* st, uint32_t levels, uint2* q0, uint2* q1, uint32_t* level_count,
                                                          uint32_t ref_base, uint32_t leaf_tag, uint32_t remap, const uint2* __restrict__ children,
                                                          const Box* __restrict__ leaf_boxes, const uint32_t* __restrict__ order,
-                                                         const Box* __restrict__ node_boxes, uint32_t* __restrict__ tri_perm, BvhNode* __restrict__ nodes) {
+                                                         const Box* __restrict__ node_boxes, const uint32_t* __restrict__ words,
+                                                         uint32_t* __restrict__ tri_perm, BvhNode* __restrict__ nodes) {
   if (st->tree_ok == 0) return;
   uint32_t n_in = 1, before = 0;
   for (uint32_t level = 0; level < levels; level++) {
     if (threadIdx.x < n_in) {
-      if (W6) emit_sah_node6(threadIdx.x, (level & 1u) ? q1 : q0, (level & 1u) ? q0 : q1, &level_count[level], &st->leaf_count, before + n_in, children, leaf_boxes,
-                             order, node_boxes, tri_perm, nodes);
+      if constexpr (FORM != kForm4) emit_sah_node6<FORM>(threadIdx.x, (level & 1u) ? q1 : q0, (level & 1u) ? q0 : q1, &level_count[level], &st->leaf_count,
+                                                         before + n_in, children, leaf_boxes, order, node_boxes, words, tri_perm, nodes);
       else emit_sah_node(threadIdx.x, (level & 1u) ? q1 : q0, (level & 1u) ? q0 : q1, &level_count[level], before + n_in, ref_base, leaf_tag, remap, children,
                          leaf_boxes, order, node_boxes, nodes);
     }
@@ -426,18 +445,19 @@ __global__ void __launch_bounds__(1024) k_emit_sah_head(BuildState* st, uint32_t
 }
 
 // One collapse level, its size and numbering base read from the counts the levels before it left (level 0: the root alone).
-template <bool W6>
+template <int FORM>
 __global__ void __launch_bounds__(256) k_emit_sah_dev(BuildState* st, uint32_t level, const uint2* __restrict__ q_in,
                                                        uint2* __restrict__ q_out, uint32_t* level_count, uint32_t ref_base, uint32_t leaf_tag,
                                                        uint32_t remap, const uint2* __restrict__ children, const Box* __restrict__ leaf_boxes,
-                                                       const uint32_t* __restrict__ order, const Box* __restrict__ node_boxes, uint32_t* __restrict__ tri_perm,
-                                                       BvhNode* __restrict__ nodes) {
+                                                       const uint32_t* __restrict__ order, const Box* __restrict__ node_boxes,
+                                                       const uint32_t* __restrict__ words, uint32_t* __restrict__ tri_perm, BvhNode* __restrict__ nodes) {
   if (st->tree_ok == 0) return;  // PLOC gave up: the host falls back to the radix tree
   uint32_t n_in = 1, before = 0;            // nodes of this level, nodes of all levels before it
   for (uint32_t l = 0; l < level; l++) { before += n_in; n_in = st->level_count[l]; }
   const uint32_t t = blockIdx.x * 256 + threadIdx.x;
   if (t >= n_in) return;
-  if (W6) emit_sah_node6(t, q_in, q_out, &level_count[level], &st->leaf_count, before + n_in, children, leaf_boxes, order, node_boxes, tri_perm, nodes);
+  if constexpr (FORM != kForm4)
+    emit_sah_node6<FORM>(t, q_in, q_out, &level_count[level], &st->leaf_count, before + n_in, children, leaf_boxes, order, node_boxes, words, tri_perm, nodes);
   else emit_sah_node(t, q_in, q_out, &level_count[level], before + n_in, ref_base, leaf_tag, remap, children, leaf_boxes, order, node_boxes, nodes);
 }
 // triangles in the order the 6-wide collapse numbered them: slot -> position in the Morton order -> flattening index
@@ -473,6 +493,24 @@ __device__ __forceinline__ float merged_half_area(const Box& a, const Box& b) {
   const float y = fmaxf(a.hi[1], b.hi[1]) - fminf(a.lo[1], b.lo[1]);
   const float z = fmaxf(a.hi[2], b.hi[2]) - fminf(a.lo[2], b.lo[2]);
   return x * y + y * z + z * x;
+}
+// The new binary node idx's row of the collapse's cost table (pt_collapse.h), where a merge creates it: both children exist, and their rows
+// were written by a pass before this one.  cost[6 idx + k - 1] = F(idx, k), words[idx] = its decisions.  (cost == nullptr: no 6-wide
+// collapse will ask.)  Rows are read through the pointer they are written through: no __restrict__.
+__device__ __forceinline__ void collapse_row(uint32_t idx, uint32_t left, uint32_t right, const Box& m, float* cost, uint32_t* words) {
+  if (cost == nullptr) return;
+  float fl[kCollapseWidth], fr[kCollapseWidth], f[kCollapseWidth];
+  const bool leaf_l = (left & kLeafBit) != 0, leaf_r = (right & kLeafBit) != 0;
+  const float* row_l = cost + (size_t)kCollapseWidth * (leaf_l ? 0u : left);
+  const float* row_r = cost + (size_t)kCollapseWidth * (leaf_r ? 0u : right);
+#pragma unroll
+  for (int k = 0; k < kCollapseWidth; k++) {
+    fl[k] = leaf_l ? 0.0f : row_l[k];
+    fr[k] = leaf_r ? 0.0f : row_r[k];
+  }
+  words[idx] = collapse_step(collapse_half_area(m.lo, m.hi), fl, fr, f);
+#pragma unroll
+  for (int k = 0; k < kCollapseWidth; k++) cost[(size_t)kCollapseWidth * idx + k] = f[k];
 }
 __global__ void __launch_bounds__(256) k_ploc_init(uint32_t n, const Box* __restrict__ leaf_boxes, const uint32_t* __restrict__ order,
                                                     uint32_t* __restrict__ cl_ref, Box* __restrict__ cl_box) {
@@ -550,7 +588,7 @@ __global__ void __launch_bounds__(256) k_ploc_count_dev(const BuildState* __rest
 __global__ void __launch_bounds__(256) k_ploc_apply_dev(BuildState* __restrict__ st, uint32_t pass, uint32_t n, const uint32_t* __restrict__ nn,
                                                          const uint2* __restrict__ block_counts, uint32_t* __restrict__ ref0, uint32_t* __restrict__ ref1,
                                                          Box* __restrict__ box0, Box* __restrict__ box1, uint2* __restrict__ children,
-                                                         Box* __restrict__ node_boxes) {
+                                                         Box* __restrict__ node_boxes, float* cost, uint32_t* words) {
   __shared__ uint32_t s_m[4], s_k[4];
   __shared__ uint32_t s_red[4][256];
   const PlocSlot ps = st->ploc[pass & 1u];
@@ -607,8 +645,10 @@ __global__ void __launch_bounds__(256) k_ploc_apply_dev(BuildState* __restrict__
         for (int k = 0; k < 3; k++) { m.lo[k] = fminf(x.lo[k], y.lo[k]); m.hi[k] = fmaxf(x.hi[k], y.hi[k]); }
         m._pad[0] = m._pad[1] = 0.0f;
         if (idx < n - 1) {  // (always, when the counts are consistent; an inconsistent pass is abandoned above)
-          children[idx] = make_uint2(cl_ref[i], cl_ref[j]);
+          const uint32_t left = cl_ref[i], right = cl_ref[j];
+          children[idx] = make_uint2(left, right);
           node_boxes[idx] = m;
+          collapse_row(idx, left, right, m, cost, words);
         }
         out_ref[pos] = idx;
         out_box[pos] = m;
@@ -629,7 +669,7 @@ __global__ void __launch_bounds__(256) k_ploc_apply_dev(BuildState* __restrict__
 // to BuildState::tree_ok: one cluster is left and the root is the last node created, n - 2.
 __global__ void __launch_bounds__(1024) k_ploc_tail_dev(BuildState* __restrict__ st, uint32_t slot, uint32_t n, const uint32_t* __restrict__ ref0,
                                                          const uint32_t* __restrict__ ref1, const Box* __restrict__ box0, const Box* __restrict__ box1,
-                                                         uint2* __restrict__ children, Box* __restrict__ node_boxes) {
+                                                         uint2* __restrict__ children, Box* __restrict__ node_boxes, float* cost, uint32_t* words) {
   __shared__ Box s_box[2][kPlocTail];
   __shared__ uint32_t s_ref[2][kPlocTail];
   __shared__ uint32_t s_nn[kPlocTail];
@@ -687,6 +727,7 @@ __global__ void __launch_bounds__(1024) k_ploc_tail_dev(BuildState* __restrict__
         m._pad[0] = m._pad[1] = 0.0f;
         children[idx] = make_uint2(s_ref[a][i], s_ref[a][j]);
         node_boxes[idx] = m;
+        collapse_row(idx, s_ref[a][i], s_ref[a][j], m, cost, words);
         s_ref[a ^ 1][pos] = idx;
         s_box[a ^ 1][pos] = m;
       } else {
@@ -694,6 +735,9 @@ __global__ void __launch_bounds__(1024) k_ploc_tail_dev(BuildState* __restrict__
         s_box[a ^ 1][pos] = s_box[a][i];
       }
     }
+    // (the cost rows are the one thing a pass here reads back from GLOBAL memory: a later pass's merge, on another thread of this block,
+    // reads the rows this pass wrote; the boxes and refs it needs travel in LDS)
+    __threadfence_block();
     __syncthreads();
     if (n_merge == 0) break;  // (cannot happen: the globally closest pair is always mutual)
     base += n_merge;
@@ -725,11 +769,11 @@ static size_t dev_scratch_bytes(uint32_t n) {  // ploc_dev's cluster buffers, an
 }
 
 // The binary tree by PLOC over the Morton order `order` (n >= 2): fills children[] / node_boxes[] (n - 1 slots; the root is the last node
-// created, n - 2).  The host reads the state after each batch of passes (2 read-backs on C3).  *ok = false when it gave up there
+// created, n - 2) and, with `cost`, the collapse's cost table (cost[] 6 floats, words[] one word per binary node).  The host reads the state after each batch of passes (2 read-backs on C3).  *ok = false when it gave up there
 // (PlocSlot::ok, the pass limit); what the tail decides stays on the device (BuildState::tree_ok) and reaches the host with the collapse's
 // first read-back.
-static hipError_t ploc_dev(hipStream_t s, uint32_t n, const Box* leaf_boxes, const uint32_t* order, uint2* children, Box* node_boxes, BuildState* st,
-                           Arena& arena, bool* ok) {
+static hipError_t ploc_dev(hipStream_t s, uint32_t n, const Box* leaf_boxes, const uint32_t* order, uint2* children, Box* node_boxes, float* cost,
+                           uint32_t* words, BuildState* st, Arena& arena, bool* ok) {
   hipError_t err = hipSuccess;
   *ok = false;
   const size_t mark = arena.off;  // (everything taken here is handed back on return)
@@ -753,14 +797,14 @@ static hipError_t ploc_dev(hipStream_t s, uint32_t n, const Box* leaf_boxes, con
     for (uint32_t k = 0; k < batch; k++, pass++) {
       hipLaunchKernelGGL(k_ploc_nn_dev, dim3(blocks < 4096 ? blocks : 4096), dim3(256), 0, s, st, pass, box0, box1, nn);
       hipLaunchKernelGGL(k_ploc_count_dev, dim3(tiles), dim3(256), 0, s, st, pass, nn, block_counts);
-      hipLaunchKernelGGL(k_ploc_apply_dev, dim3(tiles), dim3(256), 0, s, st, pass, n, nn, block_counts, ref0, ref1, box0, box1, children, node_boxes);
+      hipLaunchKernelGGL(k_ploc_apply_dev, dim3(tiles), dim3(256), 0, s, st, pass, n, nn, block_counts, ref0, ref1, box0, box1, children, node_boxes, cost, words);
     }
     LB_CHECK(hipMemcpyAsync(&h, &st->ploc[pass & 1u], sizeof(PlocSlot), hipMemcpyDeviceToHost, s));
     LB_CHECK(hipStreamSynchronize(s));
     if (!h.ok || h.cur > bound) goto done;
     bound = h.cur;
   }
-  hipLaunchKernelGGL(k_ploc_tail_dev, dim3(1), dim3(1024), 0, s, st, pass & 1u, n, ref0, ref1, box0, box1, children, node_boxes);
+  hipLaunchKernelGGL(k_ploc_tail_dev, dim3(1), dim3(1024), 0, s, st, pass & 1u, n, ref0, ref1, box0, box1, children, node_boxes, cost, words);
   *ok = true;
 done:
   arena.off = mark;
@@ -781,18 +825,22 @@ static hipError_t radix_tree(hipStream_t s, uint32_t n, const uint64_t* keys, co
   return hipSuccess;
 }
 
-// Level-synchronous SAH collapse of the binary tree under `root` into nodes_out, 6-wide (`wide6`: BvhNode6 + tri_perm) or 4-wide: the head
+// Level-synchronous SAH collapse of the binary tree under `root` into nodes_out, 6-wide (`form` != kForm4: BvhNode6 + tri_perm; kForm6Cost by
+// words[], the decisions of the cost table; kForm6AreaLevels counts the area rule's nodes and levels and writes nothing) or 4-wide: the head
 // launch, then batches of levels with a read-back after each (1-2 on C3).  First batch: the levels a balanced tree has and eight more;
 // further batches of six while the last level still queued something.  *ok: *emitted nodes in *levels levels, root = dense node 0;
 // !*ok: the binary tree is not whole (BuildState::tree_ok) or the wide tree is deeper than the traversal stack holds.
-static hipError_t collapse_dev(hipStream_t s, uint32_t n, uint32_t root, bool wide6, uint32_t stack_capacity, const Box* leaf_boxes, const uint32_t* order,
-                               const uint2* children, const Box* node_boxes, uint2* q0, uint2* q1, uint32_t ref_base, uint32_t leaf_tag, uint32_t remap,
+static hipError_t collapse_dev(hipStream_t s, uint32_t n, uint32_t root, int form, uint32_t stack_capacity, const Box* leaf_boxes, const uint32_t* order,
+                               const uint2* children, const Box* node_boxes, const uint32_t* words, uint2* q0, uint2* q1, uint32_t ref_base, uint32_t leaf_tag, uint32_t remap,
                                BvhNode* nodes_out, uint32_t* tri_perm, BuildState* st, bool* ok, uint32_t* emitted, uint32_t* levels) {
   hipError_t err = hipSuccess;
   *ok = false;
   BuildState h;
-  const auto head_kernel = wide6 ? k_emit_sah_head<true> : k_emit_sah_head<false>;
-  const auto level_kernel = wide6 ? k_emit_sah_dev<true> : k_emit_sah_dev<false>;
+  const bool wide6 = form != kForm4;
+  const auto head_kernel = form == kForm6Cost ? k_emit_sah_head<kForm6Cost> : form == kForm6AreaLevels ? k_emit_sah_head<kForm6AreaLevels>
+                           : form == kForm6Area ? k_emit_sah_head<kForm6Area> : k_emit_sah_head<kForm4>;
+  const auto level_kernel = form == kForm6Cost ? k_emit_sah_dev<kForm6Cost> : form == kForm6AreaLevels ? k_emit_sah_dev<kForm6AreaLevels>
+                            : form == kForm6Area ? k_emit_sah_dev<kForm6Area> : k_emit_sah_dev<kForm4>;
   const uint32_t width = wide6 ? 6u : 4u;
   uint32_t allowed = std::min<uint32_t>(stack_capacity / (width - 1), kMaxLevels - 1);  // levels the traversal stack can hold (width - 1 pushes per level)
   if (wide6) if (const char* e = getenv("PTAMD_TEST_W6_LEVELS")) allowed = std::min<uint32_t>(allowed, (uint32_t)std::max(1, atoi(e)));  // test hook: makes the 6-wide
@@ -803,14 +851,14 @@ static hipError_t collapse_dev(hipStream_t s, uint32_t n, uint32_t root, bool wi
   bool finished = false;
   hipLaunchKernelGGL(k_seed_queue, dim3(1), dim3(kMaxLevels), 0, s, st, q0, root);
   if (head) hipLaunchKernelGGL(head_kernel, dim3(1), dim3(1024), 0, s, st, head, q0, q1, st->level_count, ref_base, leaf_tag, remap, children, leaf_boxes, order,
-                               node_boxes, tri_perm, nodes_out);
+                               node_boxes, words, tri_perm, nodes_out);
   for (uint32_t l = 0; l < head; l++) level_bound = grow(level_bound);
   uint32_t batch = (uint32_t)std::ceil(std::log((double)n) / std::log((double)width)) + 8;
   batch = batch > head ? batch - head : 1;
   while (!finished) {
     for (uint32_t k = 0; k < batch && level < allowed; k++, level++) {
       hipLaunchKernelGGL(level_kernel, dim3((level_bound + 255) / 256), dim3(256), 0, s, st, level, (level & 1u) ? q1 : q0, (level & 1u) ? q0 : q1, st->level_count,
-                         ref_base, leaf_tag, remap, children, leaf_boxes, order, node_boxes, tri_perm, nodes_out);
+                         ref_base, leaf_tag, remap, children, leaf_boxes, order, node_boxes, words, tri_perm, nodes_out);
       level_bound = grow(level_bound);
     }
     batch = 6;
@@ -852,7 +900,8 @@ static hipError_t tree_arena_bytes(uint32_t n, size_t* sort_bytes_out, size_t* b
     const size_t N = n;
     *bytes = Arena::pad(sizeof(int) * 8) + Arena::pad(2 * sizeof(uint32_t)) + 2 * Arena::pad(sizeof(uint64_t) * N) + 2 * Arena::pad(sizeof(uint32_t) * N) +
              Arena::pad(sizeof(uint2) * (N - 1)) + Arena::pad(sizeof(uint32_t) * (N - 1)) + Arena::pad(sizeof(uint32_t) * N) + Arena::pad(sizeof(uint32_t) * (N - 1)) +
-             Arena::pad(sizeof(Box) * (N - 1)) + 2 * Arena::pad(sizeof(uint2) * N) + Arena::pad(sort_bytes) + dev_scratch_bytes(n);
+             Arena::pad(sizeof(Box) * (N - 1)) + 2 * Arena::pad(sizeof(uint2) * N) + Arena::pad(sort_bytes) + dev_scratch_bytes(n) +
+             Arena::pad(sizeof(float) * kCollapseWidth * (N - 1)) + Arena::pad(sizeof(uint32_t) * (N - 1));  // (the cost table: 28 B per binary node)
   }
   if (sort_bytes_out) *sort_bytes_out = sort_bytes;
   return hipSuccess;
@@ -877,8 +926,11 @@ static hipError_t build_tree(hipStream_t s, uint32_t n, const Box* leaf_boxes, u
   bool ploc = use_ploc, ok = false;  // ploc: the binary tree in children[] is PLOC's (root n - 2), not the radix tree (root 0)
   Arena arena;
   auto radix = [&] { return radix_tree(s, n, keys_b, leaf_boxes, vals_b, children, parent_int, parent_leaf, node_boxes, flags, counters, st); };
-  auto collapse = [&](bool wide6) {
-    return collapse_dev(s, n, ploc ? n - 2 : 0u, wide6, stack_capacity, leaf_boxes, vals_b, children, node_boxes, queue[0], queue[1], ref_base, leaf_tag,
+  // the 6-wide collapse by least cost (pt_collapse.h) unless $PTAMD_COLLAPSE_AREA asks for the area rule; its table is filled only when it can be used
+  const bool by_cost = want6 && use_ploc && getenv("PTAMD_COLLAPSE_AREA") == nullptr;
+  float* cost = nullptr; uint32_t* words = nullptr;
+  auto collapse = [&](int form) {
+    return collapse_dev(s, n, ploc ? n - 2 : 0u, form, stack_capacity, leaf_boxes, vals_b, children, node_boxes, words, queue[0], queue[1], ref_base, leaf_tag,
                         remap ? 1u : 0u, nodes_out, tri_perm_out, st, &ok, &emitted, &levels);
   };
 
@@ -904,6 +956,7 @@ static hipError_t build_tree(hipStream_t s, uint32_t n, const Box* leaf_boxes, u
   for (int k = 0; k < 2; k++) queue[k] = arena.take<uint2>(n);
   sort_tmp = arena.take<char>(sort_bytes);
   st = arena.take<BuildState>(1);
+  if (by_cost) { cost = arena.take<float>((size_t)kCollapseWidth * (n - 1)); words = arena.take<uint32_t>(n - 1); }
 
   hipLaunchKernelGGL(k_init_bounds, dim3(1), dim3(64), 0, s, bounds);
   hipLaunchKernelGGL(k_bounds, dim3(blocks < 256 ? blocks : 256), dim3(256), 0, s, leaf_boxes, n, bounds);
@@ -911,16 +964,29 @@ static hipError_t build_tree(hipStream_t s, uint32_t n, const Box* leaf_boxes, u
   LB_CHECK(hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, keys_a, keys_b, vals_a, vals_b, (int)n, 0, 63, s));
 
   // the binary tree
-  if (ploc) LB_CHECK(ploc_dev(s, n, leaf_boxes, vals_b, children, node_boxes, st, arena, &ploc));
+  if (ploc) LB_CHECK(ploc_dev(s, n, leaf_boxes, vals_b, children, node_boxes, cost, words, st, arena, &ploc));
   if (!ploc) LB_CHECK(radix());
   // the wide tree: 6-wide from a PLOC tree when asked for; 4-wide on the same binary tree when that is deeper than the stack (five pushes per
-  // level, the 4-wide form needs three); a PLOC tree too deep (or not whole) even so is a pathological cluster tree: the radix tree instead
-  if (ploc && want6) { LB_CHECK(collapse(true)); info->wide6 = ok; }
-  if (!ok) LB_CHECK(collapse(false));
+  // level, the 4-wide form needs three); a PLOC tree too deep (or not whole) even so is a pathological cluster tree: the radix tree instead.
+  // The AREA rule stays the arbiter of the width: a tree whose area-rule collapse is too deep is built 4-wide whatever the least-cost collapse
+  // would have made of it (a count of the area rule's levels decides; nothing is written); where it fits, the least-cost collapse is
+  // adopted when its own levels fit too and it has no more nodes than the area rule's tree (what a ray pays is the AREA-weighted node count: a
+  // cheaper tree may hold more, smaller nodes — `scatter` at 31 slots: 12 against 11 — and the node array of a render never grows by this
+  // choice); the area rule's tree is built otherwise.
+  if (ploc && want6) {
+    LB_CHECK(collapse(by_cost ? kForm6AreaLevels : kForm6Area));
+    if (ok && by_cost) {
+      const uint32_t area_nodes = emitted;
+      LB_CHECK(collapse(kForm6Cost));
+      if (!ok || emitted > area_nodes) LB_CHECK(collapse(kForm6Area));
+    }
+    info->wide6 = ok;
+  }
+  if (!ok) LB_CHECK(collapse(kForm4));
   if (!ok && ploc) {
     ploc = false;
     LB_CHECK(radix());
-    LB_CHECK(collapse(false));
+    LB_CHECK(collapse(kForm4));
   }
   if (!ok) {
     // pathological radix tree: the even-depth collapse bounds the 4-wide depth by half the binary depth (nodes keep their

@@ -2,7 +2,7 @@
 # switched to, and with the library built under -DPT_EXACT_RAY_RCP (IEEE divisions for the ray's reciprocal direction instead of v_rcp_f32: ADVICE r5;
 # build it first on the authoring box: bash tools/build_variant.sh exact_rcp -DPT_EXACT_RAY_RCP); "soak": tests/soak_restarts.py afterwards
 tag=${1:-r06}
-for v in PTAMD_BVH4 PTAMD_RADIX_TREE PTAMD_TWO_LEVEL PTAMD_NO_PAIRS PTAMD_TEX_NATIVE; do
+for v in PTAMD_BVH4 PTAMD_RADIX_TREE PTAMD_TWO_LEVEL PTAMD_NO_PAIRS PTAMD_TEX_NATIVE PTAMD_COLLAPSE_AREA; do
   env $v=1 timeout -k 10 900 python -m pytest tests -m gpu -q > gpurun_out/suite_${tag}_$v.log 2>&1
   echo "$v: $(tail -1 gpurun_out/suite_${tag}_$v.log)"
 done
