@@ -1,4 +1,4 @@
-// kernels.h — host-visible launchers of the wavefront kernels (kernels.hip) and the LBVH builder (lbvh.hip).
+// kernels.h — host-visible launchers of the wavefront kernels (kernels.hip, trace_kernels.hip) and the LBVH builder (lbvh.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -49,9 +49,12 @@ void launch_raygen(hipStream_t s, uint32_t grid, const DeviceScene& S, PathState
 // `bounce_closest`) and, if do_shadow, of the shadow queue consumed at `bounce_shadow`.
 void launch_chunk_tables(hipStream_t s, Segments seg, uint32_t cur, BatchCounters* ctr, uint32_t bounce_closest,
                          uint32_t bounce_shadow, bool do_shadow);
-// What the host has to know of the structure the trace kernels walk (pt_bvh.h Walk4 / Walk6 / WalkTwoLevel, as kernels.hip was compiled)
+// What the host has to know of the structure the trace kernels walk (pt_bvh.h Walk4 / Walk6 / WalkTwoLevel, as the kernels were compiled)
 struct TraceWalk {
-  uint32_t block_threads, closest_blocks_per_cu, shadow_blocks_per_cu;
+  uint32_t block_threads;
+  uint32_t closest_blocks_per_cu;         // k_trace_closest_unlisted and k_trace_ao (kernels.hip)
+  uint32_t closest_trace_blocks_per_cu;   // k_trace_closest (trace_kernels.hip: built without SLP packing, one wave per SIMD more)
+  uint32_t shadow_blocks_per_cu;
   bool blocks_tunable;         // $PTAMD_CLOSEST_BLOCKS_PER_CU / $PTAMD_SHADOW_BLOCKS_PER_CU apply (not where one block fills a CU's LDS)
   uint32_t pushes_per_level, exit_entries;   // stack entries a tree of L levels needs: L * pushes_per_level + exit_entries
 };

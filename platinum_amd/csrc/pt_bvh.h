@@ -114,8 +114,17 @@ PT_HD float slab_entry(const float lo[3], const float hi[3], vec3 o, vec3 inv, f
 // r4: with two triangles per leaf slot the closest-hit kernel wants 78 registers; at 7 waves per SIMD (72) it spills 5 of them, at 6 none —
 // measured per 128-spp step, C3 / C2: closest 112.5 / 36.8 ms at 7 blocks per CU, 109.3 / 35.3 at 6; shadow (71 registers, no spills) 50.8 /
 // 21.4 at 7, 52.2 / 21.5 at 6.  So each kernel gets its own occupancy.
+// r25: those registers were the price of LLVM's SLP pass, which packs the vec3 arithmetic into v_pk_* instructions on even-aligned register
+// pairs.  k_trace_closest and k_trace_shadow are now built in a translation unit of their own without it (trace_kernels.hip, Makefile): the
+// closest-hit kernel needs 69 registers there, no spill, and is built and launched at PT_CLOSEST_TRACE_WAVES = 7 blocks per CU
+// (7 x 22 528 B of LDS fit the CU's 160 KB, as for the shadow kernel; figures in profiles/r25_no_slp.md).  PT_CLOSEST_WAVES stays the launch
+// bound and the grid of the closest-hit walks that kernels.hip still builds with SLP packing, at the registers they had:
+// k_trace_closest_unlisted (76) and k_trace_ao (80).
 #ifndef PT_CLOSEST_WAVES
 #define PT_CLOSEST_WAVES 6
+#endif
+#ifndef PT_CLOSEST_TRACE_WAVES
+#define PT_CLOSEST_TRACE_WAVES PT_TRACE_WAVES
 #endif
 #ifndef PT_SHADOW_WAVES
 #define PT_SHADOW_WAVES PT_TRACE_WAVES
@@ -163,7 +172,7 @@ struct TravState; struct TraversalCount;
 // and node / leaf: one node step, one triangle test from the leaf queue.
 struct Walk4 {
   static constexpr bool kTwoLevel = false;
-  static constexpr int kThreads = kBlock, kClosestBlocksPerCu = PT_CLOSEST_WAVES, kShadowBlocksPerCu = PT_SHADOW_WAVES;
+  static constexpr int kThreads = kBlock, kClosestBlocksPerCu = PT_CLOSEST_WAVES, kClosestTraceBlocksPerCu = PT_CLOSEST_TRACE_WAVES, kShadowBlocksPerCu = PT_SHADOW_WAVES;
   static constexpr int kStackRows = kLdsStack, kPendRows = kPendLeaves, kRoom = 4;
   static constexpr uint32_t kLdsNodes = 0, kPushesPerLevel = 3, kExitEntries = 0;
   template <bool COUNT> static PT_HD void node(const BvhNode* __restrict__ nodes, TravState& ts, TraversalCount* cnt);
@@ -171,7 +180,7 @@ struct Walk4 {
 };
 struct Walk6 {
   static constexpr bool kTwoLevel = false;
-  static constexpr int kThreads = kBlock, kClosestBlocksPerCu = PT_CLOSEST_WAVES, kShadowBlocksPerCu = PT_SHADOW_WAVES;
+  static constexpr int kThreads = kBlock, kClosestBlocksPerCu = PT_CLOSEST_WAVES, kClosestTraceBlocksPerCu = PT_CLOSEST_TRACE_WAVES, kShadowBlocksPerCu = PT_SHADOW_WAVES;
   static constexpr int kStackRows = kLdsStack6, kPendRows = kPendLeaves6, kRoom = 1;
   static constexpr uint32_t kLdsNodes = 0, kPushesPerLevel = 5, kExitEntries = 0;
   template <bool COUNT> static PT_HD void node(const BvhNode* __restrict__ nodes, TravState& ts, TraversalCount* cnt);
@@ -179,7 +188,7 @@ struct Walk6 {
 };
 struct WalkTwoLevel {   // 4-wide nodes: a TLAS over instances, one object-space BLAS per mesh; an exit marker under every instance entered
   static constexpr bool kTwoLevel = true;
-  static constexpr int kThreads = PT_TWO_BLOCK, kClosestBlocksPerCu = PT_TWO_BLOCKS_PER_CU, kShadowBlocksPerCu = PT_TWO_BLOCKS_PER_CU;
+  static constexpr int kThreads = PT_TWO_BLOCK, kClosestBlocksPerCu = PT_TWO_BLOCKS_PER_CU, kClosestTraceBlocksPerCu = PT_TWO_BLOCKS_PER_CU, kShadowBlocksPerCu = PT_TWO_BLOCKS_PER_CU;
   static constexpr int kStackRows = kLdsStack, kPendRows = kPendLeaves, kRoom = 4;
   static constexpr uint32_t kLdsNodes = PT_TWO_LDS_NODES, kPushesPerLevel = 3, kExitEntries = 1;
   template <bool COUNT> static PT_HD void node(const BvhNode* __restrict__ nodes, TravState& ts, TraversalCount* cnt);

@@ -145,7 +145,7 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
       launch_chunk_tables(s, seg, 0, ctr, 0, 0, false);
     }
     ScopedTimer t(r, K_CLOSEST);
-    launch_trace_closest(s, r->closest_grid, S, r->path_state(0), r->hit.p, seg, 0u, ctr, 0u, r->spill.p, hitlog, S.width * S.height, count);
+    launch_trace_closest(s, count ? r->closest_grid : r->closest_trace_grid, S, r->path_state(0), r->hit.p, seg, 0u, ctr, 0u, r->spill.p, hitlog, S.width * S.height, count);
   }
   // The first-hit passes of a render batch: the camera rays' hits, read from the queue before k_shade consumes it.
   if (mode == BATCH_RENDER) {
@@ -174,7 +174,7 @@ int enqueue_batch(pt_renderer* r, uint32_t first, uint32_t ns, uint32_t n0, Batc
   for (uint32_t b = 0; b < S.max_bounces; b++) {
     if (b != 0) {
       ScopedTimer t(r, K_CLOSEST);
-      launch_trace_closest(s, r->closest_grid, S, r->path_state(cur), r->hit.p, seg, (uint32_t)cur, ctr, b, r->spill.p, hitlog, S.width * S.height, count);
+      launch_trace_closest(s, count ? r->closest_grid : r->closest_trace_grid, S, r->path_state(cur), r->hit.p, seg, (uint32_t)cur, ctr, b, r->spill.p, hitlog, S.width * S.height, count);
     }
     {
       ScopedTimer t(r, K_SHADE);
@@ -652,6 +652,8 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
   r->shade_grid = (uint32_t)r->num_cu * shade_blocks_per_cu();     // as many blocks as k_shade's registers / LDS keep resident
   r->primary_grid = (uint32_t)r->num_cu * primary_blocks_per_cu();
   r->closest_grid = (uint32_t)r->num_cu * (r->walk.blocks_tunable && r->closest_blocks_asked ? r->closest_blocks_asked : r->walk.closest_blocks_per_cu);
+  // (k_trace_closest's own grid: it is built for one block per CU more than the closest-hit walks of kernels.hip, which keep closest_grid)
+  r->closest_trace_grid = (uint32_t)r->num_cu * (r->walk.blocks_tunable && r->closest_blocks_asked ? r->closest_blocks_asked : r->walk.closest_trace_blocks_per_cu);
   r->shadow_grid = (uint32_t)r->num_cu * (r->walk.blocks_tunable && r->shadow_blocks_asked ? r->shadow_blocks_asked : r->walk.shadow_blocks_per_cu);
   r->nstats = std::max(std::max(r->grid, r->primary_grid) * (kBlock / 64), r->shade_grid * (shade_block_threads() / 64));
   for (int k = 0; k < 2; k++) {
@@ -670,7 +672,7 @@ int allocate_buffers(pt_renderer* r, const pt_render_params* p) {
   // (max_bounces + 1 rows: the table pass after the LAST bounce's k_shade still sorts for a bounce nobody runs, and reads that row)
   PT_HIP(r->shade_cost.alloc((size_t)r->nseg * (r->S.max_bounces + 1u)));
   PT_HIP(hipMemsetAsync(r->shade_cost.p, 0, sizeof(uint32_t) * r->shade_cost.n, r->stream));   // no batch of this render has been shaded yet
-  PT_HIP(r->spill.alloc((size_t)std::max(r->closest_grid, r->shadow_grid) * r->walk.block_threads * kSpillStack));  // per-thread HBM stack slab behind the LDS stack
+  PT_HIP(r->spill.alloc((size_t)std::max(std::max(r->closest_grid, r->closest_trace_grid), r->shadow_grid) * r->walk.block_threads * kSpillStack));  // per-thread HBM stack slab behind the LDS stack
   PT_HIP(hipMemsetAsync(r->wave_stats.p, 0, sizeof(WaveStats) * r->nstats, r->stream));
   if (p->external_accumulator) {
     r->acc = (vec4*)p->external_accumulator;
@@ -1063,7 +1065,7 @@ int dev_debug_ao(pt_renderer* r, uint32_t sample_idx, float* origins, float* dir
   seg.nsamples = 1;
   launch_camera_raygen(r, seg, sample_idx, 1, nullptr);
   launch_chunk_tables(s, seg, 0, r->ctr.p, 0, 0, false);
-  launch_trace_closest(s, r->closest_grid, r->S, r->path_state(0), r->hit.p, seg, 0, r->ctr.p, 0, r->spill.p, nullptr, npix, false);
+  launch_trace_closest(s, r->closest_trace_grid, r->S, r->path_state(0), r->hit.p, seg, 0, r->ctr.p, 0, r->spill.p, nullptr, npix, false);
   launch_trace_ao(s, r->closest_grid, r->S, r->path_state(0), r->hit.p, seg, r->ctr.p, r->spill.p, r->Obuf.p, r->ao_distance, log.p, npix);
   launch_ao_scatter(s, r->grid, r->S.width, r->path_state(0), r->hit.p, seg, r->Obuf.p, st.p);
   launch_fold_counters(s, r->ctr.p, r->totals.p + 1, seg, false);  // clears the per-wave statistics (scratch slot), as pt_trace_primary
@@ -1392,7 +1394,7 @@ int dev_trace_primary(pt_renderer* r, uint32_t sample_idx, pt_hit_record* out) {
   seg.nsamples = 1;
   launch_camera_raygen(r, seg, sample_idx, 1, nullptr);
   launch_chunk_tables(s, seg, 0, r->ctr.p, 0, 0, false);
-  launch_trace_closest(s, r->closest_grid, r->S, r->path_state(0), r->hit.p, seg, 0, r->ctr.p, 0, r->spill.p, nullptr, npix, false);
+  launch_trace_closest(s, r->closest_trace_grid, r->S, r->path_state(0), r->hit.p, seg, 0, r->ctr.p, 0, r->spill.p, nullptr, npix, false);
   launch_hit_records(s, r->grid, r->S, r->path_state(0), r->hit.p, seg, rec.p);
   launch_fold_counters(s, r->ctr.p, r->totals.p + 1, seg, false);  // clears the per-wave statistics (scratch slot)
   PT_HIP(hipGetLastError());

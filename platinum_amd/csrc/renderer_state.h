@@ -224,7 +224,7 @@ struct pt_renderer {
   pt_camera_list_stats cam_stats{};
   uint32_t primary_grid = 0;
   TraceWalk walk{};   // of the structure in use (kernels.h trace_walk; set with the build)
-  uint32_t closest_grid = 0, shadow_grid = 0, closest_blocks_asked = 0, shadow_blocks_asked = 0;  // persistent trace grids, each sized for its kernel's occupancy (asked: $PTAMD_*_BLOCKS_PER_CU, 0 = unset)
+  uint32_t closest_grid = 0, closest_trace_grid = 0, shadow_grid = 0, closest_blocks_asked = 0, shadow_blocks_asked = 0;  // persistent trace grids, each sized for its kernel's occupancy (asked: $PTAMD_*_BLOCKS_PER_CU, 0 = unset)
   uint32_t last_batch_ns = 0, last_batch_first = 0;  // the batch Lbuf holds ($PTAMD_DEBUG_PIXEL)
   uint32_t nseg = 0, tiles_per_seg = 1, seg_bands = 4, tiles_per_seg_override = 0, nstats = 0, seg_cap = 0, blocks_per_cu = 6, shade_grid = 0, refill_threshold = 48;
   DevBuf<BatchCounters> ctr;

@@ -13,6 +13,7 @@ for o in $(sed -n 's/^OBJS = //p' Makefile); do
   u=${o%.o}
   if [ -f $u.hip ]; then
     extra=; [ $u = kernels ] && extra="-mllvm -disable-machine-licm"   # same flags as the Makefile's kernels.o
+    [ $u = trace_kernels ] && extra="-mllvm -disable-machine-licm -fno-slp-vectorize"   # ... and as its trace_kernels.o
     /opt/rocm/bin/hipcc $F $extra "$@" -c $u.hip -o /tmp/${u}_$tag.o
     o=/tmp/${u}_$tag.o
   fi
