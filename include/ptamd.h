@@ -515,6 +515,36 @@ int pt_plan_bloom(uint32_t width, uint32_t height, uint32_t levels, pt_bloom_pla
 int pt_debug_bloom(pt_renderer* r, const float* rgba, uint32_t width, uint32_t height, const pt_bloom_options* options, float* out,
                    float* pyramid_out);
 
+/* ---- sun and sky: a single-scattering atmosphere as environment map (NEW, an additive extension of ABI 5: two entry points and two
+ * structs) ----
+ * pt_generate_sky fills a width x height lat-long RGBA32F image in the environment map's own layout (texel (x, y) looks along
+ * uvToRayDir((x + 1/2) / w, (y + 1/2) / h), the direction whose miss lookup lands on its centre); the caller hands it to the renderer as
+ * the snapshot's env_texture like any other RGBA32F environment.  One kernel launch on the renderer's stream, one lane per texel; the
+ * model, its constants and the order of every sum are DESIGN.md section 3m.  Lengths in km; the three channels are the render's
+ * working-space rgb as given.  The sun stands at s = (-cos a cos e, sin e, -sin a cos e): column a / 2pi * w, row (pi/2 - e) / pi * h.
+ * The disc has the radius alpha_eff = max(sun_angular_radius, pi / height) and is drawn by 4 x 4 coverage per texel, its radiance
+ * sun_intensity * T / Omega_d with Omega_d the DISCRETE solid angle of the covered texels: the disc's irradiance is sun_intensity times
+ * the coverage-weighted mean transmittance at every map size.  Every output is finite and >= 0, alpha is 1.
+ * Needs only pt_create.  PT_ERR_INVALID_ARGUMENT, before the renderer is looked at: options outside the ranges below, a NaN anywhere, an
+ * image outside 1..2^26 texels, a null options or rgba_out; then a null renderer. */
+typedef struct pt_sky_options {
+  float sun_elevation, sun_azimuth;   /* radians; elevation in [-pi/2, pi/2], azimuth any finite value (reduced modulo 2 pi in double) */
+  float sun_angular_radius;           /* default 0.004712 (0.27 deg); in (0, 0.2] */
+  float sun_intensity;                /* irradiance of the sun above the atmosphere, per channel; default 1; finite, >= 0 */
+  uint32_t sun_disc;                  /* default 1: draw the disc; 0: sky and ground only */
+  float altitude_km;                  /* default 0.001; in [0.001, 60] */
+  float air_density, dust_density, ozone_density;   /* defaults 1; in [0, 10] */
+  float ground_albedo;                /* default 0.3; in [0, 1] */
+} pt_sky_options;
+typedef struct pt_sky_stats {
+  float sun_direction[3]; float sun_radius_used;   /* s; alpha_eff */
+  double sun_solid_angle;                          /* Omega_d */
+  uint32_t sun_texels; float kernel_ms;            /* texels with coverage > 0; the kernel's time by events */
+} pt_sky_stats;
+void pt_default_sky_options(pt_sky_options* o);   /* elevation 0.5, azimuth 0, the defaults above */
+int pt_generate_sky(pt_renderer* r, const pt_sky_options* options, uint32_t width, uint32_t height, float* rgba_out,
+                    pt_sky_stats* stats_out /* may be NULL */);
+
 /* ---- math probe (NEW, an additive extension of ABI 5: one entry point and one enum) ----
  * Parity surface: the deterministic fp32 math, the sample warps and the Halton sequence of the kernels, evaluated on the device on their own.
  * One elementwise launch on the renderer's stream computes function `fn` on n elements: a[i] (and b[i] for a function of two arguments) in,

@@ -62,6 +62,8 @@
  *   (no counterpart; the camera type of a scene editor)           pt_camera_projection& projection() / setProjection(...), renderProjection(): orthographic,
  *                                                                panoramic and fisheye cameras beside the perspective one (ptamd.h, ABI 5 extension);
  *                                                                handed over at startRender
+ *   (no counterpart; the "sun and sky" light of a scene editor)   generateSky(options, width, height): a single-scattering atmosphere as a lat-long
+ *                                                                environment image, generated on the device (ptamd.h, ABI 5 extension)
  *   (no counterpart; the "render pass" drop-down of a viewport)    pt_view_options& viewOptions(), viewStats(): what the target shows of the AOVs, the
  *                                                                mattes, the film's alpha and the sampling (ptamd.h, ABI 5 extension); handed
  *                                                                over whenever a target is asked for
@@ -363,6 +365,15 @@ public:
     if (check(pt_debug_ao(m_pt, sampleIdx, origins.data(), directions.data(), state.data()))) return true;
     origins.clear(); directions.clear(); state.clear();
     return false;
+  }
+  // Sun and sky (ptamd.h, an additive extension of ABI 5): the width x height lat-long RGBA32F image of a single-scattering atmosphere under
+  // `o`, in the environment map's layout (hand it to the scene as its environment texture); empty on failure.  Needs no started render.  Blocks.
+  [[nodiscard]] std::vector<float> generateSky(const pt_sky_options& o, uint32_t width, uint32_t height, pt_sky_stats* stats = nullptr) const {
+    std::vector<float> out;
+    if (!m_pt || width == 0 || height == 0 || (uint64_t)width * height > (1ull << 26)) return out;
+    out.resize((size_t)width * height * 4);
+    if (!check(pt_generate_sky(m_pt, &o, width, height, out.data(), stats))) out.clear();
+    return out;
   }
   // Pass views (ptamd.h, an additive extension of ABI 5): `view` chooses what presentRenderTarget / readbackRenderTarget show: the beauty,
   // or the albedo, the normals, the depth, the film's alpha, the ID mattes, the sample counts or the noise estimate the render keeps.  A view

@@ -299,6 +299,21 @@ class AoStats(C.Structure):
 
 AO_MISS, AO_OCCLUDED, AO_OPEN = 0, 1, 2   # pt_debug_ao's state per camera ray
 
+
+class SkyOptions(C.Structure):
+    """pt_sky_options: the sun (radians; irradiance above the atmosphere), the observer's altitude in km, the densities of air, dust and
+    ozone relative to the standard atmosphere, and the ground's albedo (pt_generate_sky)."""
+    _fields_ = [("sun_elevation", C.c_float), ("sun_azimuth", C.c_float), ("sun_angular_radius", C.c_float), ("sun_intensity", C.c_float),
+                ("sun_disc", C.c_uint32), ("altitude_km", C.c_float), ("air_density", C.c_float), ("dust_density", C.c_float),
+                ("ozone_density", C.c_float), ("ground_albedo", C.c_float)]
+
+
+class SkyStats(C.Structure):
+    """pt_sky_stats: the sun's direction, the disc radius in use, its discrete solid angle, the texels it covers and the kernel's time."""
+    _fields_ = [("sun_direction", C.c_float * 3), ("sun_radius_used", C.c_float), ("sun_solid_angle", C.c_double), ("sun_texels", C.c_uint32),
+                ("kernel_ms", C.c_float)]
+
+
 PROJ_PERSPECTIVE, PROJ_ORTHOGRAPHIC, PROJ_EQUIRECT, PROJ_FISHEYE = range(4)
 PROJ_NAMES = ("perspective", "ortho", "equirect", "fisheye")
 
@@ -440,6 +455,8 @@ SYMBOLS = [
     ("pt_read_ao_counts", C.c_int, [C.c_void_p, C.c_void_p]),
     ("pt_debug_ao", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pt_get_ao_stats", C.c_int, [C.c_void_p, C.POINTER(AoStats)]),
+    ("pt_default_sky_options", None, [C.POINTER(SkyOptions)]),
+    ("pt_generate_sky", C.c_int, [C.c_void_p, C.POINTER(SkyOptions), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(SkyStats)]),
     ("pt_last_error", C.c_char_p, []),
     ("pt_get_constants", C.c_int, [C.c_void_p, C.POINTER(Constants)]),
     ("pt_get_lights", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),

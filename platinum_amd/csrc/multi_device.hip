@@ -728,6 +728,11 @@ int pt_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const 
   return dev_debug_math(is_group(r) ? r->group->shards[0] : r, fn, n, a, b, out0, out1);
 }
 
+// the sky generator needs no render: a group's first member answers
+int pt_generate_sky(pt_renderer* r, const pt_sky_options* options, uint32_t width, uint32_t height, float* rgba_out, pt_sky_stats* stats_out) {
+  return dev_generate_sky(is_group(r) ? r->group->shards[0] : r, options, width, height, rgba_out, stats_out);
+}
+
 // every member of a group holds the whole scene: the first one answers
 int pt_debug_lights(pt_renderer* r, uint32_t fn, uint32_t n, const pt_light_probe_args* args, const void* in, void* out) {
   return dev_debug_lights(is_group(r) ? r->group->shards[0] : r, fn, n, args, in, out);

@@ -1100,6 +1100,56 @@ int dev_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const
   return PT_OK;
 }
 
+// ---- sun and sky (sky.hip) ----
+extern "C" void pt_default_sky_options(pt_sky_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->sun_elevation = 0.5f;
+  o->sun_angular_radius = 0.004712f;
+  o->sun_intensity = 1.0f;
+  o->sun_disc = 1u;
+  o->altitude_km = 0.001f;
+  o->air_density = o->dust_density = o->ozone_density = 1.0f;
+  o->ground_albedo = 0.3f;
+}
+
+// One launch of k_sky into a buffer of its own, timed by events; Omega_d and the covered texels are counted on the host (pt_sky.h) and the
+// renderer's own state is untouched.  (The options and the size are checked before the renderer, as dev_debug_bloom.)
+int dev_generate_sky(pt_renderer* r, const pt_sky_options* o, uint32_t width, uint32_t height, float* rgba_out, pt_sky_stats* stats_out) {
+  if (!o || !rgba_out) return fail(PT_ERR_INVALID_ARGUMENT, "pt_generate_sky: null argument");
+  if (const char* why = sky_options_error(*o, width, height)) return fail(PT_ERR_INVALID_ARGUMENT, std::string("pt_generate_sky: ") + why);
+  if (!r) return fail(PT_ERR_INVALID_ARGUMENT, "pt_generate_sky: null renderer");
+  PT_HIP(hipSetDevice(r->device));
+  SkyParams P = sky_setup(*o, width, height);
+  uint32_t texels = 0;
+  const double omega = sky_solid_angle(P, &texels);
+  P.omega = o->sun_disc ? (float)omega : 0.0f;
+  const size_t n = (size_t)width * height;
+  DevBuf<vec4> img;
+  PT_HIP(img.alloc(n));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  PT_HIP(hipEventCreate(&e0));
+  hipError_t e = hipEventCreate(&e1);
+  if (e == hipSuccess) e = hipEventRecord(e0, r->stream);
+  if (e == hipSuccess) { launch_sky(r->stream, P, img.p); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipEventRecord(e1, r->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+  float ms = 0.0f;
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  PT_HIP(e);
+  PT_HIP(hipMemcpy(rgba_out, img.p, sizeof(vec4) * n, hipMemcpyDeviceToHost));
+  if (stats_out) {
+    stats_out->sun_direction[0] = P.s.x; stats_out->sun_direction[1] = P.s.y; stats_out->sun_direction[2] = P.s.z;
+    stats_out->sun_radius_used = P.alpha_eff;
+    stats_out->sun_solid_angle = omega;
+    stats_out->sun_texels = texels;
+    stats_out->kernel_ms = ms;
+  }
+  return PT_OK;
+}
+
 // one elementwise launch of light_probe.hip on uploaded records against the started render's scene table; the render's state is untouched.
 // The draws and directions are checked on the host first: shade_nee_light and stage_miss index tables with them, and a draw outside [0, 1)
 // (a NaN too) would walk the light search or the alias table out of bounds.

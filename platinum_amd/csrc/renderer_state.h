@@ -22,6 +22,7 @@
 #include "projection.h"
 #include "pt_math_probe.h"
 #include "selection.h"
+#include "sky.h"
 #include "view.h"
 #include "kernels.h"
 #include "pt_bvh.h"
@@ -332,6 +333,7 @@ int dev_set_profiling(pt_renderer* r, int enabled);
 int dev_get_stats(pt_renderer* r, pt_stats* out);
 int dev_read_aov(pt_renderer* r, uint32_t aov, float* rgba_out);
 int dev_debug_math(pt_renderer* r, uint32_t fn, uint32_t n, const void* a, const void* b, void* out0, void* out1);
+int dev_generate_sky(pt_renderer* r, const pt_sky_options* o, uint32_t width, uint32_t height, float* rgba_out, pt_sky_stats* stats_out);
 int dev_debug_lights(pt_renderer* r, uint32_t fn, uint32_t n, const pt_light_probe_args* args, const void* in, void* out);
 int dev_debug_shading(pt_renderer* r, uint32_t n, const void* in, void* out);
 int dev_set_adaptive_options(pt_renderer* r, const pt_adaptive_options* o);

@@ -305,6 +305,24 @@ class Renderer:
                                                       None if pyr is None or pyr.size == 0 else pyr.ctypes.data))
         return (out, pyr) if pyramid else out
 
+    # sun and sky (include/ptamd.h, an additive extension of ABI 5): no reference counterpart
+    def skyOptions(self, **fields):
+        """pt_default_sky_options with `fields` over them, e.g. skyOptions(sun_elevation=0.1, dust_density=3)."""
+        o = abi.SkyOptions()
+        self._lib.pt_default_sky_options(C.byref(o))
+        for k, v in fields.items():
+            setattr(o, k, v)
+        return o
+
+    def generateSky(self, options=None, width=1024, height=512, stats=False, **fields):
+        """pt_generate_sky: the (height, width, 4) float32 lat-long image of the single-scattering sky under `options` (default: skyOptions
+        of `fields`), in the environment map's layout; with stats=True (image, abi.SkyStats).  Needs no started render."""
+        o = self.skyOptions(**fields) if options is None else options
+        out = np.empty((height, width, 4), np.float32)
+        st = abi.SkyStats()
+        abi.check(self._lib, self._lib.pt_generate_sky(self._h, C.byref(o), width, height, out.ctypes.data, C.byref(st)))
+        return (out, st) if stats else out
+
     # tile-adaptive sampling (include/ptamd.h, an additive extension of ABI 5): no reference counterpart
     def adaptiveOptions(self):
         """The options in effect (pt_default_adaptive_options until setAdaptiveOptions is called)."""

@@ -336,6 +336,18 @@ class Scene:
         self.camera = camera
         self.camera_world = transform.matrix() if isinstance(transform, Transform) else np.asarray(transform, dtype=f32)
 
+    def set_environment(self, rgba):
+        """An (H, W, 4) float32 lat-long image becomes the scene's environment (no host alias table: the library builds its own)."""
+        self.env_texture = self.add_texture(rgba, abi.TEX_RGBA32F)
+        self.env_alias = None
+
+    def set_sky(self, renderer, width=1024, height=512, **options):
+        """A physical sun and sky as the environment: `renderer`.generateSky (pt_generate_sky) with pt_sky_options
+        fields as keywords, e.g. set_sky(r, sun_elevation=0.2, sun_azimuth=1.0, dust_density=2).  Returns the abi.SkyStats."""
+        img, st = renderer.generateSky(width=width, height=height, stats=True, **options)
+        self.set_environment(img)
+        return st
+
     @property
     def triangle_count(self):
         return sum(self.meshes[n.mesh].triangle_count for n in self.nodes)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/kernel_resources.sh [extra hipcc flags] — VGPRs / scratch / spills / occupancy / LDS of every kernel of the device files named in
 # `units` as the Makefile compiles them (LLVM's kernel-resource-usage remarks; no GPU needed).  Exits 1 with the compiler's output when a file fails.
-units="kernels trace_kernels denoise adaptive exposure bloom matte selection film ao view camera_lists projection"
+units="kernels trace_kernels denoise adaptive exposure bloom matte selection film ao view camera_lists projection sky"
 cd "$(dirname "${BASH_SOURCE[0]}")/../platinum_amd/csrc"
 
 # device_compile <unit> <flags...>: the device pass of one unit under the Makefile's flags (HIPFLAGS without the warnings; its rules for kernels.o

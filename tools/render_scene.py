@@ -19,6 +19,7 @@ tracing (GMoN optional), fused post-process + tonemap — to an 8-bit PNG.
     python tools/render_scene.py builtin:c3 heat.png --size 960 540 --spp 256 --adaptive 0.05 --view samples --ramp heat
     python tools/render_scene.py builtin:c5 probe.png --size 1024 512 --spp 64 --projection equirect     (a light probe of the scene)
     python tools/render_scene.py builtin:c5 dome.png --size 1024 1024 --spp 64 --projection fisheye --fisheye-fov 3.14159
+    python tools/render_scene.py model.glb evening.png --env daylight --sun-elevation 8 --sun-azimuth 200 --turbidity 3 --auto-exposure
     python tools/render_scene.py plan.gltf plan.png --projection ortho --ortho-height 12     (a glTF orthographic camera is used as it is)
 """
 import argparse, os, struct, sys, time, zlib
@@ -57,7 +58,13 @@ def main():
     ap.add_argument("--gmon", type=int, default=0, help="GMoN bucket count (0 = plain mean)")
     ap.add_argument("--camera-pos", type=float, nargs=3); ap.add_argument("--camera-target", type=float, nargs=3, default=(0, 0, 0))
     ap.add_argument("--focal", type=float, default=28.0)
-    ap.add_argument("--env", default="none", help="'sky' = procedural sky, or the path of an .exr / Radiance .hdr environment map")
+    ap.add_argument("--env", default="none", help="'sky' = procedural sky, 'daylight' = a physical sun and sky generated on the device (see "
+                                                  "--sun-elevation), or the path of an .exr / Radiance .hdr environment map")
+    ap.add_argument("--sun-elevation", type=float, default=30.0, metavar="DEG", help="with --env daylight: the sun's height over the horizon, -90 .. 90")
+    ap.add_argument("--sun-azimuth", type=float, default=0.0, metavar="DEG", help="with --env daylight: the sun's azimuth (0 = towards -x, 90 = towards -z)")
+    ap.add_argument("--sun-size", type=float, default=0.27, metavar="DEG", help="with --env daylight: the sun's angular radius")
+    ap.add_argument("--turbidity", type=float, default=1.0, metavar="D", help="with --env daylight: dust density relative to a clear day, 0 .. 10")
+    ap.add_argument("--sky-size", default="1024x512", metavar="WxH", help="with --env daylight: the size of the generated environment map")
     ap.add_argument("--exposure", type=float, default=0.0)
     ap.add_argument("--auto-exposure", type=float, nargs="?", const=-2.4739313, default=None, metavar="TARGET_LOG2",
                     help="meter the image's luminance histogram and bring its mean to 2^TARGET_LOG2 (default log2 0.18) ahead of the post-process; "
@@ -140,13 +147,23 @@ def main():
             a.scene, scene_io.GLTF_SKIP_EMPTY_NODES | scene_io.GLTF_ORTHOGRAPHIC_CAMERAS)
         if a.env == "sky":
             sc.set_environment(scenes.sky_environment(1024, 512))
-        elif a.env != "none":
+        elif a.env not in ("none", "daylight"):
             sc.load_environment(a.env)
         if a.camera_pos is not None or not sc.cameras():
             sc.add_camera(a.camera_pos or (0.0, 1.5, 6.0), a.camera_target, a.focal)
         c = sc.counts()
         print(f"scene: {c.instances} instances, {c.triangles} triangles, {c.textures} textures, {c.materials} materials, cameras {sc.cameras()}")
     r = Renderer(device=0)
+    if a.env == "daylight":   # (a built-in scene takes it too: it replaces the scene's own environment)
+        try:
+            sky_w, sky_h = (int(v) for v in a.sky_size.lower().split("x"))
+            sky, ss = r.generateSky(width=sky_w, height=sky_h, stats=True, sun_elevation=np.radians(a.sun_elevation), sun_azimuth=np.radians(a.sun_azimuth),
+                                    sun_angular_radius=np.radians(a.sun_size), dust_density=a.turbidity)
+        except (ValueError, abi.PtamdError) as e:
+            ap.error("--env daylight: %s" % e)
+        sc.set_environment(sky)
+        print(f"daylight: {sky_w} x {sky_h} in {ss.kernel_ms:.2f} ms on the device; the sun covers {ss.sun_texels} texels "
+              f"({ss.sun_solid_angle:.3g} sr, radius {np.degrees(ss.sun_radius_used):.3g} deg)")
     # the projection: the scene camera's own (a glTF orthographic camera), with the command line over it
     proj = sc.camera_projection() if isinstance(sc, scene_io.SceneFile) else r.projection()
     if a.projection is not None:
